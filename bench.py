@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the dj_brdf hot path on MI355X, one JSON line on rank 0.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--n PAIRS]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--n PAIRS] [--full] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over one batch of synthetic input that is already resident
-in HBM (directions generated on-device by the counter hash of dj_brdf_amd/synth.py).
+in HBM (directions generated on-device by the counter hash of dj_brdf_amd/synth.py).  A plain run sets up,
+warms up, times K steps and prints the line; --full adds the CPU baseline and the secondary legs below.
 
 Workloads (BASELINE.json configs):
   merl_eval        configs[2]: MERL tabulated eval (nearest-bin, bit-exact index) over 1e9 (wi,wo)
@@ -23,7 +24,7 @@ batch on its own device ("weak" scaling), there is NO data-path collective; the 
 communication is the barrier and the MAX-over-ranks of the timed region.
 
 Extra objects in the JSON line:
-  secondary     (default workload only) BASELINE.json's second figure, the 100-material MERL fit on N GPUs
+  secondary     (--full, default workload only) BASELINE.json's second figure, the 100-material MERL fit on N GPUs
                 (material m -> rank m mod N, "strong", no exchange):
                   merl_fit_files_100  END TO END, what examples/merl_params.cpp:53-69 does: 100 files of
                                       34 992 012 B on local disk -> pread -> PCIe -> k_merl_convert -> one fit
@@ -36,7 +37,7 @@ Extra objects in the JSON line:
                                       the same source (examples/scalar_latency.cpp, oracle/_ref/scalar_latency)
   roofline      dominant kernel: algorithmic bytes per launch / average launch duration
                 (HIP events on the ctx stream over the timed region) vs the 8 TB/s HBM peak
-  cpu_baseline  the CPU path timed on this host (rank 0, N=1 only) on a bounded sample:
+  cpu_baseline  (--full) the CPU path timed on this host (rank 0, N=1 only) on a bounded sample:
                 kind "reference" = the real dj_brdf.h via oracle/_ref (prebuilt), else
                 "port" = oracle/djb_oracle.c
 """
@@ -190,15 +191,24 @@ def parse():
     ap.add_argument("--n", type=int, default=None, help="units per GPU per step (default: the BASELINE config size)")
     ap.add_argument("--alpha", type=float, default=0.3, help="ggx_eval_pdf: isotropic roughness (SURVEY 8d extra points 0.05 / 0.8)")
     ap.add_argument("--fresnel", default="ideal", choices=["ideal", "schlick"], help="ggx_eval_pdf: ideal (default) or schlick(1.0, 0.71, 0.29)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline and, for the default merl_eval "
+                         "workload, the secondary legs (other configurations, fits, plugin operators, one-pair calls, order lever)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary legs")
     ap.add_argument("--merl-dir", default=None,
-                    help="a directory of real MERL files (*.binary): the end-to-end files -> alphas leg also runs on them "
+                    help="a directory of real MERL files (*.binary): with --full the end-to-end files -> alphas leg also runs on them "
                          "(secondary.merl_fit_dir; examples/merl_params.cpp:53-69 is the loop it stands for).  The offline image has none.")
     ap.add_argument("--selftest-n", type=int, default=None,
                     help="harness self-test only (DJB_BENCH_SHARE_GPU runs of the N-rank path on one GPU): shrink the primary batch "
-                         "to this many units per rank but keep the secondary fit legs; the line is labelled")
-    return ap.parse_args()
+                         "to this many units per rank but keep the secondary fit legs (with --full); the line is labelled")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write every array the last step computed as DIR/<name>.npy (float32); of a batch "
+                         f"longer than {DUMP_UNITS} units only a fixed sample of {DUMP_UNITS}, the same in every run with the same arguments")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 GGX_ALPHA, GGX_FRESNEL = 0.3, "ideal"       # overridden by --alpha / --fresnel
@@ -292,8 +302,26 @@ def finish(step):
     getattr(step, "cleanup", lambda: None)()
 
 
+DUMP_UNITS = 1 << 20      # --dump-outputs: units kept of a longer batch (12 MB of a [3, n] float32 output, 28 MB for evalp_is)
+
+
+def dump_outputs(outputs, d, torch):
+    """--dump-outputs: every array of the last timed step as <d>/<name>.npy in float32.  Of a batch longer than DUMP_UNITS units (the
+    last axis) only the units at DUMP_UNITS indices drawn without replacement by a generator of fixed seed, in ascending order: the same
+    units in every run with the same arguments, so that two builds can be compared output for output."""
+    os.makedirs(d, exist_ok=True)
+    for name, a in outputs.items():
+        n = a.shape[-1]
+        if n > DUMP_UNITS:
+            idx = np.sort(np.random.default_rng(0).choice(n, DUMP_UNITS, replace=False))
+            a = a.index_select(a.dim() - 1, torch.from_numpy(idx).to(a.device)) if isinstance(a, torch.Tensor) else a[..., idx]
+        a = a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        np.save(os.path.join(d, name + ".npy"), a.astype(np.float32))
+
+
 def make_step(name, n, djb, synth, ctx, torch):
-    """Returns (step_fn, keepalive).  Inputs are generated on-device before the timed region."""
+    """Returns (step_fn, keepalive).  Inputs are generated on-device before the timed region.  step_fn.outputs() names the arrays
+    the last call of step_fn computed (what a caller of the operator receives; --dump-outputs)."""
     if name == "merl_eval":
         i = djb.gen_directions(n, synth.SEED_I, ctx=ctx)
         o = djb.gen_directions(n, synth.SEED_O, ctx=ctx)
@@ -305,6 +333,7 @@ def make_step(name, n, djb, synth, ctx, torch):
         def step():
             djb._lib.check(lib.djb_eval_batch(ctx._h, m._h, C.c_int64(n), C.byref(vi.view), C.byref(vo.view),
                                               None, C.byref(vout.view), C.c_int(0)))
+        step.outputs = lambda: {"eval": out}
         return step, (i, o, m, out, vi, vo, vout)
     if name in ("merl_eval_uniform_bins", "merl_eval_coherent"):
         i, o = merl_pairs(name, n, djb, torch, ctx)
@@ -316,6 +345,7 @@ def make_step(name, n, djb, synth, ctx, torch):
         def step():
             djb._lib.check(lib.djb_eval_batch(ctx._h, m._h, C.c_int64(n), C.byref(vi.view), C.byref(vo.view),
                                               None, C.byref(vout.view), C.c_int(0)))
+        step.outputs = lambda: {"eval": out}
         return step, (i, o, m, out, vi, vo, vout)
     if name in ("sgd_eval", "sgd_eval_contract"):
         i = djb.gen_directions(n, synth.SEED_I, ctx=ctx)
@@ -327,6 +357,7 @@ def make_step(name, n, djb, synth, ctx, torch):
         def step():
             djb._lib.check(lib.djb_eval_batch(ctx._h, m._h, C.c_int64(n), C.byref(vi.view), C.byref(vo.view),
                                               None, C.byref(vout.view), C.c_int(0)))
+        step.outputs = lambda: {"eval": out}
         return contract_mode(step, name, djb, ctx), (i, o, m, None, out, vi, vo, vout)
     if name in ("ggx_eval_pdf", "ggx_eval_pdf_contract", "ggx_unpolarized_eval_pdf", "ggx_unpolarized_eval_pdf_contract"):
         i = djb.gen_directions(n, synth.SEED_I, ctx=ctx)
@@ -344,6 +375,7 @@ def make_step(name, n, djb, synth, ctx, torch):
             djb._lib.check(lib.djb_eval_pdf_batch(ctx._h, g._h, C.c_int64(n), C.byref(vi.view), C.byref(vo.view),
                                                   C.byref(p._p), C.c_int(0), C.byref(vout.view),
                                                   C.c_void_p(pdf.data_ptr()), C.c_int(0)))
+        step.outputs = lambda: {"eval": out, "pdf": pdf}
         return contract_mode(step, name, djb, ctx), (i, o, g, p, out, pdf, vi, vo, vout)
     if name in ("beckmann_sample", "beckmann_sample_contract"):
         o = djb.gen_directions(n, synth.SEED_O, ctx=ctx)
@@ -357,6 +389,7 @@ def make_step(name, n, djb, synth, ctx, torch):
             djb._lib.check(lib.djb_sample_rng_batch(ctx._h, b._h, C.c_int64(n), C.c_uint32(synth.SEED_U1),
                                                     C.c_uint32(synth.SEED_U2), C.c_uint64(0), C.byref(vo.view),
                                                     C.byref(p._p), C.byref(vout.view)))
+        step.outputs = lambda: {"sample": out}
         return contract_mode(step, name, djb, ctx), (o, out, b, p, vo, vout)
     if name in ("utia_eval", "utia_eval_contract"):
         i = djb.gen_directions(n, synth.SEED_I, ctx=ctx)
@@ -370,6 +403,7 @@ def make_step(name, n, djb, synth, ctx, torch):
         def step():
             djb._lib.check(lib.djb_eval_batch(ctx._h, u._h, C.c_int64(n), C.byref(vi.view), C.byref(vo.view),
                                               None, C.byref(vout.view), C.c_int(0)))
+        step.outputs = lambda: {"eval": out}
         return contract_mode(step, name, djb, ctx), (i, o, u, out, vi, vo, vout)
     if name in PLUGIN_LEGS:
         return plugin_leg_step(name, n, djb, synth, ctx, torch)
@@ -380,6 +414,7 @@ def make_step(name, n, djb, synth, ctx, torch):
 
         def step():
             result["alphas"] = djb.fit_brdf_batch(mats, 90, True, ctx=ctx)
+        step.outputs = lambda: dict(zip(("alpha_beckmann", "alpha_ggx"), result["alphas"]))
         return step, (mats, result)
     if name == "merl_fit_files":
         from dj_brdf_amd import merl_params
@@ -387,7 +422,8 @@ def make_step(name, n, djb, synth, ctx, torch):
         result = {}
 
         def step():
-            ab, ag, result["timing"] = merl_params.fit_files_on(ctx, paths)
+            result["alpha_beckmann"], result["alpha_ggx"], result["timing"] = merl_params.fit_files_on(ctx, paths)
+        step.outputs = lambda: {k: result[k] for k in ("alpha_beckmann", "alpha_ggx")}
         return step, (paths, result)
     raise ValueError(name)
 
@@ -405,16 +441,32 @@ def plugin_leg_step(name, n, djb, synth, ctx, torch):
     lib, C = djb._lib.load(), ctypes
     chk = djb._lib.check
     dev = f"cuda:{ctx.device}"
+    # the fits: one object construction per step; the object of the step before is closed first (one construction and one close
+    # per step, one object alive at a time), so that the last step's tables are still there for --dump-outputs
+    last = []
     if name == "fit_tabular_90":
         src = djb.merl.from_table(synth.merl_table(*synth.material_recipe(0)), ctx=ctx)
         def step():
-            djb.tabular(src, 90, True, ctx=ctx).close()
-        return step, (src,)
+            if last:
+                last.pop().close()
+            last.append(djb.tabular(src, 90, True, ctx=ctx))
+        step.outputs = lambda: {"p22": last[0].get_p22v(), "sigma": last[0].get_sigmav(), "cdf": last[0].get_cdfv(), "qf": last[0].get_qfv(),
+                                "fresnel": last[0].get_fresnel().get_points(), "alphas": np.array(last[0]._alphas())}
+        return step, (src, last)
     if name == "fit_aniso_90x90":
         src = djb.utia.from_table(utia_payload(), ctx=ctx)
         def step():
-            djb.tabular_anisotropic(src, 90, 90, True, ctx=ctx).close()
-        return step, (src,)
+            if last:
+                last.pop().close()
+            last.append(djb.tabular_anisotropic(src, 90, 90, True, ctx=ctx))
+        def outputs():
+            t = last[0]
+            out = {"p22": t.get_p22v()[0], "sigma": t.get_sigmav()[0], "fresnel": t.get_fresnel().get_points()}
+            out.update((k, t.get_table(k)) for k in ("pdf1", "cdf1", "qf1", "pdf2", "cdf2", "qf2"))
+            out.update(zip(("fit_beckmann", "fit_ggx"), (np.array(list(p.v)) for p in t._fits())))
+            return out
+        step.outputs = outputs
+        return step, (src, last)
     o = djb.gen_directions(n, synth.SEED_O, ctx=ctx)
     vo = djb._Vec(o)
     if name.startswith("tabular_aniso"):
@@ -440,6 +492,7 @@ def plugin_leg_step(name, n, djb, synth, ctx, torch):
         def step():
             chk(lib.djb_sample_rng_batch(ctx._h, b._h, C.c_int64(n), C.c_uint32(synth.SEED_U1), C.c_uint32(synth.SEED_U2), C.c_uint64(0),
                                          C.byref(vo.view), None, C.byref(vout.view)))
+        step.outputs = lambda: {"sample": out}
         return step, (o, out, b, src, vo, vout)
     if name.endswith("_evalp_is"):
         u1 = djb.gen_uniforms(n, synth.SEED_U1, ctx=ctx); u2 = djb.gen_uniforms(n, synth.SEED_U2, ctx=ctx)
@@ -449,12 +502,14 @@ def plugin_leg_step(name, n, djb, synth, ctx, torch):
         def step():
             chk(lib.djb_evalp_is_batch(ctx._h, b._h, C.c_int64(n), C.c_void_p(u1.data_ptr()), C.c_void_p(u2.data_ptr()), C.byref(vo.view),
                                        C.byref(p._p), C.byref(vout.view), C.byref(vwi.view), C.c_void_p(pdf.data_ptr()), C.c_int(0)))
+        step.outputs = lambda: {"weight": out, "i": wi, "pdf": pdf}
         return step, (o, out, b, p, u1, u2, wi, pdf, vo, vout, vwi)
     i = djb.gen_directions(n, synth.SEED_I, ctx=ctx)
     vi = djb._Vec(i)
     if name == "abc_evalp":
         def step():
             chk(lib.djb_evalp_batch(ctx._h, b._h, C.c_int64(n), C.byref(vi.view), C.byref(vo.view), None, C.byref(vout.view), C.c_int(0)))
+        step.outputs = lambda: {"evalp": out}
         return step, (i, o, out, b, vi, vo, vout)
     pdf = torch.empty((n,), dtype=torch.float32, device=dev)
     if name == "lean_evalp_pdf":
@@ -467,10 +522,12 @@ def plugin_leg_step(name, n, djb, synth, ctx, torch):
         def step():
             chk(lib.djb_eval_lean_batch(ctx._h, b._h, C.c_int64(n), C.byref(vi.view), C.byref(vo.view), C.byref(base._p), C.c_float(1.0), C.c_int(0),
                                         C.c_void_p(lean.data_ptr()), C.c_int(6), C.byref(vout.view), C.c_void_p(pdf.data_ptr()), C.c_void_p(0), C.c_int(0)))
+        step.outputs = lambda: {"evalp": out, "pdf": pdf}
         return step, (i, o, out, pdf, b, base, lean, vi, vo, vout)
     def step():             # tabular / tabular_anisotropic eval + pdf fused
         chk(lib.djb_eval_pdf_batch(ctx._h, b._h, C.c_int64(n), C.byref(vi.view), C.byref(vo.view), None, C.c_int(0), C.byref(vout.view),
                                    C.c_void_p(pdf.data_ptr()), C.c_int(0)))
+    step.outputs = lambda: {"eval": out, "pdf": pdf}
     return step, (i, o, out, pdf, b, src, vi, vo, vout)
 
 
@@ -909,11 +966,13 @@ def main():
         t = torch.tensor([dt, ev_ms], dtype=torch.float64, device=red_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt, ev_ms = float(t[0]), float(t[1])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(step.outputs(), args.dump_outputs, torch)
 
     # BASELINE.json's second figure: wall time of the 100-material MERL fit on N GPUs (strong scaling:
     # material m -> rank m mod N, no exchange; tables resident in HBM).  Every rank takes part.
     fit100 = fitfiles = None
-    want_secondary = not args.no_secondary and name == "merl_eval" and args.n is None
+    want_secondary = args.full and not args.no_secondary and name == "merl_eval" and args.n is None
     finish(step)
     if want_secondary:
         del step, keep
@@ -1111,7 +1170,7 @@ def main():
             rec["scaling_model_ms"] = scaling_model_ms(world)
         if name == "merl_fit_files":
             rec["pipeline"] = keep[1].get("timing")   # last step: total / load (read+upload+convert) / fit seconds
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             rec["cpu_baseline"] = cpu_baseline(name, synth)
         if want_secondary and world > 1:
             rec["secondary"] = {"merl_fit_files_100": fitfiles, "merl_fit_100": fit100}

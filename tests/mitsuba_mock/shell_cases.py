@@ -54,7 +54,8 @@ def build(side, shells=SHELLS, quiet=True):
             src = f"/root/reference/mitsuba/{s}.cpp"
             inc = ["-I", os.path.join(ROOT, "include")]
             lib = os.path.join(ROOT, "dj_brdf_amd", "lib")
-            link = ["-L", lib, "-ldjb_hip", f"-Wl,-rpath,{lib}"]
+            # rpath relative to the shell itself: the tree is built in one directory and may be run from another
+            link = ["-L", lib, "-ldjb_hip", "-Wl,-rpath,$ORIGIN/" + os.path.relpath(lib, out)]
             deps = [src] + [os.path.join(ROOT, "include", f) for f in ("djb_hip.h", "djb_hip.hpp", "dj_brdf.h")]
             flags = ["-w"]
         elif side == "ref":
@@ -66,7 +67,8 @@ def build(side, shells=SHELLS, quiet=True):
             src = os.path.join(ROOT, "mitsuba", f"{s}.cpp")
             inc = ["-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "mitsuba")]
             lib = os.path.join(ROOT, "dj_brdf_amd", "lib")
-            link = ["-L", lib, "-ldjb_hip", f"-Wl,-rpath,{lib}"]
+            # rpath relative to the shell itself: the tree is built in one directory and may be run from another
+            link = ["-L", lib, "-ldjb_hip", "-Wl,-rpath,$ORIGIN/" + os.path.relpath(lib, out)]
             deps = [src] + [os.path.join(ROOT, "mitsuba", f) for f in os.listdir(os.path.join(ROOT, "mitsuba")) if f.endswith(".hpp")] \
                 + [os.path.join(ROOT, "include", f) for f in ("djb_hip.h", "djb_hip.hpp")]
             flags = ["-Wall", "-Wno-unused-parameter"]

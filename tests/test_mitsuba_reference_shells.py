@@ -24,6 +24,9 @@ def run_side(tmp_path, which, env_extra, drop=()):
         pytest.skip("oracle/_ref/shells_on_facade not built (needs /root/reference at build time)")
     out = str(tmp_path / f"refsrc_{which}.npz")
     env = {k: v for k, v in os.environ.items() if k not in drop}
+    # the shells load this tree's libdjb_hip.so: oracle/_ref may be a link to a directory outside the tree, from where
+    # no rpath of the shells leads back to dj_brdf_amd/lib
+    env["LD_LIBRARY_PATH"] = os.pathsep.join(p for p in (os.path.join(ROOT, "dj_brdf_amd", "lib"), env.get("LD_LIBRARY_PATH")) if p)
     env.update(env_extra, DJB_QUIET="1")
     r = subprocess.run([sys.executable, CASES, "--side", "refsrc", "--which", which, "--prebuilt", "--out", out], capture_output=True, text=True, env=env, timeout=1500)
     assert r.returncode == 0, (r.stdout + r.stderr)[-6000:]

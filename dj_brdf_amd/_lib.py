@@ -69,6 +69,8 @@ EXPORTS = [
     "djb_gen_directions", "djb_gen_uniforms", "djb_histogram_xy", "djb_helper",
     "djb_set_file_map_observer", "djb_brdf_create_user_microfacet", "djb_fit_query_dirs", "djb_fit_aniso_query_dirs", "djb_brdf_create_tabular_from_samples",
     "djb_brdf_create_tabular_anisotropic_from_samples",
+    "djb_dmap_to_nmap", "djb_leanmap_create_from_nmap", "djb_leanmap_create_from_dmap", "djb_leanmap_create_from_moments", "djb_leanmap_info",
+    "djb_leanmap_get_level", "djb_leanmap_destroy", "djb_leanmap_lookup_batch", "djb_eval_leanmap_batch", "djb_sample_leanmap_batch",
 ]
 
 _lib = None

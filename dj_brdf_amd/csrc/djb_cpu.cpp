@@ -943,6 +943,60 @@ djb_status sample_pp(djb_ctx *ctx, const djb_brdf *b_, int64_t n, const float *u
 	return DJB_OK;
 }
 
+// ------------------------------------------------------------------ LEAN maps: the per-texel code of djb_leanmap.inc in host loops
+void dmap_to_nmap(djb_ctx *ctx, int w, int h, const unsigned char *dmap, float scale, unsigned char *rgb)
+{
+	parallel_for(C(ctx), (long long)w * h, 1 << 14, [=](long long k0, long long k1) {
+		for (long long k = k0; k < k1; ++k) dmap_to_nmap_texel(dmap, w, h, (int)(k % w), (int)(k / w), scale, rgb + 3 * k);
+	});
+}
+void leanmap_level0_from_nmap(djb_ctx *ctx, int w, int h, const unsigned char *rgb, int pixel_stride, float base_roughness, float *texels)
+{
+	parallel_for(C(ctx), (long long)w * h, 1 << 14, [=](long long k0, long long k1) {
+		for (long long k = k0; k < k1; ++k) {
+			const unsigned char *px = rgb + (long long)pixel_stride * k;
+			float e[5];
+			nmap_to_lean_texel(px[0], px[1], px[2], base_roughness, e);
+			leanmap_store((float4 *)texels + 2 * k, e);
+		}
+	});
+}
+void leanmap_level0_from_moments(djb_ctx *ctx, int w, int h, const float *moments5, bool biased, float *texels)
+{
+	parallel_for(C(ctx), (long long)w * h, 1 << 14, [=](long long k0, long long k1) {
+		for (long long k = k0; k < k1; ++k) {
+			float e[5];
+			for (int c = 0; c < 5; ++c) e[c] = moments5[5 * k + c];
+			if (biased) { e[0] -= 25.0f; e[1] -= 25.0f; e[4] -= 625.0f; }
+			leanmap_store((float4 *)texels + 2 * k, e);
+		}
+	});
+}
+void leanmap_build_pyramid(djb_ctx *ctx, int lw, int lh, float *texels)
+{
+	float4 *t = (float4 *)texels;
+	for (int l = 1; l < leanmap_levels(lw, lh); ++l) {
+		const int ws = 1 << (lw > l - 1 ? lw - (l - 1) : 0), hs = 1 << (lh > l - 1 ? lh - (l - 1) : 0);
+		const int wd = 1 << (lw > l ? lw - l : 0), hd = 1 << (lh > l ? lh - l : 0);
+		const float4 *src = t + 2ull * leanmap_level_offset(lw, lh, l - 1);
+		float4 *dst = t + 2ull * leanmap_level_offset(lw, lh, l);
+		parallel_for(C(ctx), (long long)wd * hd, 1 << 13, [=](long long k0, long long k1) {
+			for (long long k = k0; k < k1; ++k) {
+				float e[5];
+				leanmap_downsample_texel(src, ws, hs, (int)(k % wd), (int)(k / wd), e);
+				leanmap_store(dst + 2 * k, e);
+			}
+		});
+	}
+}
+void leanmap_lookup(djb_ctx *ctx, const float *texels, int lw, int lh, int64_t n, const float *uv, const float *lod, float *out5)
+{
+	const LeanSrc src{ { (const float4 *)texels, lw, lh }, uv, lod };
+	parallel_for(C(ctx), n, 4096, [=](long long k0, long long k1) {
+		for (long long k = k0; k < k1; ++k) leanmap_lookup_hit(src, k, out5 + 5 * k);
+	});
+}
+
 djb_status query(djb_ctx *ctx, const djb_brdf *b_, int which, int64_t n, const djb_vec3_view *a, const djb_vec3_view *bb,
                  const djb_vec3_view *c, const djb_params *params, const djb_vec3_view *out)
 {

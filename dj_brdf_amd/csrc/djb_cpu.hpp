@@ -89,6 +89,12 @@ djb_status eval_pp(djb_ctx *, const djb_brdf *, int64_t n, const djb_vec3_view *
 djb_status sample_pp(djb_ctx *, const djb_brdf *, int64_t n, const float *u1, const float *u2, const djb_vec3_view *o, const float *rec,
                      int mode, const float *base5, float scale, int lean_flags, const djb_vec3_view *out_w, const djb_vec3_view *out_i,
                      float *out_pdf, float *out_pp);
+// LEAN maps in host memory (djb_leanmap.inc on the host): texels = 8 floats per texel, every level (djbdev::leanmap_total_texels)
+void dmap_to_nmap(djb_ctx *, int w, int h, const unsigned char *dmap, float scale, unsigned char *rgb);
+void leanmap_level0_from_nmap(djb_ctx *, int w, int h, const unsigned char *rgb, int pixel_stride, float base_roughness, float *texels);
+void leanmap_level0_from_moments(djb_ctx *, int w, int h, const float *moments5, bool biased, float *texels);
+void leanmap_build_pyramid(djb_ctx *, int lw, int lh, float *texels);
+void leanmap_lookup(djb_ctx *, const float *texels, int lw, int lh, int64_t n, const float *uv, const float *lod, float *out5);
 djb_status query(djb_ctx *, const djb_brdf *, int which, int64_t n, const djb_vec3_view *a, const djb_vec3_view *b,
                  const djb_vec3_view *c, const djb_params *, const djb_vec3_view *out);
 djb_status io_hd(djb_ctx *, int64_t n, const djb_vec3_view *a, const djb_vec3_view *b, const djb_vec3_view *c,

@@ -686,5 +686,6 @@ DJB_DEV float atan2_to_f32(float y, float x, double scale, LdsTab) { return atan
 #include "djb_device_microfacet.inc"
 #include "djb_device_tables.inc"
 #include "djb_device_units.inc"
+#include "djb_leanmap.inc"          // LEAN maps: level 0, the pyramid, the filtered lookup
 
 } // namespace djbdev

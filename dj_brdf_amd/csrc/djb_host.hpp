@@ -110,6 +110,18 @@ struct djb_brdf {
 	mutable std::atomic<int> twin_built{0};
 };
 
+// a resident LEAN map (djb_leanmap.hip): the mip pyramid of the five slope moments, 32 bytes per texel, levels one after the
+// other (djb_leanmap.inc).  Immutable after its constructor returned.
+struct djb_leanmap {
+	int device;                      // of the creating context, < 0: a CPU context's map (kept here: the handle may outlive its context)
+	int lw, lh;                      // log2 of the size of level 0
+	float4 *dev = nullptr;           // GPU map: the pyramid in HBM
+	// CPU map: the pyramid.  GPU map: its host copy for the host twin (scalar-size DJB_MEM_HOST calls), made by the first such call
+	mutable std::vector<float> host;
+	mutable std::mutex host_mu;
+	mutable std::atomic<int> host_ready{0};
+};
+
 namespace djbh {
 
 djb_status fail(djb_status st, const char *fmt, ...);      // sets the thread's djb_last_error() message (djb_host.hip)
@@ -338,6 +350,23 @@ djb_status check_call(djb_ctx *ctx, const djb_brdf *b, long long n, int mem);
 // scalar-size DJB_MEM_HOST calls: the host twin of a GPU object, or NULL when the call belongs on the GPU (djb_host.hip)
 const djb_brdf *scalar_twin(const djb_ctx *ctx, const djb_brdf *b, long long n, int mem);
 djb_status cpu_pair_check(const djb_ctx *ctx, const djb_brdf *b);
+// LEAN maps (djb_leanmap.hip): the map belongs to the context; the pyramid in host memory (a GPU map's copy is made on first use)
+djb_status leanmap_check(const djb_ctx *ctx, const djb_leanmap *m);
+djb_status leanmap_host_texels(const djb_leanmap *m, const float **out);
+// the (u, v) pairs and lods of a per-hit call where the kernels read them: src->uv / src->lod are the caller's pointers on entry
+inline djb_status stage_leanmap_coords(Staged &sg, const float *uv, const float *lod, djbdev::LeanSrc *src)
+{
+	if (!uv) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null uv array");
+	if (sg.mem == DJB_MEM_DEVICE) { src->uv = uv; src->lod = lod; return DJB_OK; }
+	float *d = nullptr;
+	djb_status st = sg.alloc(sizeof(float) * 2 * (size_t)sg.n, (void **)&d);
+	if (st != DJB_OK) return st;
+	if (sg.n && (st = sg.copy(d, uv, sizeof(float) * 2 * (size_t)sg.n, hipMemcpyHostToDevice)) != DJB_OK) return st;
+	src->uv = d;
+	src->lod = nullptr;
+	if (lod && (st = sg.in_f(lod, &src->lod)) != DJB_OK) return st;
+	return DJB_OK;
+}
 // object construction helpers (djb_host.hip)
 djb_status alloc_brdf(djb_ctx *ctx, int kind, djb_brdf **out);
 djb_status upload_floats(djb_brdf *b, const float *host, size_t count, const float **dev_out);

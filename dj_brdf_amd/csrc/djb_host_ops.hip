@@ -683,11 +683,25 @@ try {
 }
 DJB_ABI_CATCH
 
+// mode 2 (the fused LEAN-map calls): the records are looked up in `hit->map` at (hit->uv, hit->lod); `rec` is not used
+struct LeanHit { const djb_leanmap *map; const float *uv, *lod; };
+// the host path's form of a mode 2 call: the records by the host lookup, then mode 1 (what the kernels do per lane)
+static djb_status leanmap_host_records(const djb_ctx *ctx, const LeanHit *hit, int64_t n, std::vector<float> *rec)
+{
+	const float *texels;
+	djb_status st = leanmap_host_texels(hit->map, &texels);
+	if (st != DJB_OK) return st;
+	rec->resize(5 * (size_t)n);
+	djbcpu::leanmap_lookup(is_cpu(ctx) ? const_cast<djb_ctx *>(ctx) : djbcpu::twin_ctx(), texels, hit->map->lw, hit->map->lh, n, hit->uv, hit->lod, rec->data());
+	return DJB_OK;
+}
+
 static djb_status eval_pp_common(djb_ctx *ctx, const djb_brdf *b, int64_t n, const djb_vec3_view *i,
                                  const djb_vec3_view *o, const float *rec, int mode, const float *base5,
-                                 float scale, int lean_flags, int want, const djb_vec3_view *out_fr, float *out_pdf, float *out_pp, int mem)
+                                 float scale, int lean_flags, int want, const djb_vec3_view *out_fr, float *out_pdf, float *out_pp, int mem,
+                                 const LeanHit *hit = nullptr)
 {
-	if (!b || !rec || !ctx) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null argument");
+	if (!b || !ctx || (hit ? !hit->uv : !rec)) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null argument");
 	const int bkind = djb_brdf_kind(b);
 	if (bkind > DJB_KIND_TABULAR && bkind != DJB_KIND_TABULAR_ANISO)
 		return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: per-pair params need a microfacet brdf");
@@ -695,12 +709,20 @@ static djb_status eval_pp_common(djb_ctx *ctx, const djb_brdf *b, int64_t n, con
 		return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: want must be eval(1)|evalp(2) and/or pdf(4)");
 	djb_status st = cpu_pair_check(ctx, b);
 	if (st != DJB_OK) return st;
-	if (is_cpu(ctx)) return n <= 0 ? DJB_OK : djbcpu::eval_pp(ctx, b, n, i, o, rec, mode, base5, scale, lean_flags, want, out_fr, out_pdf, out_pp);
-	if (const djb_brdf *tw = scalar_twin(ctx, b, n, mem)) return n <= 0 ? DJB_OK : djbcpu::eval_pp(djbcpu::twin_ctx(), tw, n, i, o, rec, mode, base5, scale, lean_flags, want, out_fr, out_pdf, out_pp);
+	if (hit && (st = leanmap_check(ctx, hit->map)) != DJB_OK) return st;
+	if (n < 0 && hit) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: negative batch size");
+	const djb_brdf *tw = is_cpu(ctx) ? nullptr : scalar_twin(ctx, b, n, mem);
+	if (is_cpu(ctx) || tw) {
+		if (n <= 0) return DJB_OK;
+		std::vector<float> looked_up;
+		if (hit) { if ((st = leanmap_host_records(ctx, hit, n, &looked_up)) != DJB_OK) return st; rec = looked_up.data(); mode = 1; }
+		return is_cpu(ctx) ? djbcpu::eval_pp(ctx, b, n, i, o, rec, mode, base5, scale, lean_flags, want, out_fr, out_pdf, out_pp)
+		                   : djbcpu::eval_pp(djbcpu::twin_ctx(), tw, n, i, o, rec, mode, base5, scale, lean_flags, want, out_fr, out_pdf, out_pp);
+	}
 	st = check_call(ctx, b, n, mem);
 	if (st != DJB_OK) return st;
 	std::lock_guard<std::recursive_mutex> call_lock(ctx->call_mu);
-	if (mem == DJB_MEM_HOST && n > SMALL_N && i && o && (!(want & 3) || out_fr)) {   // large host batch: chunked, both PCIe directions busy
+	if (!hit && mem == DJB_MEM_HOST && n > SMALL_N && i && o && (!(want & 3) || out_fr)) {   // large host batch: chunked, both PCIe directions busy
 		bool taken = false;
 		const bool wfr = (want & 3) != 0, wpdf = (want & 4) != 0;
 		std::vector<PipeArr> ins{ PipeArr::vec(i), PipeArr::vec(o), PipeArr::arr(rec, 5) }, outs;
@@ -720,7 +742,11 @@ static djb_status eval_pp_common(djb_ctx *ctx, const djb_brdf *b, int64_t n, con
 	float *dpdf = nullptr, *dpp = nullptr; const float *drec = rec;
 	if ((st = sg.in_vec(i, &vi)) != DJB_OK) return st;
 	if ((st = sg.in_vec(o, &vo)) != DJB_OK) return st;
-	if (mem == DJB_MEM_HOST) {
+	djbdev::LeanSrc src{ { nullptr, 0, 0 }, nullptr, nullptr };
+	if (hit) {
+		src.map = djbdev::LeanMap{ hit->map->dev, hit->map->lw, hit->map->lh };
+		if ((st = stage_leanmap_coords(sg, hit->uv, hit->lod, &src)) != DJB_OK) return st;
+	} else if (mem == DJB_MEM_HOST) {
 		float *d = nullptr;
 		if ((st = sg.alloc(sizeof(float) * 5 * (size_t)n, (void **)&d)) != DJB_OK) return st;
 		if (n && (st = sg.copy(d, rec, sizeof(float) * 5 * (size_t)n, hipMemcpyHostToDevice)) != DJB_OK) return st;
@@ -735,7 +761,7 @@ static djb_status eval_pp_common(djb_ctx *ctx, const djb_brdf *b, int64_t n, con
 			sg.out_raw.push_back({ dpp, { out_pp, sizeof(float) * 5 * (size_t)n } });
 		}
 	}
-	HIP_TRY(djbk::launch_eval_pp(ctx->stream, b->dev, n, vi, vo, drec, mode, base5, scale, lean_flags, vout, dpdf, dpp, want));
+	HIP_TRY(djbk::launch_eval_pp(ctx->stream, b->dev, n, vi, vo, drec, mode, base5, scale, lean_flags, vout, dpdf, dpp, want, hit ? &src : nullptr));
 	return sg.finish();
 }
 
@@ -766,9 +792,9 @@ DJB_ABI_CATCH
 static djb_status sample_pp_common(djb_ctx *ctx, const djb_brdf *b, int64_t n, const float *u1, const float *u2,
                                    const djb_vec3_view *o, const float *rec, int mode, const float *base5, float scale,
                                    int lean_flags, const djb_vec3_view *out_w, const djb_vec3_view *out_i, float *out_pdf,
-                                   float *out_pp, int mem)
+                                   float *out_pp, int mem, const LeanHit *hit = nullptr)
 {
-	if (!b || !rec || !ctx || !u1 || !u2) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null argument");
+	if (!b || !ctx || !u1 || !u2 || (hit ? !hit->uv : !rec)) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null argument");
 	const int bkind = djb_brdf_kind(b);
 	if (bkind > DJB_KIND_TABULAR && bkind != DJB_KIND_TABULAR_ANISO)
 		return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: per-pair params need a microfacet brdf");
@@ -776,13 +802,20 @@ static djb_status sample_pp_common(djb_ctx *ctx, const djb_brdf *b, int64_t n, c
 	if (is && !out_pdf) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null argument");
 	djb_status st = cpu_pair_check(ctx, b);
 	if (st != DJB_OK) return st;
-	if (is_cpu(ctx)) return n <= 0 ? DJB_OK : djbcpu::sample_pp(ctx, b, n, u1, u2, o, rec, mode, base5, scale, lean_flags, out_w, out_i, out_pdf, out_pp);
-	if (const djb_brdf *tw = scalar_twin(ctx, b, n, mem))
-		return n <= 0 ? DJB_OK : djbcpu::sample_pp(djbcpu::twin_ctx(), tw, n, u1, u2, o, rec, mode, base5, scale, lean_flags, out_w, out_i, out_pdf, out_pp);
+	if (hit && (st = leanmap_check(ctx, hit->map)) != DJB_OK) return st;
+	if (n < 0 && hit) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: negative batch size");
+	const djb_brdf *tw = is_cpu(ctx) ? nullptr : scalar_twin(ctx, b, n, mem);
+	if (is_cpu(ctx) || tw) {
+		if (n <= 0) return DJB_OK;
+		std::vector<float> looked_up;
+		if (hit) { if ((st = leanmap_host_records(ctx, hit, n, &looked_up)) != DJB_OK) return st; rec = looked_up.data(); mode = 1; }
+		return is_cpu(ctx) ? djbcpu::sample_pp(ctx, b, n, u1, u2, o, rec, mode, base5, scale, lean_flags, out_w, out_i, out_pdf, out_pp)
+		                   : djbcpu::sample_pp(djbcpu::twin_ctx(), tw, n, u1, u2, o, rec, mode, base5, scale, lean_flags, out_w, out_i, out_pdf, out_pp);
+	}
 	st = check_call(ctx, b, n, mem);
 	if (st != DJB_OK) return st;
 	std::lock_guard<std::recursive_mutex> call_lock(ctx->call_mu);
-	if (mem == DJB_MEM_HOST && n > SMALL_N && o && out_i) {          // large host batch: chunked, both PCIe directions busy
+	if (!hit && mem == DJB_MEM_HOST && n > SMALL_N && o && out_i) {          // large host batch: chunked, both PCIe directions busy
 		bool taken = false;
 		std::vector<PipeArr> ins{ PipeArr::arr(u1), PipeArr::arr(u2), PipeArr::vec(o), PipeArr::arr(rec, 5) }, outs{ PipeArr::vec(out_i) };
 		int kq = -1;
@@ -800,7 +833,11 @@ static djb_status sample_pp_common(djb_ctx *ctx, const djb_brdf *b, int64_t n, c
 	if ((st = sg.in_f(u1, &d1)) != DJB_OK) return st;
 	if ((st = sg.in_f(u2, &d2)) != DJB_OK) return st;
 	if ((st = sg.in_vec(o, &vo)) != DJB_OK) return st;
-	if (mem == DJB_MEM_HOST) {
+	djbdev::LeanSrc src{ { nullptr, 0, 0 }, nullptr, nullptr };
+	if (hit) {
+		src.map = djbdev::LeanMap{ hit->map->dev, hit->map->lw, hit->map->lh };
+		if ((st = stage_leanmap_coords(sg, hit->uv, hit->lod, &src)) != DJB_OK) return st;
+	} else if (mem == DJB_MEM_HOST) {
 		float *d = nullptr;
 		if ((st = sg.alloc(sizeof(float) * 5 * (size_t)n, (void **)&d)) != DJB_OK) return st;
 		if (n && (st = sg.copy(d, rec, sizeof(float) * 5 * (size_t)n, hipMemcpyHostToDevice)) != DJB_OK) return st;
@@ -818,7 +855,7 @@ static djb_status sample_pp_common(djb_ctx *ctx, const djb_brdf *b, int64_t n, c
 			sg.out_raw.push_back({ dpp, { out_pp, sizeof(float) * 5 * (size_t)n } });
 		}
 	}
-	HIP_TRY(djbk::launch_sample_pp(ctx->stream, b->dev, n, d1, d2, vo, drec, mode, base5, scale, lean_flags, vi, is ? &vw : nullptr, dpdf, dpp));
+	HIP_TRY(djbk::launch_sample_pp(ctx->stream, b->dev, n, d1, d2, vo, drec, mode, base5, scale, lean_flags, vi, is ? &vw : nullptr, dpdf, dpp, hit ? &src : nullptr));
 	return sg.finish();
 }
 
@@ -842,6 +879,42 @@ try {
 	djb_status st = djb_params_to_lrep(base, base5);
 	if (st != DJB_OK) return st;
 	return sample_pp_common(ctx, b, n, u1, u2, o, lean, 1, base5, scale, lean_flags, out_w, out_i, out_pdf, out_pdfparams, mem);
+}
+DJB_ABI_CATCH
+
+// the fused LEAN-map calls: per hit, the filtered lookup of the resident map, then what the _lean_ entries do with that record
+static djb_status leanmap_call_args(float scale, int lean_flags, const djb_params *base, float *base5)
+{
+	if (lean_flags & DJB_LEAN_BIASED) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: DJB_LEAN_BIASED does not apply to a LEAN map (it holds the unbiased moments)");
+	if (lean_flags & ~DJB_LEAN_NAIVE_MIP) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: unknown LEAN flag");
+	if (!(scale >= 0.0f)) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: Invalid scale");
+	return djb_params_to_lrep(base, base5);
+}
+
+djb_status djb_eval_leanmap_batch(djb_ctx *ctx, const djb_brdf *b, const djb_leanmap *map, int64_t n, const djb_vec3_view *i,
+                                  const djb_vec3_view *o, const float *uv, const float *lod, const djb_params *base, float scale,
+                                  int lean_flags, int want, const djb_vec3_view *out_fr, float *out_pdf, float *out_pdfparams, int mem)
+try {
+	float base5[5];
+	djb_status st = leanmap_call_args(scale, lean_flags, base, base5);
+	if (st != DJB_OK) return st;
+	if (!map) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null leanmap");
+	const LeanHit hit{ map, uv, lod };
+	return eval_pp_common(ctx, b, n, i, o, nullptr, 2, base5, scale, lean_flags, want, out_fr, out_pdf, out_pdfparams, mem, &hit);
+}
+DJB_ABI_CATCH
+
+djb_status djb_sample_leanmap_batch(djb_ctx *ctx, const djb_brdf *b, const djb_leanmap *map, int64_t n, const float *u1, const float *u2,
+                                    const djb_vec3_view *o, const float *uv, const float *lod, const djb_params *base, float scale,
+                                    int lean_flags, const djb_vec3_view *out_w, const djb_vec3_view *out_i, float *out_pdf,
+                                    float *out_pdfparams, int mem)
+try {
+	float base5[5];
+	djb_status st = leanmap_call_args(scale, lean_flags, base, base5);
+	if (st != DJB_OK) return st;
+	if (!map) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null leanmap");
+	const LeanHit hit{ map, uv, lod };
+	return sample_pp_common(ctx, b, n, u1, u2, o, nullptr, 2, base5, scale, lean_flags, out_w, out_i, out_pdf, out_pdfparams, mem, &hit);
 }
 DJB_ABI_CATCH
 

@@ -43,15 +43,23 @@ hipError_t launch_sample_contract_attack(hipStream_t s, const Brdf &b, const Par
 
 // per-pair params: rec = n x 5 floats; mode 0 = pdfparams records, mode 1 = LEAN texel moments composed with
 // base5 = params_to_lrep(base) (unscaled), scale = dmapscale, lean_flags = DJB_LEAN_* as dj_beckmannconductor does;
-// out_pp (optional, mode 1) receives the resolved pdfparams
+// out_pp (optional, modes 1 and 2) receives the resolved pdfparams.  mode 2 = mode 1 with the record of pair k looked up in a
+// resident LEAN map at (uv_k, lod_k): src is given, rec is not read
 hipError_t launch_eval_pp(hipStream_t s, const Brdf &b, long long n, const View &i, const View &o,
                           const float *rec, int mode, const float *base5, float scale, int lean_flags, const View &out,
-                          float *out_pdf, float *out_pp, int want);
+                          float *out_pdf, float *out_pp, int want, const djbdev::LeanSrc *src = nullptr);
 
 // sample (out_w == NULL) / evalp_is with the same per-pair records
 hipError_t launch_sample_pp(hipStream_t s, const Brdf &b, long long n, const float *u1, const float *u2, const View &o,
                             const float *rec, int mode, const float *base5, float scale, int lean_flags, const View &out_i,
-                            const View *out_w, float *out_pdf, float *out_pp);
+                            const View *out_w, float *out_pdf, float *out_pp, const djbdev::LeanSrc *src = nullptr);
+
+// LEAN maps (djb_leanmap.hip).  Images and texel blocks are device memory; texels: 2 float4 per texel, levels one after the other
+hipError_t launch_dmap_to_nmap(hipStream_t s, int w, int h, const unsigned char *dmap, float scale, unsigned char *rgb);
+hipError_t launch_leanmap_from_nmap(hipStream_t s, int w, int h, const unsigned char *rgb, int pixel_stride, float base_roughness, float4 *level0);
+hipError_t launch_leanmap_from_moments(hipStream_t s, int w, int h, const float *moments5, int biased, float4 *level0);
+hipError_t launch_leanmap_downsample(hipStream_t s, const float4 *src, int ws, int hs, float4 *dst, int wd, int hd);
+hipError_t launch_leanmap_lookup(hipStream_t s, const djbdev::LeanSrc &src, long long n, float *out5);
 
 // microfacet / radial queries; out.x holds scalar results (out.xyz for the Fresnel query)
 hipError_t launch_query(hipStream_t s, const Brdf &b, const Params &p, int which, long long n,

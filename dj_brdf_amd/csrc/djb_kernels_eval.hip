@@ -310,9 +310,11 @@ hipError_t launch_eval_kind(hipStream_t s, const Brdf &b, const Params &p, long 
 // (mitsuba/dj_beckmannconductor.cpp:291-319).  MODE 0: pdfparams records (ax, ay, rho, tx, ty) are
 // read per pair.  MODE 1: per-pair LEAN texel moments (E1..E5) are composed on the fly with the base
 // lobe, params = lrep_to_params(lrep(lean_k) * dmapscale + params_to_lrep(base)), and optionally written back.
+// MODE 2: the moments of pair k are the filtered lookup of a resident LEAN map at (uv_k, lod_k) (djb_leanmap.inc: up to 8 taps of
+// 32 bytes), then MODE 1's code on that record: what MODE 1 computes from the output of djb_leanmap_lookup_batch, by construction.
 template <int KIND, int WANT, int MODE, int FRK = -1>
 __global__ __launch_bounds__(BLOCK) void k_eval_pp(Brdf b, long long n, View vi, View vo, const float *rec,
-                                                   LeanCfg base, View vout, float *out_pdf, float *out_pp)
+                                                   LeanCfg base, View vout, float *out_pdf, float *out_pp, LeanSrc ls)
 {
 	__shared__ unsigned long long s_exp[KIND == KIND_BECKMANN ? 256 : 1];     // as in k_eval
 	constexpr bool ATANT = KIND == KIND_TABULAR || KIND == KIND_TABULAR_ANISO || KIND == KIND_SGD || FRK == FR_SPLINE;
@@ -323,7 +325,12 @@ __global__ __launch_bounds__(BLOCK) void k_eval_pp(Brdf b, long long n, View vi,
 	long long stride = (long long)gridDim.x * BLOCK;
 	for (long long k = (long long)blockIdx.x * BLOCK + threadIdx.x; k < n; k += stride) {
 		v3 fr = mk(0, 0, 0); float pdf = 0.0f;
-		pp_one<KIND, WANT, MODE, FRK>(b, load3(vi, k), load3(vo, k), rec + 5 * k, base, out_pp ? out_pp + 5 * k : nullptr, fr, pdf);
+		if constexpr (MODE == 2) {
+			float r[5];
+			leanmap_lookup_hit(ls, k, r);
+			pp_one<KIND, WANT, 1, FRK>(b, load3(vi, k), load3(vo, k), r, base, out_pp ? out_pp + 5 * k : nullptr, fr, pdf);
+		} else
+			pp_one<KIND, WANT, MODE, FRK>(b, load3(vi, k), load3(vo, k), rec + 5 * k, base, out_pp ? out_pp + 5 * k : nullptr, fr, pdf);
 		if (WANT & 3) store3(vout, k, fr);
 		if (WANT & 4) out_pdf[k] = pdf;
 	}
@@ -332,15 +339,15 @@ __global__ __launch_bounds__(BLOCK) void k_eval_pp(Brdf b, long long n, View vi,
 template <int KIND, int MODE, int FRK>
 hipError_t launch_eval_pp_kind_fr(hipStream_t s, const Brdf &b, long long n, const View &i, const View &o,
                                   const float *rec, const LeanCfg &base, const View &out, float *out_pdf,
-                                  float *out_pp, int want)
+                                  float *out_pp, int want, const LeanSrc &ls)
 {
 	dim3 g((KIND == KIND_BECKMANN || KIND == KIND_GGX) ? grid_full(n) : grid_for(n)), t(BLOCK);
 	switch (want) {
-	case 1: hipLaunchKernelGGL((k_eval_pp<KIND, 1, MODE, FRK>), g, t, 0, s, b, n, i, o, rec, base, out, out_pdf, out_pp); break;
-	case 2: hipLaunchKernelGGL((k_eval_pp<KIND, 2, MODE, FRK>), g, t, 0, s, b, n, i, o, rec, base, out, out_pdf, out_pp); break;
-	case 4: hipLaunchKernelGGL((k_eval_pp<KIND, 4, MODE, FRK>), g, t, 0, s, b, n, i, o, rec, base, out, out_pdf, out_pp); break;
-	case 5: hipLaunchKernelGGL((k_eval_pp<KIND, 5, MODE, FRK>), g, t, 0, s, b, n, i, o, rec, base, out, out_pdf, out_pp); break;
-	case 6: hipLaunchKernelGGL((k_eval_pp<KIND, 6, MODE, FRK>), g, t, 0, s, b, n, i, o, rec, base, out, out_pdf, out_pp); break;
+	case 1: hipLaunchKernelGGL((k_eval_pp<KIND, 1, MODE, FRK>), g, t, 0, s, b, n, i, o, rec, base, out, out_pdf, out_pp, ls); break;
+	case 2: hipLaunchKernelGGL((k_eval_pp<KIND, 2, MODE, FRK>), g, t, 0, s, b, n, i, o, rec, base, out, out_pdf, out_pp, ls); break;
+	case 4: hipLaunchKernelGGL((k_eval_pp<KIND, 4, MODE, FRK>), g, t, 0, s, b, n, i, o, rec, base, out, out_pdf, out_pp, ls); break;
+	case 5: hipLaunchKernelGGL((k_eval_pp<KIND, 5, MODE, FRK>), g, t, 0, s, b, n, i, o, rec, base, out, out_pdf, out_pp, ls); break;
+	case 6: hipLaunchKernelGGL((k_eval_pp<KIND, 6, MODE, FRK>), g, t, 0, s, b, n, i, o, rec, base, out, out_pdf, out_pp, ls); break;
 	default: return hipErrorInvalidValue;
 	}
 	return hipGetLastError();
@@ -349,22 +356,22 @@ hipError_t launch_eval_pp_kind_fr(hipStream_t s, const Brdf &b, long long n, con
 template <int KIND, int MODE>
 hipError_t launch_eval_pp_kind(hipStream_t s, const Brdf &b, long long n, const View &i, const View &o,
                                const float *rec, const LeanCfg &base, const View &out, float *out_pdf,
-                               float *out_pp, int want)
+                               float *out_pp, int want, const LeanSrc &ls)
 {
 	// as launch_eval_kind: the analytic lobes get kernels specialised for the ideal / schlick Fresnel terms
 	if constexpr (KIND == KIND_BECKMANN || KIND == KIND_GGX) {
 		if (b.fr.kind == FR_IDEAL || want == 4)
-			return launch_eval_pp_kind_fr<KIND, MODE, FR_IDEAL>(s, b, n, i, o, rec, base, out, out_pdf, out_pp, want);
+			return launch_eval_pp_kind_fr<KIND, MODE, FR_IDEAL>(s, b, n, i, o, rec, base, out, out_pdf, out_pp, want, ls);
 		if (b.fr.kind == FR_SCHLICK)
-			return launch_eval_pp_kind_fr<KIND, MODE, FR_SCHLICK>(s, b, n, i, o, rec, base, out, out_pdf, out_pp, want);
+			return launch_eval_pp_kind_fr<KIND, MODE, FR_SCHLICK>(s, b, n, i, o, rec, base, out, out_pdf, out_pp, want, ls);
 		if (b.fr.kind == FR_UNPOLARIZED)
-			return launch_eval_pp_kind_fr<KIND, MODE, FR_UNPOLARIZED>(s, b, n, i, o, rec, base, out, out_pdf, out_pp, want);
+			return launch_eval_pp_kind_fr<KIND, MODE, FR_UNPOLARIZED>(s, b, n, i, o, rec, base, out, out_pdf, out_pp, want, ls);
 	}
 	if constexpr (KIND == KIND_TABULAR || KIND == KIND_TABULAR_ANISO) {
 		if (b.fr.kind == FR_SPLINE)
-			return launch_eval_pp_kind_fr<KIND, MODE, FR_SPLINE>(s, b, n, i, o, rec, base, out, out_pdf, out_pp, want);
+			return launch_eval_pp_kind_fr<KIND, MODE, FR_SPLINE>(s, b, n, i, o, rec, base, out, out_pdf, out_pp, want, ls);
 	}
-	return launch_eval_pp_kind_fr<KIND, MODE, -1>(s, b, n, i, o, rec, base, out, out_pdf, out_pp, want);
+	return launch_eval_pp_kind_fr<KIND, MODE, -1>(s, b, n, i, o, rec, base, out, out_pdf, out_pp, want, ls);
 }
 
 // ------------------------------------------------------------------ sample / evalp_is
@@ -486,7 +493,7 @@ hipError_t launch_sample_kind(hipStream_t s, const Brdf &b, const Params &p, lon
 template <int KIND, bool IS, int MODE, int FRK = -1>
 __global__ __launch_bounds__(BLOCK) void k_sample_pp(Brdf b, long long n, const float *u1a, const float *u2a, View vo,
                                                      const float *rec, LeanCfg base, View vi_out, View vw_out,
-                                                     float *out_pdf, float *out_pp)
+                                                     float *out_pdf, float *out_pp, LeanSrc ls)
 {
 	__shared__ double s_glibc[KIND == KIND_BECKMANN ? GLIBC_LDS_WORDS : 1];
 	GlibcTabs gt = glibc_tabs_global();
@@ -499,8 +506,13 @@ __global__ __launch_bounds__(BLOCK) void k_sample_pp(Brdf b, long long n, const 
 	const long long stride = (long long)gridDim.x * BLOCK;
 	for (long long k = (long long)blockIdx.x * BLOCK + threadIdx.x; k < n; k += stride) {
 		v3 i_out, w; float pdf;
-		pp_sample_one<KIND, IS, MODE, FRK>(b, u1a[k], u2a[k], load3(vo, k), rec + 5 * k, base, out_pp ? out_pp + 5 * k : nullptr,
-		                                   gt, i_out, w, pdf);
+		if constexpr (MODE == 2) {                      // records from a resident LEAN map, as in k_eval_pp
+			float r[5];
+			leanmap_lookup_hit(ls, k, r);
+			pp_sample_one<KIND, IS, 1, FRK>(b, u1a[k], u2a[k], load3(vo, k), r, base, out_pp ? out_pp + 5 * k : nullptr, gt, i_out, w, pdf);
+		} else
+			pp_sample_one<KIND, IS, MODE, FRK>(b, u1a[k], u2a[k], load3(vo, k), rec + 5 * k, base, out_pp ? out_pp + 5 * k : nullptr,
+			                                   gt, i_out, w, pdf);
 		store3(vi_out, k, i_out);
 		if (IS) { store3(vw_out, k, w); out_pdf[k] = pdf; }
 	}
@@ -509,12 +521,13 @@ __global__ __launch_bounds__(BLOCK) void k_sample_pp(Brdf b, long long n, const 
 template <int KIND>
 hipError_t launch_sample_pp_kind(hipStream_t s, const Brdf &b, long long n, const float *u1, const float *u2, const View &o,
                                  const float *rec, int mode, const LeanCfg &base, const View &out_i, const View *out_w,
-                                 float *out_pdf, float *out_pp)
+                                 float *out_pdf, float *out_pp, const LeanSrc &ls)
 {
 	dim3 g((KIND == KIND_BECKMANN || KIND == KIND_GGX) ? grid_full(n) : grid_for(n)), t(BLOCK);
 	View w = out_w ? *out_w : View{ nullptr, nullptr, nullptr, 0 };
-#define DJB_SPP(IS_, FRK_) do { if (mode == 0) hipLaunchKernelGGL((k_sample_pp<KIND, IS_, 0, FRK_>), g, t, 0, s, b, n, u1, u2, o, rec, base, out_i, w, out_pdf, out_pp); \
-                                else hipLaunchKernelGGL((k_sample_pp<KIND, IS_, 1, FRK_>), g, t, 0, s, b, n, u1, u2, o, rec, base, out_i, w, out_pdf, out_pp); \
+#define DJB_SPP(IS_, FRK_) do { if (mode == 0) hipLaunchKernelGGL((k_sample_pp<KIND, IS_, 0, FRK_>), g, t, 0, s, b, n, u1, u2, o, rec, base, out_i, w, out_pdf, out_pp, ls); \
+                                else if (mode == 1) hipLaunchKernelGGL((k_sample_pp<KIND, IS_, 1, FRK_>), g, t, 0, s, b, n, u1, u2, o, rec, base, out_i, w, out_pdf, out_pp, ls); \
+                                else hipLaunchKernelGGL((k_sample_pp<KIND, IS_, 2, FRK_>), g, t, 0, s, b, n, u1, u2, o, rec, base, out_i, w, out_pdf, out_pp, ls); \
                                 return hipGetLastError(); } while (0)
 	if (!out_w) DJB_SPP(false, -1);
 	if constexpr (KIND == KIND_BECKMANN || KIND == KIND_GGX) {
@@ -760,12 +773,15 @@ hipError_t launch_sample(hipStream_t s, const Brdf &b, const Params &p, long lon
 
 hipError_t launch_eval_pp(hipStream_t s, const Brdf &b, long long n, const View &i, const View &o,
                           const float *rec, int mode, const float *base5, float scale, int lean_flags, const View &out,
-                          float *out_pdf, float *out_pp, int want)
+                          float *out_pdf, float *out_pp, int want, const LeanSrc *src)
 {
 	if (n <= 0) return hipSuccess;
+	if ((mode == 2) != (src != nullptr)) return hipErrorInvalidValue;
 	const LeanCfg base = lean_cfg(base5, scale, lean_flags);
-#define DJB_PP(K) (mode == 0 ? launch_eval_pp_kind<K, 0>(s, b, n, i, o, rec, base, out, out_pdf, out_pp, want) \
-                             : launch_eval_pp_kind<K, 1>(s, b, n, i, o, rec, base, out, out_pdf, out_pp, want))
+	const LeanSrc ls = src ? *src : LeanSrc{ { nullptr, 0, 0 }, nullptr, nullptr };
+#define DJB_PP(K) (mode == 0 ? launch_eval_pp_kind<K, 0>(s, b, n, i, o, rec, base, out, out_pdf, out_pp, want, ls) \
+                 : mode == 1 ? launch_eval_pp_kind<K, 1>(s, b, n, i, o, rec, base, out, out_pdf, out_pp, want, ls) \
+                             : launch_eval_pp_kind<K, 2>(s, b, n, i, o, rec, base, out, out_pdf, out_pp, want, ls))
 	switch (b.kind) {
 	case KIND_BECKMANN: return DJB_PP(KIND_BECKMANN);
 	case KIND_GGX:      return DJB_PP(KIND_GGX);
@@ -778,15 +794,17 @@ hipError_t launch_eval_pp(hipStream_t s, const Brdf &b, long long n, const View 
 
 hipError_t launch_sample_pp(hipStream_t s, const Brdf &b, long long n, const float *u1, const float *u2, const View &o,
                             const float *rec, int mode, const float *base5, float scale, int lean_flags, const View &out_i,
-                            const View *out_w, float *out_pdf, float *out_pp)
+                            const View *out_w, float *out_pdf, float *out_pp, const LeanSrc *src)
 {
 	if (n <= 0) return hipSuccess;
+	if ((mode == 2) != (src != nullptr)) return hipErrorInvalidValue;
 	const LeanCfg base = lean_cfg(base5, scale, lean_flags);
+	const LeanSrc ls = src ? *src : LeanSrc{ { nullptr, 0, 0 }, nullptr, nullptr };
 	switch (b.kind) {
-	case KIND_BECKMANN: return launch_sample_pp_kind<KIND_BECKMANN>(s, b, n, u1, u2, o, rec, mode, base, out_i, out_w, out_pdf, out_pp);
-	case KIND_GGX:      return launch_sample_pp_kind<KIND_GGX>(s, b, n, u1, u2, o, rec, mode, base, out_i, out_w, out_pdf, out_pp);
-	case KIND_TABULAR:  return launch_sample_pp_kind<KIND_TABULAR>(s, b, n, u1, u2, o, rec, mode, base, out_i, out_w, out_pdf, out_pp);
-	case KIND_TABULAR_ANISO: return launch_sample_pp_kind<KIND_TABULAR_ANISO>(s, b, n, u1, u2, o, rec, mode, base, out_i, out_w, out_pdf, out_pp);
+	case KIND_BECKMANN: return launch_sample_pp_kind<KIND_BECKMANN>(s, b, n, u1, u2, o, rec, mode, base, out_i, out_w, out_pdf, out_pp, ls);
+	case KIND_GGX:      return launch_sample_pp_kind<KIND_GGX>(s, b, n, u1, u2, o, rec, mode, base, out_i, out_w, out_pdf, out_pp, ls);
+	case KIND_TABULAR:  return launch_sample_pp_kind<KIND_TABULAR>(s, b, n, u1, u2, o, rec, mode, base, out_i, out_w, out_pdf, out_pp, ls);
+	case KIND_TABULAR_ANISO: return launch_sample_pp_kind<KIND_TABULAR_ANISO>(s, b, n, u1, u2, o, rec, mode, base, out_i, out_w, out_pdf, out_pp, ls);
 	}
 	return hipErrorInvalidValue;
 }

@@ -720,6 +720,186 @@ microfacet.sample_pp = _sample_pp
 microfacet.sample_lean = _sample_lean
 
 
+# --------------------------------------------------------------------------- resident LEAN maps (include/djb_hip.h: djb_leanmap)
+def _image_u8(a, channels):
+    a = np.ascontiguousarray(a, dtype=np.uint8)
+    want = 2 if channels == 1 else 3
+    if a.ndim != want or (channels != 1 and a.shape[2] not in (3, 4)):
+        raise exc(1, f"djb_error: expected a uint8 image [h, w{'' if channels == 1 else ', 3 or 4'}], got {a.shape}")
+    return a
+
+
+def dmap_to_nmap(dmap, scale=0.1, ctx: Optional[Context] = None):
+    """The reference's ``dmap2nmap()`` (utils/dmap2nmap.cpp:13-44) on the context's device: uint8 height map [h, w] ->
+    uint8 normal map [h, w, 3], the same bytes."""
+    ctx = ctx or default_context()
+    d = _image_u8(dmap, 1)
+    out = np.empty(d.shape + (3,), np.uint8)
+    _lib.check(_lib.load().djb_dmap_to_nmap(ctx._h, C.c_int(d.shape[1]), C.c_int(d.shape[0]), C.c_void_p(d.ctypes.data),
+                                            C.c_float(scale), C.c_void_p(out.ctypes.data)))
+    return out
+
+
+class leanmap:
+    """A LEAN map resident on its context's device: level 0 with the reference's arithmetic (utils/nmap2leanmap.cpp), the mip
+    pyramid of the five moments, and the trilinear lookup the per-hit kernels run (include/djb_hip.h defines both).  Images are
+    numpy arrays [h, w(, c)], row-major: texel (x, y) is ``a[y, x]``."""
+
+    def __init__(self, ctx: Optional[Context] = None):
+        self.ctx = ctx or default_context()
+        self._h = C.c_void_p()
+
+    def _made(self):
+        w, h, l = C.c_int(), C.c_int(), C.c_int()
+        _lib.check(_lib.load().djb_leanmap_info(self._h, C.byref(w), C.byref(h), C.byref(l)))
+        self.width, self.height, self.levels = w.value, h.value, l.value
+        return self
+
+    @classmethod
+    def from_nmap(cls, nmap, base_roughness=1e-5, ctx: Optional[Context] = None):
+        """``nmap2leanmap()`` per texel of a uint8 normal map [h, w, 3 or 4]."""
+        m, a = cls(ctx), _image_u8(nmap, 3)
+        _lib.check(_lib.load().djb_leanmap_create_from_nmap(m.ctx._h, C.c_int(a.shape[1]), C.c_int(a.shape[0]), C.c_void_p(a.ctypes.data),
+                                                            C.c_int(a.shape[2]), C.c_float(base_roughness), C.byref(m._h)))
+        return m._made()
+
+    @classmethod
+    def from_dmap(cls, dmap, scale=0.1, base_roughness=1e-5, ctx: Optional[Context] = None):
+        """``dmap2nmap()`` then ``nmap2leanmap()`` of a uint8 height map [h, w], chained on the device."""
+        m, a = cls(ctx), _image_u8(dmap, 1)
+        _lib.check(_lib.load().djb_leanmap_create_from_dmap(m.ctx._h, C.c_int(a.shape[1]), C.c_int(a.shape[0]), C.c_void_p(a.ctypes.data),
+                                                            C.c_float(scale), C.c_float(base_roughness), C.byref(m._h)))
+        return m._made()
+
+    @classmethod
+    def from_moments(cls, moments, biased=False, ctx: Optional[Context] = None):
+        """Import of ready moments [h, w, 5] (E1..E5), e.g. decoded from the EXR pair the reference's tools write;
+        biased=True: they come from ``nmap2leanmap_biased`` (E1, E2 carry +25, E5 +625)."""
+        m = cls(ctx)
+        a = np.ascontiguousarray(moments, dtype=np.float32)
+        if a.ndim != 3 or a.shape[2] != 5:
+            raise exc(1, f"djb_error: expected moments [h, w, 5], got {a.shape}")
+        _lib.check(_lib.load().djb_leanmap_create_from_moments(m.ctx._h, C.c_int(a.shape[1]), C.c_int(a.shape[0]), C.c_void_p(a.ctypes.data),
+                                                               C.c_int(1 if biased else 0), C.byref(m._h)))
+        return m._made()
+
+    def level_shape(self, l):
+        return max(1, self.height >> l), max(1, self.width >> l)
+
+    def level(self, l, biased=False):
+        """Level ``l`` as float32 [h_l, w_l, 5]; biased=True re-applies the bias of ``nmap2leanmap_biased`` (for export)."""
+        if not 0 <= l < self.levels:
+            raise exc(1, f"djb_error: the LEAN map has levels 0 .. {self.levels - 1} (got {l})")
+        out = np.empty(self.level_shape(l) + (5,), np.float32)
+        _lib.check(_lib.load().djb_leanmap_get_level(self._h, C.c_int(l), C.c_int(1 if biased else 0), C.c_void_p(out.ctypes.data)))
+        return out
+
+    def lookup(self, uv, lod=None):
+        """Filtered moments [n, 5] at uv [n, 2] and lod [n] (None: level 0): records ``eval_lean`` / ``sample_lean`` accept.
+        numpy in, numpy out; torch tensors on the context's GPU in, a tensor there out."""
+        (uv_keep, uv_ptr, lod_keep, lod_ptr), n, on_dev, dev = _hit_coords(uv, lod), len(uv), _is_dev(uv), getattr(uv, "device", None)
+        out = torch.empty((n, 5), dtype=torch.float32, device=dev) if on_dev else np.empty((n, 5), np.float32)
+        _lib.check(_lib.load().djb_leanmap_lookup_batch(self.ctx._h, self._h, C.c_int64(n), C.c_void_p(uv_ptr), C.c_void_p(lod_ptr),
+                                                        C.c_void_p(out.data_ptr() if on_dev else out.ctypes.data),
+                                                        C.c_int(_lib.MEM_DEVICE if on_dev else _lib.MEM_HOST)))
+        del uv_keep, lod_keep
+        return out
+
+    def close(self):
+        if self._h:
+            _lib.load().djb_leanmap_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _is_dev(a):
+    return torch is not None and isinstance(a, torch.Tensor) and a.is_cuda
+
+
+def _hit_coords(uv, lod, like_dev=None):
+    """(uv array, pointer, lod array or None, pointer or None) in the memory space of ``uv`` (or of the directions, like_dev)."""
+    on_dev = _is_dev(uv) if like_dev is None else like_dev is not False
+    if on_dev:
+        dev = uv.device if _is_dev(uv) else like_dev
+        uv = uv.float().contiguous() if _is_dev(uv) else torch.as_tensor(np.asarray(uv, np.float32), device=dev)
+        if lod is not None:
+            lod = lod.float().contiguous() if _is_dev(lod) else torch.as_tensor(np.asarray(lod, np.float32), device=dev)
+        uv_ptr, lod_ptr = uv.data_ptr(), None if lod is None else lod.data_ptr()
+    else:
+        uv = np.ascontiguousarray(uv.cpu().numpy() if hasattr(uv, "cpu") else uv, dtype=np.float32)
+        if lod is not None:
+            lod = np.ascontiguousarray(lod.cpu().numpy() if hasattr(lod, "cpu") else lod, dtype=np.float32)
+        uv_ptr, lod_ptr = uv.ctypes.data, None if lod is None else lod.ctypes.data
+    if uv.ndim != 2 or uv.shape[1] != 2 or (lod is not None and tuple(lod.shape) != (uv.shape[0],)):
+        raise exc(1, "djb_error: uv must be [n, 2] and lod [n] (or None)")
+    return uv, uv_ptr, lod, lod_ptr
+
+
+def _eval_leanmap(self, i, o, lmap, uv, lod, base, scale, want="evalp", return_params=False, filtering=True):
+    """``eval_lean`` with the records read from a resident LEAN map inside the kernel: per hit the trilinear lookup at
+    (uv, lod), then dj_beckmannconductor's per-hit path on the filtered moments.  Equal, bit for bit, to
+    ``eval_lean(..., lean=lmap.lookup(uv, lod))``."""
+    lib = _lib.load()
+    vi, vo = _Vec(i), _Vec(o)
+    uvk, uv_ptr, lodk, lod_ptr = _hit_coords(uv, lod, vi.device if vi.is_torch else False)
+    if uvk.shape[0] != vi.n:
+        raise exc(1, "djb_error: uv must have one row per pair")
+    code = {"eval": 1, "evalp": 2, "pdf": 4, "eval+pdf": 5, "evalp+pdf": 6}[want]
+    out = vi.like() if code & 3 else None
+    pdf = pdf_ptr = None
+    if code & 4:
+        pdf, pdf_ptr = vi.scalars()
+    pp = pp_ptr = None
+    if return_params:
+        pp = torch.empty((vi.n, 5), dtype=torch.float32, device=vi.device) if vi.is_torch else np.empty((vi.n, 5), np.float32)
+        pp_ptr = pp.data_ptr() if vi.is_torch else pp.ctypes.data
+    _lib.check(lib.djb_eval_leanmap_batch(self.ctx._h, self._h, lmap._h, C.c_int64(vi.n), C.byref(vi.view), C.byref(vo.view),
+                                          C.c_void_p(uv_ptr), C.c_void_p(lod_ptr), _params_ptr(base), C.c_float(scale),
+                                          C.c_int(0 if filtering else LEAN_NAIVE_MIP), C.c_int(code),
+                                          C.byref(out.view) if out else None, C.c_void_p(pdf_ptr), C.c_void_p(pp_ptr), C.c_int(vi.mem)))
+    del uvk, lodk
+    res = [x for x in (out.keep if out else None, pdf) if x is not None]
+    if return_params:
+        res.append(pp)
+    return res[0] if len(res) == 1 else tuple(res)
+
+
+def _sample_leanmap(self, u1, u2, o, lmap, uv, lod, base, scale, evalp_is=True, return_params=False, filtering=True):
+    """``sample_lean`` with the records read from a resident LEAN map inside the kernel (see ``eval_leanmap``)."""
+    lib = _lib.load()
+    vo = _Vec(o)
+    k1, p1 = _scalar_in(u1, vo)
+    k2, p2 = _scalar_in(u2, vo)
+    uvk, uv_ptr, lodk, lod_ptr = _hit_coords(uv, lod, vo.device if vo.is_torch else False)
+    if uvk.shape[0] != vo.n:
+        raise exc(1, "djb_error: uv must have one row per sample")
+    i = vo.like()
+    w = vo.like() if evalp_is else None
+    pdf, pdf_ptr = vo.scalars() if evalp_is else (None, None)
+    pp = pp_ptr = None
+    if return_params:
+        pp = torch.empty((vo.n, 5), dtype=torch.float32, device=vo.device) if vo.is_torch else np.empty((vo.n, 5), np.float32)
+        pp_ptr = pp.data_ptr() if vo.is_torch else pp.ctypes.data
+    _lib.check(lib.djb_sample_leanmap_batch(self.ctx._h, self._h, lmap._h, C.c_int64(vo.n), C.c_void_p(p1), C.c_void_p(p2), C.byref(vo.view),
+                                            C.c_void_p(uv_ptr), C.c_void_p(lod_ptr), _params_ptr(base), C.c_float(scale),
+                                            C.c_int(0 if filtering else LEAN_NAIVE_MIP), C.byref(w.view) if w else None, C.byref(i.view),
+                                            C.c_void_p(pdf_ptr), C.c_void_p(pp_ptr), C.c_int(vo.mem)))
+    del k1, k2, uvk, lodk
+    res = (w.keep, i.keep, pdf) if evalp_is else (i.keep,)
+    if return_params:
+        res = res + (pp,)
+    return res[0] if len(res) == 1 else res
+
+
+microfacet.eval_leanmap = _eval_leanmap
+microfacet.sample_leanmap = _sample_leanmap
+
+
 class beckmann(microfacet):
     class lrep:
         """beckmann::lrep: linear representation by slope moments E1..E5 (dj_brdf.h:330-356)."""

@@ -58,7 +58,10 @@ extern "C" {
  *   233  round 6: + djb_fit_merl_files_multi (the file pipeline over several contexts), djb_merl_bin_keys_batch.  The on-chip uniforms of
  *        djb_sample_rng_batch / djb_gen_uniforms are a cheaper counter hash (dj_brdf_amd/synth.py: rng_uniforms); same interface.
  *   234  round 6: + djb_selftest_fast_trig; DJB_OPT_CONTRACT_1E5 also covers utia eval / evalp (the sRGB power of the decode only).
- *   235  round 6: + djb_selftest_model_fast (the decided fast tier of the sgd / abc models). */
+ *   235  round 6: + djb_selftest_model_fast (the decided fast tier of the sgd / abc models).
+ *        Additive under 235, no existing entry changed: resident LEAN maps -- djb_leanmap, djb_dmap_to_nmap,
+ *        djb_leanmap_create_from_nmap / _from_dmap / _from_moments, djb_leanmap_info, djb_leanmap_get_level, djb_leanmap_destroy,
+ *        djb_leanmap_lookup_batch, djb_eval_leanmap_batch, djb_sample_leanmap_batch. */
 #define DJB_HIP_VERSION 235
 #define DJB_HIP_VERSION_MAJOR(v) ((v) / 100)
 
@@ -95,6 +98,7 @@ enum { DJB_MEM_DEVICE = 0, DJB_MEM_HOST = 1 };
 
 typedef struct djb_ctx djb_ctx;     /* one GPU + one HIP stream */
 typedef struct djb_brdf djb_brdf;   /* an immutable BRDF object resident in HBM (djb::brdf subclass) */
+typedef struct djb_leanmap djb_leanmap;   /* an immutable LEAN map (mip pyramid of slope moments) resident in HBM */
 
 typedef struct { float *x, *y, *z; int64_t stride; } djb_vec3_view;
 
@@ -404,6 +408,65 @@ djb_status djb_sample_lean_batch(djb_ctx *, const djb_brdf *, int64_t n, const f
                                  const djb_vec3_view *o, const djb_params *base, float scale, int lean_flags,
                                  const float *lean, const djb_vec3_view *out_w, const djb_vec3_view *out_i,
                                  float *out_pdf, float *out_pdfparams, int mem);
+/* ---- resident LEAN maps: the textures dj_beckmannconductor reads per hit (five slope moments E1..E5 per texel), built by the
+ * context that owns them -- on the GPU for a GPU context -- with their mip pyramid, and read with a trilinear filter per hit.
+ * What the reference's utils/ programs prepare offline (dmap2nmap, nmap2leanmap, nmap2leanmap_biased) and its renderer filters.
+ *
+ * Images are HOST memory, row-major, x fastest: texel (x, y) -- the reference's (i, j) -- is element x + w * y.  w and h are powers
+ * of two in [1, 8192], not necessarily equal; anything else is DJB_ERR_INVALID_ARGUMENT.  A map belongs to the context that made
+ * it, as a djb_brdf does (a CPU context's map on a GPU context, or the reverse, is DJB_ERR_INVALID_ARGUMENT), may be destroyed
+ * after it, and stores the UNBIASED moments.
+ *
+ * Level 0 is the reference's arithmetic, bit for bit:
+ *   djb_dmap_to_nmap               dmap2nmap() (utils/dmap2nmap.cpp:13-44): w * h height bytes -> w * h RGB byte triples; neighbours
+ *                                  clamp at the border (CImg's atXY; the tool's --clamp_to_border switch changes nothing)
+ *   djb_leanmap_create_from_nmap   nmap2leanmap() (utils/nmap2leanmap.cpp:18-56) per texel; pixel k starts at rgb + pixel_stride * k
+ *                                  (3 = RGB, 4 = RGBA).  A blue byte of 0 gives the infinite / NaN moments it gives there.
+ *   djb_leanmap_create_from_dmap   the two chained on the device: the normal map never travels
+ *   djb_leanmap_create_from_moments  w * h records (E1..E5) made elsewhere, e.g. by the reference's tools (the caller decodes the
+ *                                  EXR); biased != 0: they come from nmap2leanmap_biased, E1 -= 25, E2 -= 25, E5 -= 625 on import
+ *   djb_leanmap_get_level          level `level` as w_l * h_l records (E1..E5); biased != 0 re-applies that bias (E1 + 25, E2 + 25,
+ *                                  E5 + 625: the textures dj_beckmannconductor.cpp:300-303 expects)
+ *
+ * The pyramid and the filter have no reference (the reference leaves them to Mitsuba); they are DEFINED here, as float operations
+ * in this order, one rounding each, no contraction:
+ *   levels      w_l = max(1, w >> l), h_l = max(1, h >> l), l = 0 .. L - 1, L = 1 + max(log2 w, log2 h)
+ *   downsample  per moment, with x0 = min(2x, w_s - 1), x1 = min(2x + 1, w_s - 1), y0, y1 alike in the level below (w_s x h_s):
+ *                 T_l[x, y] = ((T[x0, y0] + T[x1, y0]) + (T[x0, y1] + T[x1, y1])) * 0.25f      (all five moments, as stored)
+ *   lookup(u, v, lod)
+ *     lod: NaN -> 0, then clamped to [0, L - 1];  l0 = floorf(lod), t = lod - l0, l1 = min(l0 + 1, L - 1)
+ *     uf = u - floorf(u);  uf = 0 unless 0 <= uf < 1 (NaN, inf, a fraction that rounds up to 1);  vf alike
+ *     in level l:  x = uf * w_l - 0.5f, x0 = floorf(x), fx = x - x0, columns x0 and x0 + 1 wrapped by REPEAT; y, fy, rows alike
+ *                  A_l = lerp(lerp(T00, T10, fx), lerp(T01, T11, fx), fy)     [Tcr: column c, row r; lerp(a, b, s) = a + (b - a) * s]
+ *     result = lerp(A_l0, A_l1, t);  when t == 0, level l1 is not read and the result is A_l0
+ *   (lerp in this form returns a where b == a and where s == 0, for finite a and b: a constant map filters to its constant at every
+ *   (u, v, lod), and the centre of a texel to that texel, exactly; a * (1 - s) + b * s rounds both.)
+ *
+ * Per-hit calls: uv = n (u, v) pairs, lod = n floats or NULL (level 0), in the memory space `mem` names, like every other array.
+ *   djb_leanmap_lookup_batch   out_lean = n records (E1..E5), as djb_eval_lean_batch / djb_sample_lean_batch accept
+ *   djb_eval_leanmap_batch     per hit: that lookup, then exactly what djb_eval_lean_batch does with the record (one kernel)
+ *   djb_sample_leanmap_batch   per hit: that lookup, then exactly what djb_sample_lean_batch does with the record
+ *   lean_flags: DJB_LEAN_NAIVE_MIP as there (E3, E4, E5 rebuilt from the FILTERED E1, E2); DJB_LEAN_BIASED is an invalid argument. */
+djb_status djb_dmap_to_nmap(djb_ctx *, int w, int h, const unsigned char *dmap, float scale, unsigned char *out_rgb);
+djb_status djb_leanmap_create_from_nmap(djb_ctx *, int w, int h, const unsigned char *rgb, int pixel_stride, float base_roughness,
+                                        djb_leanmap **out);
+djb_status djb_leanmap_create_from_dmap(djb_ctx *, int w, int h, const unsigned char *dmap, float scale, float base_roughness,
+                                        djb_leanmap **out);
+djb_status djb_leanmap_create_from_moments(djb_ctx *, int w, int h, const float *moments, int biased, djb_leanmap **out);
+djb_status djb_leanmap_info(const djb_leanmap *, int *w, int *h, int *levels);
+djb_status djb_leanmap_get_level(const djb_leanmap *, int level, int biased, float *out);
+djb_status djb_leanmap_destroy(djb_leanmap *);
+djb_status djb_leanmap_lookup_batch(djb_ctx *, const djb_leanmap *, int64_t n, const float *uv, const float *lod, float *out_lean,
+                                    int mem);
+djb_status djb_eval_leanmap_batch(djb_ctx *, const djb_brdf *, const djb_leanmap *, int64_t n, const djb_vec3_view *i,
+                                  const djb_vec3_view *o, const float *uv, const float *lod, const djb_params *base, float scale,
+                                  int lean_flags, int want, const djb_vec3_view *out_fr, float *out_pdf, float *out_pdfparams,
+                                  int mem);
+djb_status djb_sample_leanmap_batch(djb_ctx *, const djb_brdf *, const djb_leanmap *, int64_t n, const float *u1, const float *u2,
+                                    const djb_vec3_view *o, const float *uv, const float *lod, const djb_params *base, float scale,
+                                    int lean_flags, const djb_vec3_view *out_w, const djb_vec3_view *out_i, float *out_pdf,
+                                    float *out_pdfparams, int mem);
+
 /* beckmann::lrep algebra on {E1..E5} (host scalars; dj_brdf.h:330-356, 1959-2051).  b may be NULL
  * (= the default lrep(0,0,1,1,0)); x (and y) are the scalar arguments of mul / shear / scale.
  * IADD keeps the reference's operator+= ordering (dj_brdf.h:2013-2017), which differs from ADD.   */

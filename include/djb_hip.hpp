@@ -23,6 +23,7 @@
 #ifndef DJB_HIP_HPP
 #define DJB_HIP_HPP
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstddef>
@@ -964,6 +965,49 @@ private:
 	float_t qf2_radial(float_t u, float_t cos_theta_k, float_t sin_theta_k) const DJB_HIP_FINAL { return rq(DJB_Q_QF2_RADIAL, u, cos_theta_k, sin_theta_k); } \
 	float_t qf3_radial(float_t u, float_t qf2) const DJB_HIP_FINAL { return rq(DJB_Q_QF3_RADIAL, u, qf2); }
 
+/* A LEAN map resident on its context's device (include/djb_hip.h, djb_leanmap): what the reference's utils/ programs prepare
+ * offline -- dmap2nmap, nmap2leanmap, nmap2leanmap_biased -- with the mip pyramid of the five moments and the trilinear lookup
+ * the per-hit kernels run.  Images are host memory, row-major, texel (x, y) at x + w * y; w, h powers of two up to 8192. */
+class leanmap {
+public:
+	/* nmap2leanmap() of a normal map; pixel_stride 3 (RGB) or 4 (RGBA) */
+	static leanmap from_nmap(int w, int h, const unsigned char *rgb, int pixel_stride = 3, float_t base_roughness = 1e-5f, hip::context *c = NULL)
+	{ leanmap m(c); hip::check(djb_leanmap_create_from_nmap(m.ctx(), w, h, rgb, pixel_stride, base_roughness, &m.m_h)); return m; }
+	/* dmap2nmap() then nmap2leanmap() of a height map, chained on the device */
+	static leanmap from_dmap(int w, int h, const unsigned char *dmap, float_t scale = 0.1f, float_t base_roughness = 1e-5f, hip::context *c = NULL)
+	{ leanmap m(c); hip::check(djb_leanmap_create_from_dmap(m.ctx(), w, h, dmap, scale, base_roughness, &m.m_h)); return m; }
+	/* moments[w * h][5] made elsewhere (biased: by nmap2leanmap_biased) */
+	static leanmap from_moments(int w, int h, const float_t *moments, bool biased = false, hip::context *c = NULL)
+	{ leanmap m(c); hip::check(djb_leanmap_create_from_moments(m.ctx(), w, h, moments, biased ? 1 : 0, &m.m_h)); return m; }
+	/* the reference's dmap2nmap(): w * h height bytes -> w * h RGB triples */
+	static void dmap_to_nmap(int w, int h, const unsigned char *dmap, float_t scale, unsigned char *out_rgb, hip::context *c = NULL)
+	{ hip::check(djb_dmap_to_nmap((c ? *c : hip::context::standard()).get(), w, h, dmap, scale, out_rgb)); }
+	~leanmap() { djb_leanmap_destroy(m_h); }
+	leanmap(leanmap &&o) noexcept : m_ctx(o.m_ctx), m_h(o.m_h) { o.m_h = NULL; }
+	leanmap &operator=(leanmap &&o) noexcept { if (this != &o) { djb_leanmap_destroy(m_h); m_ctx = o.m_ctx; m_h = o.m_h; o.m_h = NULL; } return *this; }
+	leanmap(const leanmap &) = delete;
+	leanmap &operator=(const leanmap &) = delete;
+	const djb_leanmap *get() const { return m_h; }
+	int width() const { int v; hip::check(djb_leanmap_info(m_h, &v, NULL, NULL)); return v; }
+	int height() const { int v; hip::check(djb_leanmap_info(m_h, NULL, &v, NULL)); return v; }
+	int levels() const { int v; hip::check(djb_leanmap_info(m_h, NULL, NULL, &v)); return v; }
+	/* level l as max(1, w >> l) * max(1, h >> l) records (E1..E5); biased: with the bias of nmap2leanmap_biased re-applied */
+	std::vector<float_t> level(int l, bool biased = false) const
+	{
+		std::vector<float_t> out((size_t)5 * (size_t)std::max(1, width() >> l) * (size_t)std::max(1, height() >> l));
+		hip::check(djb_leanmap_get_level(m_h, l, biased ? 1 : 0, out.data()));
+		return out;
+	}
+	/* filtered moments at n (u, v) pairs and lods (NULL: level 0): records beckmann::evalp_lean accepts */
+	void lookup(size_t n, const float_t *uv, const float_t *lod, float_t *out_lean) const
+	{ hip::check(djb_leanmap_lookup_batch(ctx(), m_h, (int64_t)n, uv, lod, out_lean, DJB_MEM_HOST)); }
+private:
+	explicit leanmap(hip::context *c) : m_ctx(c), m_h(NULL) {}
+	djb_ctx *ctx() const { return (m_ctx ? *m_ctx : hip::context::standard()).get(); }
+	hip::context *m_ctx;
+	djb_leanmap *m_h;
+};
+
 /* Beckmann Microfacet NDF, dj_brdf.h:327-371 */
 class beckmann : public radial {
 public:
@@ -1012,6 +1056,25 @@ public:
 		djb_vec3_view vo = hip::view(o), vr = hip::view(out_fr_cos), vi = hip::view(out_i);
 		hip::check(djb_sample_lean_batch(ctx(), m_h, (int64_t)n, u1, u2, &vo, base.desc(), dmapscale, lean_flags, lean,
 		                                 &vr, &vi, out_pdf, NULL, DJB_MEM_HOST));
+	}
+	/* evalp_lean / evalp_is_lean with the records read from a resident LEAN map inside the kernel: per hit the trilinear lookup
+	 * at (uv_k, lod_k) (lod == NULL: level 0), then the same code; bit for bit what map.lookup() followed by evalp_lean gives.
+	 * lean_flags = DJB_LEAN_NAIVE_MIP or 0 (the map holds unbiased moments) */
+	void evalp_leanmap(size_t n, const vec3 *i, const vec3 *o, const leanmap &map, const float_t *uv, const float_t *lod,
+	                   const microfacet::params &base, float_t dmapscale, vec3 *out_fr_cos, float_t *out_pdf = NULL,
+	                   int lean_flags = 0) const
+	{
+		djb_vec3_view vi = hip::view(i), vo = hip::view(o), vr = hip::view(out_fr_cos);
+		hip::check(djb_eval_leanmap_batch(ctx(), m_h, map.get(), (int64_t)n, &vi, &vo, uv, lod, base.desc(), dmapscale, lean_flags,
+		                                  out_pdf ? 6 : 2, &vr, out_pdf, NULL, DJB_MEM_HOST));
+	}
+	void evalp_is_leanmap(size_t n, const float_t *u1, const float_t *u2, const vec3 *o, const leanmap &map, const float_t *uv,
+	                      const float_t *lod, const microfacet::params &base, float_t dmapscale, vec3 *out_fr_cos, vec3 *out_i,
+	                      float_t *out_pdf, int lean_flags = 0) const
+	{
+		djb_vec3_view vo = hip::view(o), vr = hip::view(out_fr_cos), vi = hip::view(out_i);
+		hip::check(djb_sample_leanmap_batch(ctx(), m_h, map.get(), (int64_t)n, u1, u2, &vo, uv, lod, base.desc(), dmapscale, lean_flags,
+		                                    &vr, &vi, out_pdf, NULL, DJB_MEM_HOST));
 	}
 	beckmann(const fresnel::impl &f = fresnel::ideal(), bool shadow = true, hip::context *c = NULL) : radial(c, f)
 	{ djb_fresnel_desc d = resident_desc(f, &m_host_eval); hip::check(djb_brdf_create_beckmann(ctx(), &d, shadow, &m_h)); }

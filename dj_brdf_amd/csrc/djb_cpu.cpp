@@ -131,7 +131,7 @@ djb_status params_for(const djb_params *in, int brdf_kind, Params *p)
 	if (in && brdf_kind != KIND_LAMBERT && (in->kind & DJB_PARAMS_RESOLVED_FOLLOWS) && DJB_PARAMS_KIND(in->kind) != DJB_PARAMS_LAMBERT) {   // (in == NULL reaches here for a lambert)
 		// a parameter set that carries its resolved form (include/djb_hip.h: djb_params_cached; the facade's params objects): read it
 		const djb_params_resolved &r = reinterpret_cast<const djb_params_cached *>(in)->r;
-		if (!(r.ax > 0.0f && r.ay > 0.0f && r.rho > -1.0f && r.rho < 1.0f))     // a stray flag on a plain djb_params: refuse, do not read garbage as parameters
+		if (!djbk::cached_params_follow(reinterpret_cast<const djb_params_cached *>(in)))     // a stray flag on a plain djb_params: refuse, do not read garbage as parameters
 			return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: DJB_PARAMS_RESOLVED_FOLLOWS is set but no resolved parameter set follows the djb_params");
 		p->nx = r.n[0]; p->ny = r.n[1]; p->nz = r.n[2]; p->ax = r.ax; p->ay = r.ay; p->rho = r.rho; p->s = r.sqrt_one_minus_rho_sqr;
 		p->tx = r.tx_n; p->ty = r.ty_n; p->r_ax = 0.0; p->r_t2 = 0.0;

@@ -124,4 +124,23 @@ unsigned long long trig_sweep_compare(int host_fn, uint32_t first_bits, int64_t 
 namespace djbk {
 djb_status set_error(djb_status st, const char *fmt, ...);
 djb_status resolve_device_params(const djb_params *in, float out9[9], int brdf_kind);   // Params {nx,ny,nz,ax,ay,rho,s,tx,ty}
+
+// Does a resolved parameter set really follow this flagged djb_params (include/djb_hip.h: djb_params_cached)?  The flag is a promise
+// about the bytes behind `c->p`, and a stray 0x100 in a plain djb_params must not turn into silently wrong parameters.  djb_params_resolve
+// copies its inputs into the resolved form bit for bit (elliptic: a1, a2, phi_a; pdfparams: ax, ay, rho, tx_n, ty_n; standard: 1, 1, 0),
+// so `r` carries a tag of `p`: it is held against `p`, and against what resolve can never write (NaN or negative ax / ay, |rho| > 1).
+// No range test beyond that: rho == +-1 (elliptic(1, 1e-4, pi/4)) and every other set the plain path answers are legitimate.
+static inline bool cached_params_follow(const djb_params_cached *c)
+{
+	const djb_params_resolved &r = c->r;
+	if (!(r.ax >= 0.0f && r.ay >= 0.0f) || r.rho > 1.0f || r.rho < -1.0f) return false;
+	auto same = [](float a, float b) { return __builtin_memcmp(&a, &b, sizeof a) == 0; };
+	const float *v = c->p.v;
+	switch (DJB_PARAMS_KIND(c->p.kind)) {
+	case DJB_PARAMS_STANDARD: return r.a1 == 1.0f && r.a2 == 1.0f && same(r.phi_a, 0.0f) && same(r.tx_n, 0.0f) && same(r.ty_n, 0.0f);
+	case DJB_PARAMS_ELLIPTIC: return same(r.a1, v[0]) && same(r.a2, v[1]) && same(r.phi_a, v[2]) && same(r.tx_n, 0.0f) && same(r.ty_n, 0.0f);
+	case DJB_PARAMS_PDFPARAMS: return same(r.ax, v[0]) && same(r.ay, v[1]) && same(r.rho, v[2]) && same(r.tx_n, v[3]) && same(r.ty_n, v[4]);
+	default: return false;
+	}
+}
 } // namespace djbk

@@ -146,7 +146,9 @@ DJB_DEV float sgd_ndf_fast(const double *m, int ch, double c2, double t2, double
 	const double X = __builtin_fma(-m[9 + ch], L, m[SGD_FAST_LNKPI + ch] - ax);
 	const double V = fexp(dmin_(dmax_(X, -700.0), 700.0), ET) * rc2;
 	const double b = __builtin_fma(12.0 * 0x1p-52, ax, __builtin_fma(m[SGD_FAST_B_L + ch], aL, m[SGD_FAST_B_K + ch]));
-	const float lo = F(__builtin_fma(V, -b, V)), hi = F(__builtin_fma(V, b, V));
+	// the reference's value is a quotient of positive terms: never below +0.  Without the clamp a bound b > 1 (ax above 3.7e14, where
+	// e^-ax is long +0: a user's row with alpha = 1e-12) put the lower end below zero, F() made it -0, and -0 == +0 decided it
+	const float lo = F(dmax_(__builtin_fma(V, -b, V), 0.0)), hi = F(__builtin_fma(V, b, V));
 	if (dbg) { dbg[0] = V; dbg[1] = b; }
 	decided = (lo == hi) & (hi < 3e38f) & (ax >= 0x1p-100) & (ax <= 0x1p100) & (c2 >= 0x1p-30) & (c2 <= 2.0) & (X < 700.0);
 	return lo;

@@ -61,7 +61,9 @@ extern "C" {
  *   235  round 6: + djb_selftest_model_fast (the decided fast tier of the sgd / abc models).
  *        Additive under 235, no existing entry changed: resident LEAN maps -- djb_leanmap, djb_dmap_to_nmap,
  *        djb_leanmap_create_from_nmap / _from_dmap / _from_moments, djb_leanmap_info, djb_leanmap_get_level, djb_leanmap_destroy,
- *        djb_leanmap_lookup_batch, djb_eval_leanmap_batch, djb_sample_leanmap_batch. */
+ *        djb_leanmap_lookup_batch, djb_eval_leanmap_batch, djb_sample_leanmap_batch.
+ *        Behaviour under 235, no layout changed: a djb_params_cached is accepted for every set djb_params_resolve can return (rho == +-1 was
+ *        refused); what makes it one is that `r` repeats the values of `p` (see djb_params_cached), no longer a range test. */
 #define DJB_HIP_VERSION 235
 #define DJB_HIP_VERSION_MAJOR(v) ((v) / 100)
 
@@ -121,7 +123,10 @@ typedef struct {
  * cos / sin / sqrt / atan set-up once, eval / pdf / sample copy the result).  `p.kind` carries DJB_PARAMS_RESOLVED_FOLLOWS and `r` is what
  * djb_params_resolve(&p, &r) returned for the same p (with the flag cleared): every entry point that takes a `const djb_params *` then
  * reads `r` instead of redoing the set-up -- 40-60 ns of a ~100 ns one-pair call.  The djb:: facade's params objects are of this form.
- * The flag is a promise about the bytes BEHIND the djb_params: a copy of `p` alone must have it cleared (DJB_PARAMS_KIND). */
+ * The flag is a promise about the bytes BEHIND the djb_params: a copy of `p` alone must have it cleared (DJB_PARAMS_KIND).  The promise
+ * is checked: djb_params_resolve copies its inputs into `r` (elliptic: a1, a2, phi_a; pdfparams: ax, ay, rho, tx_n, ty_n; standard: 1, 1, 0),
+ * and a flagged djb_params whose `r` does not repeat them bit for bit -- or holds a negative / NaN scale or |rho| > 1, which resolve
+ * never writes -- is DJB_ERR_INVALID_ARGUMENT.  So `p` must not be edited after it was resolved; resolve again instead. */
 #define DJB_PARAMS_RESOLVED_FOLLOWS 0x100
 #define DJB_PARAMS_KIND(k) ((k) & 0xff)
 typedef struct { djb_params p; djb_params_resolved r; } djb_params_cached;

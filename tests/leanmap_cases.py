@@ -352,3 +352,93 @@ def check_errors(ctx):
                                                   C.byref(base._p), C.c_float(1), 0, 2, C.byref(fr.view), None, None, 1))
     m.close(); m.close()                                             # destroy twice through the wrapper: the handle is cleared
     assert lib.djb_leanmap_destroy(None) == 0
+
+
+# ------------------------------------------------------------------ records a map produces, through the per-hit operators, against the oracle
+STEEP_ROUGHNESS = (1e-5, 0.05)
+LEAN_BASE_T = ("elliptic", 0.12, 0.2, 0.3)
+LEAN_LOBES_T = [("beckmann", ("ideal",)), ("ggx", ("schlick", 1.0, 0.71, 0.29))]          # lobes(ctx), in the oracle's form
+ZERO_VARIANCE_SHARE = 0.25
+
+
+def steep_nmap(seed=41):
+    """a 64 x 64 normal map of steep facets: red / green uniform over 0..255, blue uniform over 1..12 -- slopes up to 255, so that
+    E3 = sx^2 + base_roughness^2 / 2 rounds to sx^2 at base_roughness = 1e-5 and a texel has NO variance left (E3 - E1^2 <= 0)"""
+    rng = np.random.default_rng(seed)
+    return np.stack([rng.integers(0, 256, (64, 64)), rng.integers(0, 256, (64, 64)), rng.integers(1, 13, (64, 64))], 2).astype(np.uint8)
+
+
+def steep_coords(n, levels, seed, w=64, h=64):
+    """hostile_coords with every third hit at the centre of a level-0 texel (lod 0): records that ARE texels"""
+    uv, lod = hostile_coords(n, levels, seed)
+    rng = np.random.default_rng(seed + 1)
+    k = np.arange(n) % 3 == 0
+    m = int(k.sum())
+    uv[k] = np.stack([(rng.integers(0, w, m) + 0.5) / w, (rng.integers(0, h, m) + 0.5) / h], 1).astype(f32)
+    lod[k] = 0
+    return uv, lod
+
+
+def zero_variance_share(rec):
+    """of the records with finite moments, the share whose slope variance in x is not positive (float32, as the definition computes it)"""
+    rec = np.ascontiguousarray(rec, f32)
+    fin = np.isfinite(rec).all(1)
+    with np.errstate(over="ignore", invalid="ignore"):
+        var = rec[fin, 2] - rec[fin, 0] * rec[fin, 0]
+    return float(np.mean(var <= 0)) if fin.any() else 0.0
+
+
+def check_map_records_against_oracle(ctx, oracle, n=6000, device=None):
+    """For every fixture map, the hostile map (infinite moments) and a steep map (zero-variance texels) at two base roughnesses:
+    rec = map.lookup(hostile coordinates: every level, filtered top levels, NaN / Inf coordinates), then
+      eval_lean / sample_lean(rec)        == oracle.eval_lean / oracle.sample_lean on the same records: values and written-back pdfparams,
+      eval_leanmap / sample_leanmap(uv, lod) == the same oracle output,
+    with LEAN filtering on and off and dmapscale 1, 0.37 and 0.  Equal bits, NaNs in the same places (the module docstring)."""
+    maps = [(name, m, l0, hostile_coords) for name, m, l0 in all_maps(ctx)]
+    steep = steep_nmap()
+    for br in STEEP_ROUGHNESS:
+        l0 = nmap2leanmap_np(steep, br)
+        maps.append((f"steep{br}", djb.leanmap.from_nmap(steep, br, ctx=ctx), l0, steep_coords))
+    base = P.elliptic(*LEAN_BASE_T[1:])
+    i, o = synth.directions_aos(n, synth.SEED_I), synth.directions_aos(n, synth.SEED_O)
+    u1, u2 = synth.uniforms(n, synth.SEED_U1), synth.uniforms(n, synth.SEED_U2)
+    if device is not None:
+        import torch
+        dev = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=device)
+    else:
+        dev = lambda a: a
+    di, do, d1, d2 = dev(i), dev(o), dev(u1), dev(u2)
+    for name, m, l0, coords in maps:
+        uv, lod = coords(n, m.levels, 37)
+        ref = lookup_np(pyramid_np(l0), uv, lod)
+        if name == "steep1e-05":
+            z = zero_variance_share(ref)                              # from the numpy restatement alone
+            assert z >= ZERO_VARIANCE_SHARE, f"only {z:.3f} of the steep map's finite records have no variance left"
+        if name == "hostile":
+            assert not np.isfinite(ref).all()                         # infinite moments do reach the per-hit operators
+        duv, dlod = dev(uv), dev(lod)
+        drec = m.lookup(duv, dlod)
+        rec = to_np(drec)
+        assert same(rec, ref), (name, first_diff(rec, ref))
+        for (lname, b), (oname, fres) in zip(lobes(ctx), LEAN_LOBES_T):
+            assert lname == oname
+            ob = oracle.microfacet(oname, fres, True)
+            for filtering in (True, False):
+                for scale in (1.0, 0.37, 0.0):
+                    tag = (name, lname, filtering, scale)
+                    for op in ("eval", "evalp", "pdf"):
+                        want = oracle.eval_lean(ob, i, o, LEAN_BASE_T, scale, rec, op, filtering=filtering)
+                        got = b.eval_lean(di, do, base, scale, drec, want=op, return_params=True, filtering=filtering)
+                        fused = b.eval_leanmap(di, do, m, duv, dlod, base, scale, want=op, return_params=True, filtering=filtering)
+                        for how, g in (("eval_lean", got), ("eval_leanmap", fused)):
+                            for what, x, y in zip(("value", "pdfparams"), g, want):
+                                assert same(to_np(x), y), (tag, op, how, what, first_diff(to_np(x), y))
+                    for is_ in (True, False):
+                        want = oracle.sample_lean(ob, u1, u2, o, LEAN_BASE_T, scale, rec, evalp_is=is_, filtering=filtering)
+                        got = b.sample_lean(d1, d2, do, base, scale, drec, evalp_is=is_, return_params=True, filtering=filtering)
+                        fused = b.sample_leanmap(d1, d2, do, m, duv, dlod, base, scale, evalp_is=is_, return_params=True, filtering=filtering)
+                        for how, g in (("sample_lean", got), ("sample_leanmap", fused)):
+                            assert len(g) == len(want)
+                            for k, (x, y) in enumerate(zip(g, want)):
+                                assert same(to_np(x), y), (tag, "evalp_is" if is_ else "sample", how, k, first_diff(to_np(x), y))
+        m.close()

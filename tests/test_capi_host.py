@@ -204,3 +204,79 @@ def test_params_that_carry_their_resolved_form():
                     with pytest.raises(djb.exc):
                         lam.eval(i, o, q)
     ctx.close()
+
+
+def test_degenerate_params_that_carry_their_resolved_form():
+    """djb_params_resolve legitimately writes rho == +-1.0f (elliptic(1, 1e-4, pi/4), ...) and radii near both ends of the float range
+    (tests/param_space_cases.py, the `degenerate` sets): the reference answers all of them, the plain djb_params path returns its bits,
+    and the cached form -- what the C++ facade's params objects always pass -- must return the same bits with the same status, for one
+    pair and for a batch.  (Up to ABI 235's first release the cached form was refused unless -1 < rho < 1.)"""
+    import param_space_cases as ps
+    ctx = djb.Context("cpu")
+    degenerate = [p for tag, p in ps.CASES if tag == "degenerate"]
+    assert len(degenerate) >= 7
+    lib = _lib.load()
+    rhos = []
+    for p in degenerate:
+        r = _lib.ParamsResolved(); _lib.check(lib.djb_params_resolve(C.byref(ps.mk_params(p)._p), C.byref(r))); rhos.append(r.rho)
+    assert sum(abs(r) == 1.0 for r in rhos) >= 4, rhos            # the sets do reach the limit the old range test excluded
+    for ndf in ("ggx", "beckmann"):
+        g = getattr(djb, ndf)(djb.fresnel.schlick((0.9, 0.6, 0.3)), True, ctx=ctx)
+        for n in (1, 257):
+            i, o = synth.directions_aos(n, 5), synth.directions_aos(n, 6)
+            u1, u2 = synth.uniforms(n, 7), synth.uniforms(n, 8)
+            for p in degenerate:
+                plain, cached = ps.mk_params(p), ps.mk_cached(p)
+                sp, a = ps.product_outputs(g, (i, o, u1, u2), plain)
+                sc, b = ps.product_outputs(g, (i, o, u1, u2), cached)
+                assert sp is None and sc is None, (ndf, p, n, sp, sc)
+                assert sorted(a) == sorted(b) and len(a) == 10
+                for k in a:
+                    assert np.array_equal(ps.value_bits(a[k]), ps.value_bits(b[k])), (ndf, p, n, k)
+    ctx.close()
+
+
+def test_a_stray_resolved_flag_is_still_refused():
+    """DJB_PARAMS_RESOLVED_FOLLOWS on a djb_params that no resolved form follows -- zeros, garbage bytes, the resolved form of ANOTHER
+    parameter set, or a djb_params edited after it was resolved -- must fail with DJB_ERR_INVALID_ARGUMENT, not be read as parameters:
+    the resolved form repeats its djb_params' values bit for bit, and that is checked."""
+    import param_space_cases as ps
+    lib = _lib.load()
+    ctx = djb.Context("cpu")
+    g = djb.ggx(ctx=ctx)
+    i, o = synth.directions_aos(4, 5), synth.directions_aos(4, 6)
+    rng = np.random.default_rng(11)
+
+    def flagged(c):
+        q = djb.microfacet.params.standard(); q._p = c.p; q._keep = c
+        return q
+
+    def refused(c, why):
+        with pytest.raises(djb.exc) as e:
+            g.eval(i, o, flagged(c))
+        assert e.value.status_name == "DJB_ERR_INVALID_ARGUMENT" and "no resolved parameter set follows" in str(e.value), why
+        with pytest.raises(djb.exc):
+            g.sample(synth.uniforms(4, 7), synth.uniforms(4, 8), o, flagged(c))
+
+    sets = [None, ("elliptic", 0.3, 0.2, 0.5), ("pdfparams", 0.4, 0.25, 0.3, 0.1, -0.05), ("elliptic", 1.0, 1e-4, np.pi / 4)]
+    for p in sets:
+        plain = djb.microfacet.params.standard() if p is None else ps.mk_params(p)
+        c = ps.Cached(); c.p = plain._p; c.p.kind |= 0x100
+        refused(c, (p, "zeros"))
+        for _ in range(64):
+            junk = rng.integers(0, 256, C.sizeof(_lib.ParamsResolved), dtype=np.uint8).tobytes()
+            C.memmove(C.byref(c.r), junk, len(junk))
+            refused(c, (p, "garbage"))
+        # plausible garbage: positive scales, a correlation inside (-1, 1) -- what the range test of ABI 231 let through
+        c.r = _lib.ParamsResolved(); c.r.ax = 0.5; c.r.ay = 0.25; c.r.rho = 0.1; c.r.sqrt_one_minus_rho_sqr = 0.99; c.r.n[2] = 1.0
+        c.r.a1 = 0.5; c.r.a2 = 0.25
+        refused(c, (p, "plausible garbage"))
+        other = ("elliptic", 0.31, 0.2, 0.5)
+        _lib.check(lib.djb_params_resolve(C.byref(ps.mk_params(other)._p), C.byref(c.r)))
+        refused(c, (p, "another set's resolved form"))
+        if p is not None:
+            good = ps.mk_cached(p)._keep
+            g.eval(i, o, flagged(good))                          # the real thing is accepted ...
+            good.p.v[1] = good.p.v[1] * 2                        # ... until its djb_params is edited behind the resolved form's back
+            refused(good, (p, "edited after resolve"))
+    ctx.close()

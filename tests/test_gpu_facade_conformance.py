@@ -263,3 +263,28 @@ def test_anisotropic_and_lean(facade, oracle, inputs):
     for which, args in (("pdf1", (phi,)), ("cdf1", (phi,)), ("qf1", (u1,)), ("pdf2", (th, phi)), ("cdf2", (th, phi)), ("qf2", (u2, phi))):
         close(f"aniso {which}", facade.aniso_query(ft, which, *args), oracle.aniso_query(ot, which, *args), 2e-4)
     close("aniso eval", facade.eval(ft, i, o), oracle.eval(ot, i, o), 2e-4)
+
+
+import param_space_cases as ps      # noqa: E402
+
+# not golden_cases.PARAM_CASES (the golden files index that list): the sets on which djb_params_resolve reaches a limit
+DEGENERATE_PARAM_CASES = [p for tag, p in ps.CASES if tag == "degenerate"]
+
+
+@pytest.mark.parametrize("ndf", ["ggx", "beckmann"])
+def test_degenerate_parameter_sets(facade, oracle, ndf):
+    """rho == +-1 (elliptic(1, 1e-4, pi/4), ...) and radii near both ends of the float range through the C++ facade, whose params objects
+    always pass the cached form (djb_params_cached): the reference answers these sets, so the facade must -- with the oracle's bits, on
+    pairs half of which the oracle's sampler placed inside the lobe."""
+    fres = ("schlick", 1.0, 0.71, 0.29)
+    f, b = facade.microfacet(ndf, fres, True), oracle.microfacet(ndf, fres, True)
+    for p in DEGENERATE_PARAM_CASES:
+        want = oracle.params_get(p); got = facade.params_get(p)
+        assert (np.isnan(want) | (bits(got) == bits(want))).all(), (p, got, want)
+        i, o, u1, u2 = ps.pairs(oracle, b, p, N)
+        for op in ("eval", "evalp", "pdf"):
+            close(f"{ndf}/{p}/{op}", facade.eval(f, i, o, p, op), oracle.eval(b, i, o, p, op))
+        close(f"{ndf}/{p}/sample", facade.sample(f, u1, u2, o, p), oracle.sample(b, u1, u2, o, p))
+        for tag, x, y in zip(("w", "i", "pdf"), facade.evalp_is(f, u1, u2, o, p), oracle.evalp_is(b, u1, u2, o, p)):
+            close(f"{ndf}/{p}/evalp_is {tag}", x, y)
+    facade.destroy(f)

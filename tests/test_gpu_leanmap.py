@@ -128,3 +128,60 @@ def test_maps_give_their_hbm_back(gpu_ctx):
     m = djb.leanmap.from_dmap(d[:64, :64], 0.1, ctx=c)
     c.close()
     m.close()
+
+
+def test_map_records_through_the_per_hit_operators_against_the_oracle_device_arrays(gpu_ctx, oracle):
+    """records every fixture map, the hostile map and the steep (zero-variance) maps produce, through eval_lean / sample_lean and the fused
+    eval_leanmap / sample_leanmap kernels, against oracle.eval_lean / oracle.sample_lean: values and written-back pdfparams"""
+    lc.check_map_records_against_oracle(gpu_ctx, oracle, device="cuda:0")
+
+
+def test_map_records_through_the_per_hit_operators_against_the_oracle_host_arrays(gpu_ctx, oracle):
+    lc.check_map_records_against_oracle(gpu_ctx, oracle)                 # host batches: the chunked pipeline in front of the same kernels
+    lc.check_map_records_against_oracle(gpu_ctx, oracle, n=37)           # ... and the host twin
+
+
+def _check_large_map(m, l0, first_level, n_lookups, window):
+    """levels first_level .. top == pyramid_np; n_lookups hostile lookups and every texel centre of a window of level 0 == lookup_np"""
+    h, w = l0.shape[:2]
+    ref = lc.pyramid_np(l0)
+    assert (m.width, m.height, m.levels) == (w, h, len(ref))
+    for l in range(first_level, m.levels):
+        got = m.level(l)
+        assert got.shape == ref[l].shape and lc.same(got, ref[l]), (w, h, l, lc.first_diff(got, ref[l]))
+    uv, lod = lc.hostile_coords(n_lookups, m.levels, 43)
+    want = lc.lookup_np(ref, uv, lod)
+    got = m.lookup(uv, lod)
+    assert lc.same(got, want), (w, h, lc.first_diff(got, want))
+    wh, ww = min(window, h), min(window, w)
+    y0, x0 = (h - wh) // 2, (w - ww) // 3
+    yy, xx = np.mgrid[y0:y0 + wh, x0:x0 + ww]
+    centres = np.stack([(xx.ravel() + 0.5) / w, (yy.ravel() + 0.5) / h], 1).astype(f32)
+    got = m.lookup(centres, np.zeros(len(centres), f32))
+    assert lc.same(got, lc.lookup_np(ref, centres, np.zeros(len(centres), f32))), (w, h, "texel centres")
+
+
+def test_large_and_extreme_map_shapes(gpu_ctx):
+    """The builder, pyramid and lookup kernels at sizes where the closed form for a level's offset, 32-bit texel indices and the grid
+    sizes are first exercised on the GPU (the value checks above stop at 128 x 128): from_dmap of an 8192 x 4096 random height map --
+    1.4 GB of device memory --, from_moments of 8192 x 2 and 2 x 8192.  Every level from 3 up == the numpy pyramid, 2^20 hostile lookups
+    and all texel centres of a 256 x 256 window of level 0 == the numpy lookup.  One map at a time."""
+    rng = np.random.default_rng(8192)
+    cpu = djb.cpu_context()
+    d = rng.integers(0, 256, (4096, 8192), dtype=np.uint8)
+    nmap = djb.dmap_to_nmap(d, 0.1, ctx=cpu)                              # the host path (held to the reference tool's bytes by test_leanmap_host.py)
+    assert np.array_equal(djb.dmap_to_nmap(d, 0.1, ctx=gpu_ctx), nmap)
+    m = djb.leanmap.from_dmap(d, 0.1, 1e-5, ctx=gpu_ctx)
+    try:
+        _check_large_map(m, lc.nmap2leanmap_np(nmap, 1e-5), 3, 1 << 20, 256)
+    finally:
+        m.close()
+    del nmap, d
+    gc.collect()
+    for h, w in ((2, 8192), (8192, 2)):
+        mom = (rng.standard_normal((h, w, 5)) * 3).astype(f32)
+        m = djb.leanmap.from_moments(mom, ctx=gpu_ctx)
+        try:
+            _check_large_map(m, mom, 0, 1 << 20, 256)
+        finally:
+            m.close()

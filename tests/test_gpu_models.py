@@ -116,9 +116,10 @@ def test_model_fast_tier_selftest(gpu_ctx, kind):
         assert r["g1_mismatch"] == 0 and r["ndf_mismatch"] == 0 and r["ndf"] == 3 * 0x3f800000, (name, r)
 
 
-def test_sgd_fast_tier_equals_exact_chain(gpu_ctx, monkeypatch):
-    """sgd::eval through the fast tier against the same kernel on objects created with the tier off (DJB_SGD_FAST=0): equal bits,
-    also on a row outside the tier's domain (theta0 beyond 4: the flag is cleared at creation)."""
+def test_sgd_fast_tier_equals_exact_chain(gpu_ctx, oracle, monkeypatch):
+    """sgd::eval through the fast tier against the same kernel on objects created with the tier off (DJB_SGD_FAST=0): equal bits;
+    and a row outside the tier's domain (theta0 beyond 4: the flag is cleared at creation) against the oracle's object of the same row,
+    in bits (more user-supplied rows: test_gpu_param_space.py::test_user_supplied_model_rows)."""
     n = 1 << 18
     i = synth.directions_aos(n, synth.SEED_I, 31); o = synth.directions_aos(n, synth.SEED_O, 31)
     for name in ("gold-metallic-paint", "green-acrylic", "ss440", "alumina-oxide"):
@@ -130,4 +131,6 @@ def test_sgd_fast_tier_equals_exact_chain(gpu_ctx, monkeypatch):
     row = np.array(param_tables.sgd_params("gold-metallic-paint"), np.float64)
     row[30:33] = (4.5, -4.5, 0.1)
     out = djb.sgd.from_params(row, ctx=gpu_ctx).eval(i, o)
-    assert np.isfinite(out).all()
+    from param_space_cases import oracle_model, value_bits
+    want = oracle.eval(oracle_model(oracle, "sgd", row), i, o)
+    assert np.isfinite(want).all() and np.array_equal(value_bits(out), value_bits(want)), int(np.sum(value_bits(out) != value_bits(want)))

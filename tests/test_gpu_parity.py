@@ -690,10 +690,7 @@ def hostile_pairs(dirs):
     return i, o
 
 
-def value_bits(a):
-    """the bits of every value, signs of zeros included; NaNs (whose payload is the processor's business) as one pattern"""
-    a = np.ascontiguousarray(a, np.float32)
-    return np.where(np.isnan(a), np.uint32(0x7fc00000), a.view(np.uint32))
+from param_space_cases import value_bits      # noqa: E402  (the bits of every value, signs of zeros included, NaNs as one pattern)
 
 
 @pytest.mark.parametrize("ndf", ["ggx", "beckmann"])

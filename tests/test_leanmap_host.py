@@ -49,3 +49,7 @@ def test_filtered_moments_widen_the_lobe(ctx):
 
 def test_errors_and_lifetime(ctx):
     lc.check_errors(ctx)
+
+
+def test_map_records_through_the_per_hit_operators_against_the_oracle(ctx, oracle):
+    lc.check_map_records_against_oracle(ctx, oracle)

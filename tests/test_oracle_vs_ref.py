@@ -210,3 +210,24 @@ def test_sgd_abc_all_materials(oracle, reference, inputs):
     with pytest.raises(RuntimeError) as e:
         reference.sgd("no-such-material")
     assert "No SGD parameters for no-such-material" in str(e.value)
+
+
+import param_space_cases as ps
+
+
+@pytest.mark.parametrize("case", ps.CASES, ids=ps.case_id)
+def test_parameter_space_bit_exact(oracle, reference, case):
+    """The parameter table of tests/param_space_cases.py -- the sharp and contract kernels' domain edges, offset lobes, rho = +-1, radii near
+    both ends of the float range: oracle == real reference for eval / evalp / pdf / sample / evalp_is, both NDFs, shadowing on and off, on
+    pairs half of which the reference's own sampler placed inside the lobe.  Every bit, signs of zeros included (NaN payloads aside).
+    This is what lets the host and GPU suites use the oracle as the reference out there."""
+    tag, p = case
+    for ndf in ("ggx", "beckmann"):
+        for shadow in (True, False):
+            bo, br = oracle.microfacet(ndf, ps.FRESNEL_SCHLICK, shadow), reference.microfacet(ndf, ps.FRESNEL_SCHLICK, shadow)
+            inputs = ps.pairs(oracle, bo, p, (1 << 15) + 37)
+            a, b = ps.oracle_outputs(oracle, bo, inputs, p), ps.oracle_outputs(reference, br, inputs, p)
+            for k in a:
+                assert np.array_equal(ps.value_bits(a[k]), ps.value_bits(b[k])), (ndf, shadow, p, k, int(np.sum(ps.value_bits(a[k]) != ps.value_bits(b[k]))))
+            if shadow:
+                ps.assert_reference_side_conditions(oracle, ndf, case, b["eval"])

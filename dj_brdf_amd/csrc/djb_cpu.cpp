@@ -878,6 +878,56 @@ djb_status sample(djb_ctx *ctx, const djb_brdf *b_, int64_t n, const float *u1, 
 	return DJB_OK;
 }
 
+// the per-bounce step of the dj_merl / dj_utia / dj_sgd / dj_abc plugins (mitsuba/djb_mitsuba.hpp: finish_lobe_sample), any pair of kinds
+template <int PK, int TK>
+void proxy_loop(const Brdf &tb, const Params &tp, const Brdf &pb, const Params &pp, long long k0, long long k1, const float *u1a, const float *u2a,
+                const View &vo, const View &vw_out, const View &vi_out, float *out_pdf)
+{
+	const GlibcTabs gt = glibc_tabs_global();
+	for (long long k = k0; k < k1; ++k) {
+		const v3 o = load3(vo, k);
+		v3 i_, unused_w, w = mk(0, 0, 0); float pdf = 0.0f, unused_pdf;
+		sample_one<PK, false>(pb, pp, u1a[k], u2a[k], o, gt, i_, unused_w, unused_pdf);
+		if (!(i_.z <= 0.0f)) {                                                          // the plugins' side check; a NaN i.z passes
+			v3 fr = mk(0, 0, 0), unused_fr = mk(0, 0, 0);
+			eval_one<PK, 4>(pb, pp, i_, o, unused_fr, pdf);
+			eval_one<TK, 2>(tb, tp, i_, o, fr, unused_pdf);
+			w = divs(fr, pdf);
+		}
+		store3(vw_out, k, w); store3(vi_out, k, i_); out_pdf[k] = pdf;
+	}
+}
+template <int PK>
+void proxy_target(const Brdf &tb, const Params &tp, const Brdf &pb, const Params &pp, long long k0, long long k1, const float *u1a, const float *u2a,
+                  const View &vo, const View &vw_out, const View &vi_out, float *out_pdf)
+{
+	DJB_KIND_SWITCH(tb.kind, (proxy_loop<PK, K>(tb, tp, pb, pp, k0, k1, u1a, u2a, vo, vw_out, vi_out, out_pdf)))
+}
+djb_status evalp_is_proxy(djb_ctx *ctx, const djb_brdf *target, const djb_brdf *proxy, int64_t n, const float *u1, const float *u2,
+                          const djb_vec3_view *o, const djb_params *target_params, const djb_params *proxy_params,
+                          const djb_vec3_view *out_w, const djb_vec3_view *out_i, float *out_pdf)
+{
+	if (!target || !proxy) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null brdf (%s)", !target ? "target" : "proxy");
+	if (n < 0) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: negative batch size");
+	if (B(target)->ctx != B(proxy)->ctx) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: target and proxy belong to different contexts");
+	const Brdf &tb = B(target)->dev, &pb = B(proxy)->dev;
+	Params tp, pp;
+	djb_status st = params_for(target_params, tb.kind, &tp);
+	if (st != DJB_OK) return st;
+	if ((st = params_for(proxy_params, pb.kind, &pp)) != DJB_OK) return st;
+	if (!u1 || !u2 || !valid(o) || !valid(out_w) || !valid(out_i) || !out_pdf) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null argument");
+	if (pb.kind == KIND_USER) {      // as in sample(): a radial user NDF that samples the Smith way needs qf2_radial / qf3_radial
+		const UserNdf &u = B(proxy)->ndf;
+		if (u.p22_radial && (!u.qf2_radial || !u.qf3_radial) && u.supports_smith_vndf_sampling(u.user))
+			return djbk::set_error(DJB_ERR_NOT_IMPLEMENTED, "djb_error: Not Implemented");
+	}
+	const View vo = view_of(o), vw = view_of(out_w), vi = view_of(out_i);
+	parallel_for(C(ctx), n, 2048, [&](long long k0, long long k1) {
+		DJB_KIND_SWITCH(pb.kind, (proxy_target<K>(tb, tp, pb, pp, k0, k1, u1, u2, vo, vw, vi, out_pdf)))
+	});
+	return DJB_OK;
+}
+
 djb_status eval_pp(djb_ctx *ctx, const djb_brdf *b_, int64_t n, const djb_vec3_view *i, const djb_vec3_view *o, const float *rec,
                    int mode, const float *base5, float scale, int lean_flags, int want, const djb_vec3_view *out_fr, float *out_pdf,
                    float *out_pp)

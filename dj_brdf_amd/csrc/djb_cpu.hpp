@@ -83,6 +83,10 @@ djb_status eval(djb_ctx *, const djb_brdf *, int64_t n, const djb_vec3_view *i, 
 djb_status sample(djb_ctx *, const djb_brdf *, int64_t n, const float *u1, const float *u2, uint32_t seed_u1, uint32_t seed_u2,
                   uint64_t start, const djb_vec3_view *o, const djb_params *, const djb_vec3_view *out_w,
                   const djb_vec3_view *out_i, float *out_pdf);
+// proxy importance sampling: i = proxy.sample, pdf = proxy.pdf(i, o), weight = target.evalp(i, o) / pdf; 0 and 0 where i.z <= 0.  Every pair of kinds
+djb_status evalp_is_proxy(djb_ctx *, const djb_brdf *target, const djb_brdf *proxy, int64_t n, const float *u1, const float *u2,
+                          const djb_vec3_view *o, const djb_params *target_params, const djb_params *proxy_params,
+                          const djb_vec3_view *out_w, const djb_vec3_view *out_i, float *out_pdf);
 djb_status eval_pp(djb_ctx *, const djb_brdf *, int64_t n, const djb_vec3_view *i, const djb_vec3_view *o, const float *rec,
                    int mode, const float *base5, float scale, int lean_flags, int want, const djb_vec3_view *out_fr, float *out_pdf,
                    float *out_pp);

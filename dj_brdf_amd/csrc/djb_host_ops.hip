@@ -465,6 +465,64 @@ try {
 }
 DJB_ABI_CATCH
 
+// proxy importance sampling: the per-bounce step of the dj_merl / dj_utia / dj_sgd / dj_abc plugins (mitsuba/djb_mitsuba.hpp: finish_lobe_sample) --
+// direction and pdf from `proxy`, f_r cos from `target`, weight = 0 and pdf = 0 where i.z <= 0.  One launch for device memory
+// (djb_kernels_proxy.hip); DJB_OPT_CONTRACT_1E5 does not reach it (there is no approximate tier)
+static djb_status evalp_is_proxy_common(djb_ctx *ctx, const djb_brdf *target, const djb_brdf *proxy, int64_t n, const float *u1, const float *u2,
+                                        const djb_vec3_view *o, const djb_params *target_params, const djb_params *proxy_params,
+                                        const djb_vec3_view *out_w, const djb_vec3_view *out_i, float *out_pdf, int mem)
+{
+	if (!target || !proxy) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null brdf (%s)", !target ? "target" : "proxy");
+	if (!ctx) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null ctx");
+	djb_status st = cpu_pair_check(ctx, target);
+	if (st != DJB_OK) return st;
+	if ((st = cpu_pair_check(ctx, proxy)) != DJB_OK) return st;
+	if (is_cpu(ctx)) return djbcpu::evalp_is_proxy(ctx, target, proxy, n, u1, u2, o, target_params, proxy_params, out_w, out_i, out_pdf);
+	if (target->ctx != proxy->ctx || target->device != proxy->device)
+		return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: target and proxy belong to different contexts");
+	if (const djb_brdf *tt = scalar_twin(ctx, target, n, mem)) {
+		const djb_brdf *pt = scalar_twin(ctx, proxy, n, mem);
+		if (pt) return djbcpu::evalp_is_proxy(djbcpu::twin_ctx(), tt, pt, n, u1, u2, o, target_params, proxy_params, out_w, out_i, out_pdf);
+	}
+	if ((st = check_call(ctx, target, n, mem)) != DJB_OK) return st;
+	if ((st = check_call(ctx, proxy, n, mem)) != DJB_OK) return st;
+	if (!djbk::evalp_is_proxy_supported(target->dev.kind, proxy->dev.kind) || (target->dev.kind == DJB_KIND_MERL && target->dev.merl_sparse))
+		return fail(DJB_ERR_NOT_IMPLEMENTED, "djb_error: evalp_is_proxy on the GPU takes a merl / utia / sgd / abc target and a ggx / beckmann / tabular / "
+		            "tabular_anisotropic proxy (target kind %d, proxy kind %d)", target->dev.kind, proxy->dev.kind);
+	std::lock_guard<std::recursive_mutex> call_lock(ctx->call_mu);
+	Params tp, pp;
+	if ((st = device_params(target_params, &tp, target->dev.kind)) != DJB_OK) return st;
+	if ((st = device_params(proxy_params, &pp, proxy->dev.kind)) != DJB_OK) return st;
+	if (mem == DJB_MEM_HOST && n > SMALL_N && u1 && u2 && o && out_i && out_w && out_pdf) {   // large host batch: chunked, both PCIe directions busy
+		bool taken = false;
+		std::vector<PipeArr> ins{ PipeArr::arr(u1), PipeArr::arr(u2), PipeArr::vec(o) }, outs{ PipeArr::vec(out_i), PipeArr::vec(out_w), PipeArr::arr(out_pdf) };
+		st = host_pipeline(ctx, n, ins, outs, [&](long long m, int s) {
+			djb_vec3_view dvo = ins[2].view(s), dvi = outs[0].view(s), dvw = outs[1].view(s);
+			return evalp_is_proxy_common(ctx, target, proxy, m, ins[0].dev[s], ins[1].dev[s], &dvo, target_params, proxy_params, &dvw, &dvi,
+			                             outs[2].dev[s], DJB_MEM_DEVICE);
+		}, &taken);
+		if (taken || st != DJB_OK) return st;
+	}
+	Staged sg(ctx, n, mem);
+	View vo, vi, vw; const float *d1, *d2; float *dpdf = nullptr;
+	if ((st = sg.in_f(u1, &d1)) != DJB_OK) return st;
+	if ((st = sg.in_f(u2, &d2)) != DJB_OK) return st;
+	if ((st = sg.in_vec(o, &vo)) != DJB_OK) return st;
+	if ((st = sg.out_vec(out_i, &vi)) != DJB_OK) return st;
+	if ((st = sg.out_vec(out_w, &vw)) != DJB_OK) return st;
+	if ((st = sg.out_arr(out_pdf, &dpdf)) != DJB_OK) return st;
+	HIP_TRY(djbk::launch_evalp_is_proxy(ctx->stream, target->dev, tp, proxy->dev, pp, n, d1, d2, vo, vw, vi, dpdf, ctx->merl_exact_only != 0));
+	return sg.finish();
+}
+
+djb_status djb_evalp_is_proxy_batch(djb_ctx *ctx, const djb_brdf *target, const djb_brdf *proxy, int64_t n, const float *u1, const float *u2,
+                                    const djb_vec3_view *o, const djb_params *target_params, const djb_params *proxy_params,
+                                    const djb_vec3_view *out_weight, const djb_vec3_view *out_i, float *out_pdf, int mem)
+try {
+	return evalp_is_proxy_common(ctx, target, proxy, n, u1, u2, o, target_params, proxy_params, out_weight, out_i, out_pdf, mem);
+}
+DJB_ABI_CATCH
+
 djb_status djb_sample_rng_batch(djb_ctx *ctx, const djb_brdf *b, int64_t n, uint32_t seed_u1, uint32_t seed_u2,
                                 uint64_t start, const djb_vec3_view *o, const djb_params *params,
                                 const djb_vec3_view *out_i)

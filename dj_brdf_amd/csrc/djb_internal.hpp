@@ -41,6 +41,13 @@ hipError_t launch_sample_contract_selftest(hipStream_t s, const Brdf &b, const P
 hipError_t launch_sample_contract_attack(hipStream_t s, const Brdf &b, const Params &p, long long n, float *u1, float *u2, const View &o, int iters,
                                          uint32_t seed, float *best, unsigned long long *counters);
 
+// proxy importance sampling (djb_kernels_proxy.hip): i = proxy.sample(u1, u2, o), pdf = proxy.pdf(i, o), weight = target.evalp(i, o) / pdf,
+// weight = 0 and pdf = 0 where i.z <= 0 -- one launch.  Targets: merl, utia, sgd, abc; proxies: ggx, beckmann, tabular, tabular_anisotropic
+bool evalp_is_proxy_supported(int target_kind, int proxy_kind);
+hipError_t launch_evalp_is_proxy(hipStream_t s, const Brdf &target, const Params &target_p, const Brdf &proxy, const Params &proxy_p, long long n,
+                                 const float *u1, const float *u2, const View &o, const View &out_w, const View &out_i, float *out_pdf,
+                                 bool merl_exact);
+
 // per-pair params: rec = n x 5 floats; mode 0 = pdfparams records, mode 1 = LEAN texel moments composed with
 // base5 = params_to_lrep(base) (unscaled), scale = dmapscale, lean_flags = DJB_LEAN_* as dj_beckmannconductor does;
 // out_pp (optional, modes 1 and 2) receives the resolved pdfparams.  mode 2 = mode 1 with the record of pair k looked up in a

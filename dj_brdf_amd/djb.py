@@ -404,6 +404,24 @@ class brdf:
         del k1, k2
         return w.keep, i.keep, pdf
 
+    def evalp_is_proxy(self, proxy, u1, u2, o, user_param=None, proxy_param=None):
+        """(weight, i, pdf) of proxy importance sampling, the per-bounce step of the dj_merl / dj_utia / dj_sgd / dj_abc plugins:
+        i = proxy.sample(u1, u2, o, proxy_param), pdf = proxy.pdf(i, o, proxy_param), weight = self.evalp(i, o, user_param) / pdf,
+        and weight = 0, pdf = 0 where i.z <= 0.  One kernel launch on the GPU (djb_evalp_is_proxy_batch)."""
+        if not isinstance(proxy, brdf) or not proxy._h or not self._h:     # host code on either side (a user_brdf)
+            return _evalp_is_proxy_composed(self, proxy, u1, u2, o, user_param, proxy_param)
+        lib = _lib.load()
+        vo = _Vec(o)
+        k1, p1 = _scalar_in(u1, vo)
+        k2, p2 = _scalar_in(u2, vo)
+        w, i = vo.like(), vo.like()
+        pdf, pdf_ptr = vo.scalars()
+        _lib.check(lib.djb_evalp_is_proxy_batch(self.ctx._h, self._h, proxy._h, C.c_int64(vo.n), C.c_void_p(p1), C.c_void_p(p2),
+                                                C.byref(vo.view), _params_ptr(user_param), _params_ptr(proxy_param),
+                                                C.byref(w.view), C.byref(i.view), C.c_void_p(pdf_ptr), C.c_int(vo.mem)))
+        del k1, k2
+        return w.keep, i.keep, pdf
+
     # ---- static utilities (dj_brdf.h:99-100)
     @staticmethod
     def io_to_hd(i, o, ctx: Optional[Context] = None):
@@ -1112,6 +1130,20 @@ def _sample_source(src, qi, qo) -> np.ndarray:
     rgb = np.zeros((qi.shape[0], 3), np.float32)
     rgb[ok] = np.asarray(src.eval(qi[ok], qo[ok]), np.float32).reshape(-1, 3)
     return rgb
+
+
+def _evalp_is_proxy_composed(target, proxy, u1, u2, o, user_param, proxy_param):
+    """evalp_is_proxy where an object is host code (a user_brdf): the objects' own operators composed on host arrays."""
+    o = np.ascontiguousarray(o, np.float32).reshape(-1, 3)
+    i_ = np.asarray(proxy.sample(u1, u2, o, proxy_param), np.float32).reshape(-1, 3)
+    pdf_ = np.array(proxy.pdf(i_, o, proxy_param), np.float32)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        inv = (1.0 / pdf_.astype(np.float64)).astype(np.float32)
+        w = (inv[:, None] * np.asarray(target.evalp(i_, o, user_param), np.float32).reshape(-1, 3)).astype(np.float32)
+    side = i_[:, 2] <= 0                      # the plugins' side check (a NaN i.z does not take it)
+    w[side] = 0
+    pdf_[side] = 0
+    return w, i_, pdf_
 
 
 class user_brdf(brdf):

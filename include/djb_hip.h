@@ -63,7 +63,9 @@ extern "C" {
  *        djb_leanmap_create_from_nmap / _from_dmap / _from_moments, djb_leanmap_info, djb_leanmap_get_level, djb_leanmap_destroy,
  *        djb_leanmap_lookup_batch, djb_eval_leanmap_batch, djb_sample_leanmap_batch.
  *        Behaviour under 235, no layout changed: a djb_params_cached is accepted for every set djb_params_resolve can return (rho == +-1 was
- *        refused); what makes it one is that `r` repeats the values of `p` (see djb_params_cached), no longer a range test. */
+ *        refused); what makes it one is that `r` repeats the values of `p` (see djb_params_cached), no longer a range test.
+ *        Additive under 235, no existing entry changed: djb_evalp_is_proxy_batch (proxy importance sampling: direction and pdf from a
+ *        fitted lobe, f_r cos from a measured or data-driven BRDF, in one call). */
 #define DJB_HIP_VERSION 235
 #define DJB_HIP_VERSION_MAJOR(v) ((v) / 100)
 
@@ -364,6 +366,22 @@ djb_status djb_evalp_is_batch(djb_ctx *, const djb_brdf *, int64_t n, const floa
                               const float *u2, const djb_vec3_view *o, const djb_params *params,
                               const djb_vec3_view *out_weight, const djb_vec3_view *out_i,
                               float *out_pdf, int mem);
+/* the per-bounce step of dj_merl / dj_utia / dj_abc / dj_sgd: direction and pdf from `proxy`, f_r cos from `target`.  Per unit
+ *     i      = proxy.sample(u1, u2, o, proxy_params)
+ *     pdf    = proxy.pdf(i, o, proxy_params)                     (microfacet::pdf: dot(i, h) in the denominator, no saturation)
+ *     weight = target.evalp(i, o, target_params) / pdf           (vec3 / float = (1.0f / pdf) * v, dj_brdf.h:601)
+ * and weight = (0, 0, 0), pdf = 0 where i.z <= 0 (the plugins' side check; a NaN i.z does not take it); out_i receives i in both
+ * cases.  o is not guarded (as for djb_evalp_is_batch the caller filters o.z <= 0), and where pdf == 0 with i.z > 0 the weight is
+ * what IEEE division gives.  Bit-identical to djb_sample_batch + djb_pdf_batch on the proxy, djb_evalp_batch on the target and that
+ * division; DJB_OPT_CONTRACT_1E5 does not affect it.  Both objects must belong to the call's context.  On a GPU context a batch
+ * in device memory -- or a host batch above DJB_OPT_HOST_BATCH_MAX -- is ONE kernel launch and takes a merl, utia, sgd or abc target
+ * with a ggx, beckmann, tabular or tabular_anisotropic proxy (any other pair: DJB_ERR_NOT_IMPLEMENTED); CPU contexts and scalar-size
+ * host batches serve every pair of kinds.  DJB_OPT_MERL_EXACT_ONLY sends every pair of a merl target through the exact bin index. */
+djb_status djb_evalp_is_proxy_batch(djb_ctx *, const djb_brdf *target, const djb_brdf *proxy, int64_t n,
+                                    const float *u1, const float *u2, const djb_vec3_view *o,
+                                    const djb_params *target_params, const djb_params *proxy_params,
+                                    const djb_vec3_view *out_weight, const djb_vec3_view *out_i,
+                                    float *out_pdf, int mem);
 /* microfacet and radial queries, batched (dj_brdf.h:258-276, 307-314, 366, 384).  a/b/c are the
  * call's arguments in declaration order, each as a vec3 view (scalars in .x, (x,y) slopes in
  * .x/.y, qf2_radial's (u, cos, sin) in .x/.y/.z); the result is written to out.x (Fresnel: xyz).

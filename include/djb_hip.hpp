@@ -357,6 +357,42 @@ public:
 		checked(djb_evalp_is_batch(ctx(), m_h, (int64_t)n, u1, u2, &vo, params_of(user_param), &vw, &vi,
 		                              out_pdf, DJB_MEM_HOST));
 	}
+	// ---- proxy importance sampling, the per-bounce step of the dj_merl / dj_utia / dj_abc / dj_sgd plugins: the direction and its pdf
+	// from `proxy` (a fitted lobe), f_r cos from this object; weight = 0 and pdf = 0 where i.z <= 0 (djb_evalp_is_proxy_batch)
+	vec3 evalp_is_proxy(const brdf &proxy, float_t u1, float_t u2, const vec3 &o, vec3 *i, float_t *pdf,
+	                    const void *user_param = NULL, const void *proxy_param = NULL) const
+	{
+		vec3 w, i_; float_t pdf_ = 0;
+		evalp_is_proxy(proxy, 1, &u1, &u2, &o, &w, &i_, &pdf_, user_param, proxy_param);
+		if (i) *i = i_;
+		if (pdf) *pdf = pdf_;
+		return w;
+	}
+	void evalp_is_proxy(const brdf &proxy, size_t n, const float_t *u1, const float_t *u2, const vec3 *o, vec3 *out_weight,
+	                    vec3 *out_i, float_t *out_pdf, const void *user_param = NULL, const void *proxy_param = NULL) const
+	{
+		if (!resident() || !proxy.resident()) {          // host code on either side: the objects' own virtuals, composed per unit
+			for (size_t k = 0; k < n; ++k) {
+				const vec3 i_ = proxy.sample(u1[k], u2[k], o[k], proxy_param);
+				out_i[k] = i_; out_weight[k] = vec3(0); out_pdf[k] = 0;
+				if (i_.z <= 0) continue;
+				out_pdf[k] = proxy.pdf(i_, o[k], proxy_param);
+				out_weight[k] = evalp(i_, o[k], user_param) / out_pdf[k];
+			}
+			return;
+		}
+		djb_vec3_view vo = hip::view(o), vw = hip::view(out_weight), vi = hip::view(out_i);
+		checked(djb_evalp_is_proxy_batch(ctx(), m_h, proxy.m_h, (int64_t)n, u1, u2, &vo, params_of(user_param), proxy.params_of(proxy_param),
+		                                 &vw, &vi, out_pdf, DJB_MEM_HOST));
+	}
+	void evalp_is_proxy_device(const brdf &proxy, int64_t n, const float_t *u1, const float_t *u2, const djb_vec3_view &o,
+	                           const djb_vec3_view &out_weight, const djb_vec3_view &out_i, float_t *out_pdf,
+	                           const void *user_param = NULL, const void *proxy_param = NULL) const
+	{
+		need_resident("evalp_is_proxy_device"); proxy.need_resident("evalp_is_proxy_device");
+		checked(djb_evalp_is_proxy_batch(ctx(), m_h, proxy.m_h, n, u1, u2, &o, params_of(user_param), proxy.params_of(proxy_param),
+		                                 &out_weight, &out_i, out_pdf, DJB_MEM_DEVICE));
+	}
 	// ---- batch, device-resident (SoA or strided views in HBM; asynchronous on the context stream): resident objects only
 	void eval_device(int64_t n, const djb_vec3_view &i, const djb_vec3_view &o, const djb_vec3_view &out,
 	                 const void *user_param = NULL) const

@@ -13,6 +13,15 @@ using djbdev::Brdf;
 using djbdev::Params;
 using djbdev::View;
 
+// workgroups of `block` threads for n units: one per `block` units, at most `cap` (the kernels stride over the batch beyond), at least one
+inline int grid_capped(long long n, int block, long long cap)
+{
+	long long blocks = (n + block - 1) / block;
+	if (blocks > cap) blocks = cap;
+	if (blocks < 1) blocks = 1;
+	return (int)blocks;
+}
+
 // WANT bits: 1 eval, 2 evalp, 4 pdf (1 and 2 are exclusive)
 hipError_t launch_eval(hipStream_t s, const Brdf &b, const Params &p, long long n,
                        const View &i, const View &o, const View &out_fr, float *out_pdf, int want);

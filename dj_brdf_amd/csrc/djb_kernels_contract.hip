@@ -31,14 +31,6 @@ namespace {
 
 constexpr int BLOCK = 256;
 
-inline int grid_for(long long n, long long cap = 256LL * 64)
-{
-	long long blocks = (n + BLOCK - 1) / BLOCK;
-	if (blocks > cap) blocks = cap;
-	if (blocks < 1) blocks = 1;
-	return (int)blocks;
-}
-
 #include "djb_contract_device.inc"   // CtParams, the shortcuts, ct_sigma, the Fresnel terms, the evalp_is tail (shared with the samplers)
 
 // Beckmann.  exp(-r^2) makes D as sensitive as r^2 is large: an ulp of the half vector's slope moves D by r^2 2^-23, and
@@ -564,7 +556,7 @@ hipError_t launch_ct(hipStream_t s, const Brdf &b, const Params &p, const CtPara
 	// one workgroup per 1024 pairs, no grid-stride cap: measured (profiles/r03/contract_grid.txt, 1e8 pairs) 0.696 ms with
 	// the full grid against 0.77-0.82 ms with 2048 ... 32768 persistent workgroups -- the hardware dispatcher keeps more
 	// loads in flight across workgroup boundaries than a wave's in-order loop does
-	const dim3 g(grid_for(n4, 0x7fffffffLL)), t(BLOCK), gf(grid_for((long long)CT_SHARDS * cap, 2048));
+	const dim3 g(djbk::grid_capped(n4, BLOCK, 0x7fffffffLL)), t(BLOCK), gf(djbk::grid_capped((long long)CT_SHARDS * cap, BLOCK, 2048));
 #define DJB_CT(W_) do { \
 		if (n4 > 0) hipLaunchKernelGGL((k_ct_fast_v4<KIND, W_, FRK>), g, t, 0, s, c, n4, i, o, out, out_pdf, list, cap, count); \
 		hipLaunchKernelGGL((k_ct_fixup<KIND, W_, FRK>), gf, t, 0, s, b, p, n, i, o, out, out_pdf, list, cap, count); } while (0)
@@ -624,7 +616,7 @@ hipError_t launch_contract_selftest(hipStream_t s, const Brdf &b, const Params &
 {
 	CtParams c;
 	if (!ct_params_any(b, p, model_host, &c)) return hipErrorInvalidValue;
-	const dim3 g(grid_for(n, 256LL * 16)), t(BLOCK);
+	const dim3 g(djbk::grid_capped(n, BLOCK, 256LL * 16)), t(BLOCK);
 	if (b.kind == KIND_ABC) hipLaunchKernelGGL((k_ct_selftest<KIND_ABC, -1>), g, t, 0, s, b, p, c, n, seed_i, seed_o, start, family, max_bits, counters);
 	else if (b.kind == KIND_SGD) hipLaunchKernelGGL((k_ct_selftest<KIND_SGD, -1>), g, t, 0, s, b, p, c, n, seed_i, seed_o, start, family, max_bits, counters);
 	else if (b.kind == KIND_BECKMANN) {

@@ -12,14 +12,7 @@ namespace {
 
 constexpr int BLOCK = 256;
 
-inline int grid_for(long long n)
-{
-	long long blocks = (n + BLOCK - 1) / BLOCK;
-	const long long cap = 256LL * 16;   // 256 CUs x 16 resident workgroups' worth, grid-stride beyond
-	if (blocks > cap) blocks = cap;
-	if (blocks < 1) blocks = 1;
-	return (int)blocks;
-}
+constexpr long long GRID_CAP = 256LL * 16;   // 256 CUs x 16 resident workgroups' worth, grid-stride beyond
 
 // The VALU-bound kernels of the analytic lobes (eval, eval_pp, sample of beckmann / ggx) get one
 // workgroup per 256 units: the hardware dispatcher balances the data-dependent work (Beckmann's
@@ -65,14 +58,11 @@ __global__ __launch_bounds__(eval_block(KIND), eval_min_waves(KIND)) void k_eval
 	// (round 6: sgd's polar angles come from the arctangent core below; glibc's acos -- its 21 KB of tables stay in global memory -- only
 	// answers for the units the decided fast tier leaves, djb_fast_models.inc; a row outside that tier's domain pays for it: 5.2 ms per 1e8
 	// pairs instead of 4.0.  Occupancy: 87 VGPRs = 5 waves per SIMD; 6 (16 B of scratch): the same time, 8 (80 B): 3.59 against 3.12 ms)
-	constexpr bool EXPT = KIND == KIND_BECKMANN || KIND == KIND_SGD || KIND == KIND_ABC, POWT = KIND == KIND_SGD || KIND == KIND_ABC,
-	               ACOST = false;
+	constexpr bool EXPT = KIND == KIND_BECKMANN || KIND == KIND_SGD || KIND == KIND_ABC, POWT = KIND == KIND_SGD || KIND == KIND_ABC;
 	__shared__ unsigned long long s_exp[EXPT ? 256 : 1];
 	__shared__ double s_pow[POWT ? 384 : 1];
-	__shared__ double s_acos[ACOST ? 2568 + 128 : 1];
 	if (EXPT) b.exp_lds = glibc_exp_tab_to_lds(s_exp, threadIdx.x, BS);
 	if (POWT) b.pow_lds = glibc_pow_tab_to_lds(s_pow, threadIdx.x, BS);
-	if (ACOST) b.acos_lds = glibc_acos_tab_to_lds(s_acos, threadIdx.x, BS);
 	// the tabulated lobes' table coordinates (acos / atan / atan2 of a float, rounded to float) from the arctangent core (djb_device.hpp)
 	constexpr bool ATANT = KIND == KIND_TABULAR || KIND == KIND_TABULAR_ANISO || KIND == KIND_SGD || FRK == FR_SPLINE;      // ... and the Fresnel spline's (dj_brdf.h:1341)
 	__shared__ double s_atan[ATANT ? 16 : 1];
@@ -245,7 +235,7 @@ template <int KIND, int FRK>
 hipError_t launch_eval_kind_fr(hipStream_t s, const Brdf &b, const Params &p, long long n,
                                const View &i, const View &o, const View &out, float *out_pdf, int want)
 {
-	dim3 g((KIND == KIND_BECKMANN || KIND == KIND_GGX) ? grid_full(n) : grid_for(n)), t(eval_block(KIND));
+	dim3 g((KIND == KIND_BECKMANN || KIND == KIND_GGX) ? grid_full(n) : djbk::grid_capped(n, BLOCK, GRID_CAP)), t(eval_block(KIND));
 	if (eval_block(KIND) != BLOCK) { long long bl = (n + eval_block(KIND) - 1) / eval_block(KIND); g = dim3((unsigned int)(bl < 1 ? 1 : bl > 2048 ? 2048 : bl)); }
 	const bool dn = dense(i) && dense(o) && dense(out);
 	if constexpr (KIND == KIND_BECKMANN && (FRK == FR_IDEAL || FRK == FR_SCHLICK || FRK == FR_UNPOLARIZED)) {
@@ -341,7 +331,7 @@ hipError_t launch_eval_pp_kind_fr(hipStream_t s, const Brdf &b, long long n, con
                                   const float *rec, const LeanCfg &base, const View &out, float *out_pdf,
                                   float *out_pp, int want, const LeanSrc &ls)
 {
-	dim3 g((KIND == KIND_BECKMANN || KIND == KIND_GGX) ? grid_full(n) : grid_for(n)), t(BLOCK);
+	dim3 g((KIND == KIND_BECKMANN || KIND == KIND_GGX) ? grid_full(n) : djbk::grid_capped(n, BLOCK, GRID_CAP)), t(BLOCK);
 	switch (want) {
 	case 1: hipLaunchKernelGGL((k_eval_pp<KIND, 1, MODE, FRK>), g, t, 0, s, b, n, i, o, rec, base, out, out_pdf, out_pp, ls); break;
 	case 2: hipLaunchKernelGGL((k_eval_pp<KIND, 2, MODE, FRK>), g, t, 0, s, b, n, i, o, rec, base, out, out_pdf, out_pp, ls); break;
@@ -463,7 +453,7 @@ hipError_t launch_sample_kind(hipStream_t s, const Brdf &b, const Params &p, lon
                               unsigned long long start, const View &o, const View &out_i,
                               const View *out_w, float *out_pdf)
 {
-	dim3 g((KIND == KIND_BECKMANN || KIND == KIND_GGX) ? grid_full(n) : grid_for(n)), t(BLOCK);
+	dim3 g((KIND == KIND_BECKMANN || KIND == KIND_GGX) ? grid_full(n) : djbk::grid_capped(n, BLOCK, GRID_CAP)), t(BLOCK);
 	View w = out_w ? *out_w : View{ nullptr, nullptr, nullptr, 0 };
 	const bool is = out_w != nullptr, rng = u1 == nullptr;
 	const bool dn = dense(o) && dense(out_i) && dense(w);
@@ -523,7 +513,7 @@ hipError_t launch_sample_pp_kind(hipStream_t s, const Brdf &b, long long n, cons
                                  const float *rec, int mode, const LeanCfg &base, const View &out_i, const View *out_w,
                                  float *out_pdf, float *out_pp, const LeanSrc &ls)
 {
-	dim3 g((KIND == KIND_BECKMANN || KIND == KIND_GGX) ? grid_full(n) : grid_for(n)), t(BLOCK);
+	dim3 g((KIND == KIND_BECKMANN || KIND == KIND_GGX) ? grid_full(n) : djbk::grid_capped(n, BLOCK, GRID_CAP)), t(BLOCK);
 	View w = out_w ? *out_w : View{ nullptr, nullptr, nullptr, 0 };
 #define DJB_SPP(IS_, FRK_) do { if (mode == 0) hipLaunchKernelGGL((k_sample_pp<KIND, IS_, 0, FRK_>), g, t, 0, s, b, n, u1, u2, o, rec, base, out_i, w, out_pdf, out_pp, ls); \
                                 else if (mode == 1) hipLaunchKernelGGL((k_sample_pp<KIND, IS_, 1, FRK_>), g, t, 0, s, b, n, u1, u2, o, rec, base, out_i, w, out_pdf, out_pp, ls); \
@@ -813,7 +803,7 @@ hipError_t launch_query(hipStream_t s, const Brdf &b, const Params &p, int which
                         const View &bb, const View &c, const View &out)
 {
 	if (n <= 0) return hipSuccess;
-	dim3 g(grid_for(n)), t(BLOCK);
+	dim3 g(djbk::grid_capped(n, BLOCK, GRID_CAP)), t(BLOCK);
 	switch (b.kind) {
 	case KIND_BECKMANN: hipLaunchKernelGGL((k_query<KIND_BECKMANN>), g, t, 0, s, b, p, which, n, a, bb, c, out); break;
 	case KIND_GGX:      hipLaunchKernelGGL((k_query<KIND_GGX>), g, t, 0, s, b, p, which, n, a, bb, c, out); break;
@@ -830,7 +820,7 @@ hipError_t launch_io_to_hd(hipStream_t s, long long n, const View &a, const View
                            const View &d, bool inverse)
 {
 	if (n <= 0) return hipSuccess;
-	dim3 g(grid_for(n)), t(BLOCK);
+	dim3 g(djbk::grid_capped(n, BLOCK, GRID_CAP)), t(BLOCK);
 	if (!inverse) hipLaunchKernelGGL((k_io_hd<false>), g, t, 0, s, n, a, b, c, d);
 	else hipLaunchKernelGGL((k_io_hd<true>), g, t, 0, s, n, a, b, c, d);
 	return hipGetLastError();
@@ -839,19 +829,19 @@ hipError_t launch_io_to_hd(hipStream_t s, long long n, const View &a, const View
 hipError_t launch_merl_index(hipStream_t s, long long n, const View &i, const View &o, int32_t *idx)
 {
 	if (n <= 0) return hipSuccess;
-	hipLaunchKernelGGL(k_merl_index, dim3(grid_for(n)), dim3(BLOCK), 0, s, n, i, o, idx);
+	hipLaunchKernelGGL(k_merl_index, dim3(djbk::grid_capped(n, BLOCK, GRID_CAP)), dim3(BLOCK), 0, s, n, i, o, idx);
 	return hipGetLastError();
 }
 
 hipError_t launch_merl_convert(hipStream_t s, const double *samples, long long n, MerlTexel *table)
 {
-	hipLaunchKernelGGL(k_merl_convert, dim3(grid_for(n)), dim3(BLOCK), 0, s, samples, n, table);
+	hipLaunchKernelGGL(k_merl_convert, dim3(djbk::grid_capped(n, BLOCK, GRID_CAP)), dim3(BLOCK), 0, s, samples, n, table);
 	return hipGetLastError();
 }
 
 hipError_t launch_utia_convert(hipStream_t s, const double *samples, long long n, float4 *table)
 {
-	hipLaunchKernelGGL(k_utia_convert, dim3(grid_for(n)), dim3(BLOCK), 0, s, samples, n, table);
+	hipLaunchKernelGGL(k_utia_convert, dim3(djbk::grid_capped(n, BLOCK, GRID_CAP)), dim3(BLOCK), 0, s, samples, n, table);
 	return hipGetLastError();
 }
 
@@ -859,7 +849,7 @@ hipError_t launch_gen_directions(hipStream_t s, long long n, uint32_t seed, unsi
                                  const View &out)
 {
 	if (n <= 0) return hipSuccess;
-	hipLaunchKernelGGL(k_gen_dir, dim3(grid_for(n)), dim3(BLOCK), 0, s, n, seed, start, out);
+	hipLaunchKernelGGL(k_gen_dir, dim3(djbk::grid_capped(n, BLOCK, GRID_CAP)), dim3(BLOCK), 0, s, n, seed, start, out);
 	return hipGetLastError();
 }
 
@@ -867,7 +857,7 @@ hipError_t launch_gen_uniforms(hipStream_t s, long long n, uint32_t seed, unsign
                                float *out)
 {
 	if (n <= 0) return hipSuccess;
-	hipLaunchKernelGGL(k_gen_uni, dim3(grid_for(n)), dim3(BLOCK), 0, s, n, seed, start, out);
+	hipLaunchKernelGGL(k_gen_uni, dim3(djbk::grid_capped(n, BLOCK, GRID_CAP)), dim3(BLOCK), 0, s, n, seed, start, out);
 	return hipGetLastError();
 }
 
@@ -898,7 +888,7 @@ __global__ __launch_bounds__(BLOCK) void k_libm_probe(int fn, long long n, const
 hipError_t launch_libm_probe(hipStream_t s, int fn, long long n, const double *x, const double *y, double *out)
 {
 	if (n <= 0) return hipSuccess;
-	hipLaunchKernelGGL(k_libm_probe, dim3(grid_for(n)), dim3(BLOCK), 0, s, fn, n, x, y, out);
+	hipLaunchKernelGGL(k_libm_probe, dim3(djbk::grid_capped(n, BLOCK, GRID_CAP)), dim3(BLOCK), 0, s, fn, n, x, y, out);
 	return hipGetLastError();
 }
 
@@ -916,7 +906,7 @@ __global__ __launch_bounds__(BLOCK) void k_trig_sweep(int fn, uint32_t first, lo
 hipError_t launch_trig_sweep(hipStream_t s, int fn, uint32_t first, long long n, void *out)
 {
 	if (n <= 0) return hipSuccess;
-	hipLaunchKernelGGL(k_trig_sweep, dim3(grid_for(n)), dim3(BLOCK), 0, s, fn, first, n, out);
+	hipLaunchKernelGGL(k_trig_sweep, dim3(djbk::grid_capped(n, BLOCK, GRID_CAP)), dim3(BLOCK), 0, s, fn, first, n, out);
 	return hipGetLastError();
 }
 
@@ -997,13 +987,13 @@ __global__ __launch_bounds__(BLOCK) void k_model_fast_selftest(Brdf b, long long
 hipError_t launch_model_fast_selftest(hipStream_t s, const Brdf &b, long long n, uint32_t seed, uint32_t first, unsigned long long *counters6)
 {
 	if (n <= 0) return hipSuccess;
-	hipLaunchKernelGGL(k_model_fast_selftest, dim3(grid_for(n)), dim3(BLOCK), 0, s, b, n, seed, first, counters6);
+	hipLaunchKernelGGL(k_model_fast_selftest, dim3(djbk::grid_capped(n, BLOCK, GRID_CAP)), dim3(BLOCK), 0, s, b, n, seed, first, counters6);
 	return hipGetLastError();
 }
 
 hipError_t launch_guard_selftest(hipStream_t s, long long n, uint32_t seed, unsigned long long *counters)
 {
-	hipLaunchKernelGGL(k_guard_selftest, dim3(grid_for(n)), dim3(BLOCK), 0, s, n, seed, counters);
+	hipLaunchKernelGGL(k_guard_selftest, dim3(djbk::grid_capped(n, BLOCK, GRID_CAP)), dim3(BLOCK), 0, s, n, seed, counters);
 	return hipGetLastError();
 }
 
@@ -1012,7 +1002,7 @@ hipError_t launch_histogram_xy(hipStream_t s, long long n, const View &v, int bi
 {
 	if (n <= 0) return hipSuccess;
 	size_t lds = sizeof(unsigned int) * (size_t)bins * bins;
-	hipLaunchKernelGGL(k_hist_xy, dim3(grid_for(n)), dim3(BLOCK), lds, s, n, v, bins, counts);
+	hipLaunchKernelGGL(k_hist_xy, dim3(djbk::grid_capped(n, BLOCK, GRID_CAP)), dim3(BLOCK), lds, s, n, v, bins, counts);
 	return hipGetLastError();
 }
 

@@ -26,13 +26,7 @@ constexpr int BLOCK = 256;
 #define DJB_MERL_GRID_CAP (256LL * 64)
 #endif
 
-inline int grid_for(long long n, long long cap = 256LL * 16)
-{
-	long long blocks = (n + BLOCK - 1) / BLOCK;
-	if (blocks > cap) blocks = cap;
-	if (blocks < 1) blocks = 1;
-	return (int)blocks;
-}
+constexpr long long GRID_CAP = 256LL * 16;
 
 template <int WANT>
 DJB_DEV void merl_emit(const Brdf &b, int idx, v3 i, long long k, const View &vout, float *out_pdf)
@@ -315,9 +309,9 @@ hipError_t launch_tt(hipStream_t s, const Brdf &b, long long n, const View &i, c
 	if (const char *e = getenv("DJB_MERL_GRID_CAP_ENV")) gcap = atoll(e);
 #endif
 	if (n4 > 0)
-		hipLaunchKernelGGL((k_merl_fast_v4<WANT>), dim3(grid_for(n4, gcap)), dim3(BLOCK), 0, s, b, n4, i, o, out, out_pdf, g);
+		hipLaunchKernelGGL((k_merl_fast_v4<WANT>), dim3(djbk::grid_capped(n4, BLOCK, gcap)), dim3(BLOCK), 0, s, b, n4, i, o, out, out_pdf, g);
 	if (4 * n4 < n)   // strided / unaligned input, or the < 4-pair tail of a dense batch
-		hipLaunchKernelGGL((k_merl_fast<WANT>), dim3(grid_for(n - 4 * n4)), dim3(BLOCK), 0, s, b, 4 * n4, n, i, o, out, out_pdf, g);
+		hipLaunchKernelGGL((k_merl_fast<WANT>), dim3(djbk::grid_capped(n - 4 * n4, BLOCK, GRID_CAP)), dim3(BLOCK), 0, s, b, 4 * n4, n, i, o, out, out_pdf, g);
 	return hipGetLastError();
 }
 
@@ -343,7 +337,7 @@ hipError_t launch_merl_keys(hipStream_t s, long long n, const View &i, const Vie
 {
 	if (n <= 0) return hipSuccess;
 	const MerlGuard g = MERL_GUARD_DEFAULT;
-	hipLaunchKernelGGL(k_merl_keys, dim3(grid_for(n, 256LL * 32)), dim3(BLOCK), 0, s, n, i, o, keys, g);
+	hipLaunchKernelGGL(k_merl_keys, dim3(djbk::grid_capped(n, BLOCK, 256LL * 32)), dim3(BLOCK), 0, s, n, i, o, keys, g);
 	return hipGetLastError();
 }
 
@@ -352,7 +346,7 @@ hipError_t launch_merl_guard_stats(hipStream_t s, long long n, const View &i, co
 {
 	MerlGuard g = MERL_GUARD_DEFAULT;
 	if (guard6) { g.a_h = guard6[0]; g.b_h = guard6[1]; g.a_d = guard6[2]; g.b_d = guard6[3]; g.c_d = guard6[4]; g.a_p = guard6[5]; }
-	hipLaunchKernelGGL(k_merl_guard_stats, dim3(grid_for(n)), dim3(BLOCK), 0, s, n, i, o, g, max_bits, counters);
+	hipLaunchKernelGGL(k_merl_guard_stats, dim3(djbk::grid_capped(n, BLOCK, GRID_CAP)), dim3(BLOCK), 0, s, n, i, o, g, max_bits, counters);
 	return hipGetLastError();
 }
 
@@ -361,7 +355,7 @@ hipError_t launch_merl_guard_attack(hipStream_t s, long long n, const View &i, c
 {
 	MerlGuard g = MERL_GUARD_DEFAULT;
 	if (guard6) { g.a_h = guard6[0]; g.b_h = guard6[1]; g.a_d = guard6[2]; g.b_d = guard6[3]; g.c_d = guard6[4]; g.a_p = guard6[5]; }
-	hipLaunchKernelGGL(k_merl_guard_attack, dim3(grid_for(n)), dim3(BLOCK), 0, s, n, i, o, g, iters, seed, best, counters);
+	hipLaunchKernelGGL(k_merl_guard_attack, dim3(djbk::grid_capped(n, BLOCK, GRID_CAP)), dim3(BLOCK), 0, s, n, i, o, g, iters, seed, best, counters);
 	return hipGetLastError();
 }
 

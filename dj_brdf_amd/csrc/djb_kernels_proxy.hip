@@ -26,14 +26,6 @@ constexpr int proxy_block(int pkind, int tkind) { return pkind == KIND_TABULAR_A
 // floats of table staging: what k_sample stages for the kind (qf | qf2 grid + qf1) plus what k_eval stages (p22 + sigma | both grids)
 constexpr int proxy_tab_lds(int pkind) { return pkind == KIND_TABULAR ? 2048 + 3072 : pkind == KIND_TABULAR_ANISO ? 8192 + 1024 + 16384 + 768 : 0; }
 
-inline int grid_for(long long n, int bs)
-{
-	long long blocks = (n + bs - 1) / bs;
-	const long long cap = 256LL * 16 * 256 / bs;   // 16 workgroups of 256 per CU's worth, grid-stride beyond
-	if (blocks > cap) blocks = cap;
-	if (blocks < 1) blocks = 1;
-	return (int)blocks;
-}
 inline bool dense(const View &v) { return v.stride == 1; }
 
 // the queue of the pairs MERL's tier 1 declines: {k lo, k hi, i.xyz, o.xyz, pdf}; fewer than 64 wait when an iteration starts and
@@ -158,7 +150,7 @@ hipError_t launch_pair(hipStream_t s, const Brdf &pb, const Params &pp, const Br
 {
 	constexpr int BS = proxy_block(PKIND, TKIND);
 	const MerlGuard g = MERL_GUARD_DEFAULT;
-	dim3 grid(grid_for(n, BS)), block(BS);
+	dim3 grid(djbk::grid_capped(n, BS, 256LL * 16 * 256 / BS)), block(BS);   // 16 workgroups of 256 per CU's worth, grid-stride beyond
 	if (dense(o) && dense(out_w) && dense(out_i))
 		hipLaunchKernelGGL((k_evalp_is_proxy<PKIND, TKIND, true>), grid, block, 0, s, pb, pp, tb, tp, n, u1, u2, o, out_w, out_i, out_pdf, g, merl_exact ? 1 : 0);
 	else

@@ -13,14 +13,7 @@ constexpr int BLOCK = 256;
 #define DJB_UTIA_MIN_WAVES 4
 #endif
 
-inline int grid_for(long long n)
-{
-	long long blocks = (n + BLOCK - 1) / BLOCK;
-	const long long cap = 256LL * 64;   // 4 workgroups per CU resident, 16 rounds of them (2.58 ms per 1e8 pairs; 4096: 2.66, 1024: 2.94, one per tile: 2.75)
-	if (blocks > cap) blocks = cap;
-	if (blocks < 1) blocks = 1;
-	return (int)blocks;
-}
+constexpr long long GRID_CAP = 256LL * 64;   // 4 workgroups per CU resident, 16 rounds of them (2.58 ms per 1e8 pairs; 4096: 2.66, 1024: 2.94, one per tile: 2.75)
 inline bool dense(const View &v) { return v.stride == 1 || v.x == nullptr; }
 
 // utia::eval, two-tier.  Tier 1 (k_utia_v2) decides every pair it can with cheap arithmetic and lists the rest (the index of every pair
@@ -195,7 +188,7 @@ hipError_t launch_utia_tt(hipStream_t s, const Brdf &b, long long n, const View 
 {
 	hipError_t e = hipMemsetAsync(count, 0, 16, s);
 	if (e != hipSuccess) return e;
-	dim3 g(grid_for(n)), t(BLOCK);
+	dim3 g(djbk::grid_capped(n, BLOCK, GRID_CAP)), t(BLOCK);
 	const bool dn = dense(i) && dense(o) && dense(out);
 	if (contract) {
 		if (dn) hipLaunchKernelGGL((k_utia_v2<WANT, true, true>), g, t, 0, s, b, n, i, o, out, out_pdf, list, cap, count);
@@ -229,7 +222,7 @@ hipError_t launch_utia_twotier(hipStream_t s, const Brdf &b, long long n, const 
 hipError_t launch_fast_trig_selftest(hipStream_t s, long long n, int mode, uint32_t first, uint32_t seed, unsigned long long *counters4)
 {
 	if (n <= 0) return hipSuccess;
-	hipLaunchKernelGGL(k_fast_trig_selftest, dim3(grid_for(n)), dim3(BLOCK), 0, s, n, mode, first, seed, counters4);
+	hipLaunchKernelGGL(k_fast_trig_selftest, dim3(djbk::grid_capped(n, BLOCK, GRID_CAP)), dim3(BLOCK), 0, s, n, mode, first, seed, counters4);
 	return hipGetLastError();
 }
 

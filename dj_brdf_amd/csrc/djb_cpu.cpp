@@ -928,6 +928,97 @@ djb_status evalp_is_proxy(djb_ctx *ctx, const djb_brdf *target, const djb_brdf *
 	return DJB_OK;
 }
 
+// ------------------------------------------------------------------ MERL material sets: the two loops above per hit, the table and the proxy's
+// parameters selected by the hit's material id; an id outside [0, n_mat) is an inactive hit (+0 in every output, nothing read)
+djb_status merl_set_member(const djb_ctx *ctx, const djb_brdf *b, int index, const void **texels)
+{
+	if (!b) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: merl set member %d is a null brdf", index);
+	if (!is_cpu(b) || B(b)->ctx != (const CpuCtx *)ctx)
+		return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: merl set member %d belongs to another context", index);
+	if (B(b)->dev.kind != KIND_MERL || B(b)->dev.merl_sparse || !B(b)->dev.merl)
+		return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: merl set member %d is not a dense merl brdf (kind %d)", index, B(b)->dev.kind);
+	*texels = B(b)->dev.merl;
+	return DJB_OK;
+}
+djb_status merl_set_resolve_params(const djb_params *in, void *out_params)
+{
+	return params_for(in, KIND_GGX, (Params *)out_params);
+}
+template <int WANT>
+void merl_set_eval_loop(const MerlTexel *tex, int n_mat, long long k0, long long k1, const int32_t *material, const View &vi, const View &vo, const View &vout)
+{
+	Brdf tb; memset(&tb, 0, sizeof tb); tb.kind = KIND_MERL;
+	Params tp; memset(&tp, 0, sizeof tp);
+	for (long long k = k0; k < k1; ++k) {
+		v3 fr = mk(0, 0, 0); float unused_pdf = 0.0f;
+		const unsigned int m = (unsigned int)material[k];
+		if (m < (unsigned int)n_mat) {
+			tb.merl = tex + (size_t)m * (size_t)MERL_N;
+			eval_one<KIND_MERL, WANT>(tb, tp, load3(vi, k), load3(vo, k), fr, unused_pdf);
+		}
+		store3(vout, k, fr);
+	}
+}
+djb_status merl_set_eval(djb_ctx *ctx, const void *texels, int n_mat, int64_t n, const int32_t *material, const djb_vec3_view *i,
+                         const djb_vec3_view *o, int want_cos, const djb_vec3_view *out_fr)
+{
+	if (n < 0) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: negative batch size");
+	if (!material) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null material array");
+	if (!valid(i) || !valid(o)) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null vec3 view");
+	if (!valid(out_fr)) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null output vec3 view");
+	const View vi = view_of(i), vo = view_of(o), vout = view_of(out_fr);
+	const MerlTexel *tex = (const MerlTexel *)texels;
+	parallel_for(C(ctx), n, 4096, [&](long long k0, long long k1) {
+		if (want_cos) merl_set_eval_loop<2>(tex, n_mat, k0, k1, material, vi, vo, vout);
+		else merl_set_eval_loop<1>(tex, n_mat, k0, k1, material, vi, vo, vout);
+	});
+	return DJB_OK;
+}
+template <int PK>
+void merl_set_proxy_loop(const MerlTexel *tex, const Params *params, int n_mat, const Brdf &pb, long long k0, long long k1, const int32_t *material,
+                         const float *u1a, const float *u2a, const View &vo, const View &vw_out, const View &vi_out, float *out_pdf)
+{
+	const GlibcTabs gt = glibc_tabs_global();
+	Brdf tb; memset(&tb, 0, sizeof tb); tb.kind = KIND_MERL;
+	Params tp; memset(&tp, 0, sizeof tp);
+	for (long long k = k0; k < k1; ++k) {
+		v3 i_ = mk(0, 0, 0), w = mk(0, 0, 0); float pdf = 0.0f;
+		const unsigned int m = (unsigned int)material[k];
+		if (m < (unsigned int)n_mat) {
+			const Params &pp = params[m];
+			const v3 o = load3(vo, k);
+			v3 unused_w; float unused_pdf;
+			tb.merl = tex + (size_t)m * (size_t)MERL_N;
+			sample_one<PK, false>(pb, pp, u1a[k], u2a[k], o, gt, i_, unused_w, unused_pdf);
+			if (!(i_.z <= 0.0f)) {                                                      // the plugins' side check; a NaN i.z passes
+				v3 fr = mk(0, 0, 0), unused_fr = mk(0, 0, 0);
+				eval_one<PK, 4>(pb, pp, i_, o, unused_fr, pdf);
+				eval_one<KIND_MERL, 2>(tb, tp, i_, o, fr, unused_pdf);
+				w = divs(fr, pdf);
+			}
+		}
+		store3(vw_out, k, w); store3(vi_out, k, i_); out_pdf[k] = pdf;
+	}
+}
+djb_status merl_set_evalp_is_proxy(djb_ctx *ctx, const void *texels, const void *params_, int n_mat, const djb_brdf *proxy, int64_t n,
+                                   const int32_t *material, const float *u1, const float *u2, const djb_vec3_view *o,
+                                   const djb_vec3_view *out_w, const djb_vec3_view *out_i, float *out_pdf)
+{
+	if (n < 0) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: negative batch size");
+	if (!material) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null material array");
+	if (!u1 || !u2 || !valid(o) || !valid(out_w) || !valid(out_i) || !out_pdf) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null argument");
+	if (B(proxy)->ctx != C(ctx)) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: merl set and proxy belong to different contexts");
+	const Brdf &pb = B(proxy)->dev;
+	const View vo = view_of(o), vw = view_of(out_w), vi = view_of(out_i);
+	const MerlTexel *tex = (const MerlTexel *)texels;
+	const Params *params = (const Params *)params_;
+	parallel_for(C(ctx), n, 2048, [&](long long k0, long long k1) {
+		if (pb.kind == KIND_GGX) merl_set_proxy_loop<KIND_GGX>(tex, params, n_mat, pb, k0, k1, material, u1, u2, vo, vw, vi, out_pdf);
+		else merl_set_proxy_loop<KIND_BECKMANN>(tex, params, n_mat, pb, k0, k1, material, u1, u2, vo, vw, vi, out_pdf);
+	});
+	return DJB_OK;
+}
+
 djb_status eval_pp(djb_ctx *ctx, const djb_brdf *b_, int64_t n, const djb_vec3_view *i, const djb_vec3_view *o, const float *rec,
                    int mode, const float *base5, float scale, int lean_flags, int want, const djb_vec3_view *out_fr, float *out_pdf,
                    float *out_pp)

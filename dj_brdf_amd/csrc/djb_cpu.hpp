@@ -87,6 +87,17 @@ djb_status sample(djb_ctx *, const djb_brdf *, int64_t n, const float *u1, const
 djb_status evalp_is_proxy(djb_ctx *, const djb_brdf *target, const djb_brdf *proxy, int64_t n, const float *u1, const float *u2,
                           const djb_vec3_view *o, const djb_params *target_params, const djb_params *proxy_params,
                           const djb_vec3_view *out_w, const djb_vec3_view *out_i, float *out_pdf);
+// MERL material sets on the host (include/djb_hip.h: djb_merl_set).  texels = MerlTexel[n_mat][1458000], params = djbdev::Params[n_mat]
+// (both host memory, typed in djb_device.hpp); a hit whose id is outside [0, n_mat) gets +0 in every output.
+// merl_set_member: the converted table of a dense MERL object of `ctx` (what djb_merl_set_create copies), or the reason it is refused
+djb_status merl_set_member(const djb_ctx *ctx, const djb_brdf *b, int index, const void **texels);
+// one plain djb_params resolved as the host path's single-material calls resolve it (-> one djbdev::Params)
+djb_status merl_set_resolve_params(const djb_params *in, void *out_params);
+djb_status merl_set_eval(djb_ctx *, const void *texels, int n_mat, int64_t n, const int32_t *material, const djb_vec3_view *i,
+                         const djb_vec3_view *o, int want_cos, const djb_vec3_view *out_fr);
+djb_status merl_set_evalp_is_proxy(djb_ctx *, const void *texels, const void *params, int n_mat, const djb_brdf *proxy, int64_t n,
+                                   const int32_t *material, const float *u1, const float *u2, const djb_vec3_view *o,
+                                   const djb_vec3_view *out_w, const djb_vec3_view *out_i, float *out_pdf);
 djb_status eval_pp(djb_ctx *, const djb_brdf *, int64_t n, const djb_vec3_view *i, const djb_vec3_view *o, const float *rec,
                    int mode, const float *base5, float scale, int lean_flags, int want, const djb_vec3_view *out_fr, float *out_pdf,
                    float *out_pp);

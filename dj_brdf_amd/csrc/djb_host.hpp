@@ -122,9 +122,21 @@ struct djb_leanmap {
 	mutable std::atomic<int> host_ready{0};
 };
 
+// a MERL material set (djb_merl_set.hip): the converted tables of M dense MERL objects in one block, MerlTexel[M][1458000], and -- once
+// given -- the resolved proxy parameters Params[M]; both where the set's context computes (HBM, or host memory for a CPU context).
+// The tables are immutable; the parameters are replaced in stream order by djb_merl_set_set_proxy_params.
+struct djb_merl_set {
+	int device;                      // of the creating context, < 0: a CPU context's set (kept here: the handle may outlive its context)
+	djb_ctx *ctx;                    // the creating context: compared by the batch calls, used by set_proxy_params (a GPU set's stream)
+	int n_mat = 0;
+	bool has_params = false;
+	djbdev::MerlTexel *tex = nullptr;
+	Params *params = nullptr;
+};
+
 namespace djbh {
 
-djb_status fail(djb_status st, const char *fmt, ...);      // sets the thread's djb_last_error() message (djb_host.hip)
+djb_status fail(djb_status st, const char *fmt, ...);     // sets the thread's djb_last_error() message (djb_host.hip)
 
 #define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) \
 	return djbh::fail(DJB_ERR_HIP, "djb_error: HIP %s at %s:%d: %s", #expr, __FILE__, __LINE__, \

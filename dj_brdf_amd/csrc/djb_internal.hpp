@@ -57,6 +57,15 @@ hipError_t launch_evalp_is_proxy(hipStream_t s, const Brdf &target, const Params
                                  const float *u1, const float *u2, const View &o, const View &out_w, const View &out_i, float *out_pdf,
                                  bool merl_exact);
 
+// MERL material sets (djb_kernels_merl_set.hip): tex = MerlTexel[n_mat][1458000], material = n ids (outside [0, n_mat): an inactive hit,
+// every output +0); eval / evalp per hit, and launch_evalp_is_proxy per hit with params[material] as the proxy's parameters.  One launch each;
+// proxy: ggx or beckmann
+hipError_t launch_merl_set_eval(hipStream_t s, const djbdev::MerlTexel *tex, int n_mat, long long n, const int32_t *material, const View &i,
+                                const View &o, const View &out, bool want_cos, bool merl_exact);
+hipError_t launch_merl_set_evalp_is_proxy(hipStream_t s, const Brdf &proxy, const Params *params, const djbdev::MerlTexel *tex, int n_mat, long long n,
+                                          const int32_t *material, const float *u1, const float *u2, const View &o, const View &out_w,
+                                          const View &out_i, float *out_pdf, bool merl_exact);
+
 // per-pair params: rec = n x 5 floats; mode 0 = pdfparams records, mode 1 = LEAN texel moments composed with
 // base5 = params_to_lrep(base) (unscaled), scale = dmapscale, lean_flags = DJB_LEAN_* as dj_beckmannconductor does;
 // out_pp (optional, modes 1 and 2) receives the resolved pdfparams.  mode 2 = mode 1 with the record of pair k looked up in a

@@ -1,0 +1,243 @@
+// djb_kernels_merl_set.hip -- MERL material sets: a batch of hits that lands on M resident MERL tables, one launch.
+//
+// The bin of a MERL look-up depends on (i, o) alone (merl_index_fast / merl_index), never on the material: a mixed batch computes
+// the index once and gathers from table[material][index].  No kind dispatch, no divergence beyond the one the single-material kernels
+// have.  Two kernels, both with the two-tier shape of k_merl_fast (djb_kernels_merl.hip) and k_evalp_is_proxy<.., KIND_MERL, ..>
+// (djb_kernels_proxy.hip): tier 1 in place, the pairs it declines wait in a per-wave LDS queue -- the record carries the material id --
+// and one drain site finishes them with the exact index as dense waves.
+//   k_merl_set_fast<WANT>                      eval (WANT 1) / evalp (WANT 2) per hit
+//   k_evalp_is_proxy_merl_set<PKIND, DENSE>    the per-bounce step of dj_merl per hit: direction and pdf from a GGX or Beckmann lobe
+//                                              whose Params come per lane from the resident Params[M], f_r cos from table[material]
+// A hit whose id is outside [0, M) is inactive: every output is +0.0f, no table or parameter entry is read, nothing is queued.
+// The per-unit functions are the ones the single-material kernels call (mf_sample, the pdf arm of mf_eval_pdf, merl_index_fast,
+// merl_index, scale, divs), so an active hit has the bits of the single-material route.
+// Addressing: material * 1458000 + index fits an int32 up to DJB_MERL_SET_MAX = 1024 tables, the BYTE offset (x 12) does not beyond
+// table 245 -- merl_set_texel forms the element index in 64 bits.
+#include "djb_internal.hpp"
+
+using namespace djbdev;
+
+namespace {
+
+constexpr int BLOCK = 256;
+constexpr long long GRID_CAP = 256LL * 16;
+constexpr long long MERL_TEXELS = 90LL * 90 * 180;
+
+DJB_DEV v3 merl_set_texel(const MerlTexel *tex, unsigned int material, int idx)
+{
+	const MerlTexel t = tex[(unsigned long long)material * (unsigned long long)MERL_TEXELS + (unsigned long long)(unsigned int)idx];
+	return mk(t.x, t.y, t.z);
+}
+
+// ---- the per-wave queue of the pairs tier 1 declines, W words per record.  Fewer than 64 wait when an iteration starts and an
+// iteration adds at most 64 (one unit per lane).  One wave, in-order LDS: no barrier, no atomics.
+constexpr unsigned int QCAP = 128;
+template <int W>
+DJB_DEV void set_queue_push(unsigned int (&q)[W][QCAP], unsigned int &qn, unsigned int lane, bool amb, const unsigned int (&rec)[W])
+{
+	const unsigned long long mask = __ballot(amb);
+	if (!mask) return;
+	if (amb) {
+		const unsigned int j = qn + (unsigned int)__popcll(mask & ((1ull << lane) - 1ull));
+#pragma unroll
+		for (int w = 0; w < W; ++w) q[w][j] = rec[w];
+	}
+	qn += (unsigned int)__popcll(mask);
+}
+// while a full wave of records waits -- or, on the last trip, any -- hand `finish` one record per lane
+template <int W, class Finish>
+DJB_DEV void set_queue_drain(unsigned int (&q)[W][QCAP], unsigned int &qn, unsigned int lane, bool last, Finish finish)
+{
+	while (qn >= 64u || (last && qn)) {
+		const unsigned int cnt = qn < 64u ? qn : 64u;
+		qn -= cnt;
+		__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+		__builtin_amdgcn_wave_barrier();
+		if (lane < cnt) {
+			unsigned int rec[W];
+#pragma unroll
+			for (int w = 0; w < W; ++w) rec[w] = q[w][qn + lane];
+			finish(rec);
+		}
+		__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+		__builtin_amdgcn_wave_barrier();
+	}
+}
+// the part of a record both kernels share: {k lo, k hi, material, i.xyz, o.xyz}
+DJB_DEV void rec_pack(unsigned int *rec, long long k, unsigned int material, v3 i, v3 o)
+{
+	rec[0] = (unsigned int)((unsigned long long)k & 0xffffffffull); rec[1] = (unsigned int)((unsigned long long)k >> 32);
+	rec[2] = material;
+	rec[3] = __float_as_uint(i.x); rec[4] = __float_as_uint(i.y); rec[5] = __float_as_uint(i.z);
+	rec[6] = __float_as_uint(o.x); rec[7] = __float_as_uint(o.y); rec[8] = __float_as_uint(o.z);
+}
+DJB_DEV long long rec_k(const unsigned int *rec) { return (long long)(((unsigned long long)rec[1] << 32) | rec[0]); }
+DJB_DEV v3 rec_i(const unsigned int *rec) { return mk(__uint_as_float(rec[3]), __uint_as_float(rec[4]), __uint_as_float(rec[5])); }
+DJB_DEV v3 rec_o(const unsigned int *rec) { return mk(__uint_as_float(rec[6]), __uint_as_float(rec[7]), __uint_as_float(rec[8])); }
+
+// ---- eval / evalp.  DENSE: every view has stride 1 -- the 40 B/hit streams (id, i, o, out) are touched once: non-temporal, so that
+// they leave the L2 to the table gathers
+template <int WANT, bool DENSE>
+__global__ __launch_bounds__(BLOCK) void k_merl_set_fast(const MerlTexel *tex, int n_mat, long long n, const int32_t *mat, View vi, View vo, View vout,
+                                                         MerlGuard g, int merl_exact)
+{
+	__shared__ unsigned int s_q[BLOCK / 64][9][QCAP];
+	const unsigned int t = threadIdx.x, wave = t >> 6, lane = t & 63u;
+	unsigned int (&q)[9][QCAP] = s_q[wave];
+	unsigned int qn = 0;                                                           // wave-uniform
+	const long long stride = (long long)gridDim.x * BLOCK;
+	for (long long k0 = (long long)blockIdx.x * BLOCK; ; k0 += stride) {           // workgroup-uniform trip count; one extra trip flushes the queues
+		const bool last = k0 >= n;
+		bool amb = false;
+		unsigned int id = 0u;
+		v3 i = mk(0, 0, 1), o = mk(0, 0, 1);
+		const long long k = k0 + t;
+		const unsigned int rem = last ? 0u : n - k0 >= (long long)BLOCK ? (unsigned int)BLOCK : (unsigned int)(n - k0);
+		if (t < rem) {
+			id = (unsigned int)__builtin_nontemporal_load(mat + k);
+			i = DENSE ? load3_dense_nt(vi, k0, t) : load3(vi, k); o = DENSE ? load3_dense_nt(vo, k0, t) : load3(vo, k);
+			v3 fr = mk(0, 0, 0);                                                       // an inactive hit: +0, nothing read
+			if (id < (unsigned int)n_mat) {                                            // negative ids are >= 2^31 as unsigned
+				int idx = 0;
+				if (!merl_exact && merl_index_fast(i, o, g, idx)) {
+					const v3 e = merl_set_texel(tex, id, idx);
+					fr = (WANT & 2) ? scale(i.z, e) : e;                                   // brdf::evalp, dj_brdf.h:803-806
+				} else amb = true;                                                      // the exact index finishes this pair
+			}
+			if (!amb) { if (DENSE) store3_dense_nt(vout, k0, t, fr); else store3(vout, k, fr); }
+		}
+		// the record is built HERE, from values that live across the branches above, as merl_queue's callers pass k, i, o: packed inside
+		// the declining branch, the k word of a pair tier 1 declined came out as 0 in the generated code (the fp64-only path kept it)
+		unsigned int rec[9];
+		rec_pack(rec, k, id, i, o);
+		set_queue_push(q, qn, lane, amb, rec);
+		set_queue_drain(q, qn, lane, last, [&](const unsigned int *r) {
+			const v3 i = rec_i(r);
+			const v3 e = merl_set_texel(tex, r[2], merl_index(i, rec_o(r)));
+			store3(vout, rec_k(r), (WANT & 2) ? scale(i.z, e) : e);
+		});
+		if (last) break;
+	}
+}
+
+// ---- proxy importance sampling per hit: k_evalp_is_proxy<PKIND, KIND_MERL, DENSE> with Params and the table base per lane
+template <int PKIND, bool DENSE>
+__global__ __launch_bounds__(BLOCK) void k_evalp_is_proxy_merl_set(Brdf pb, const Params *params, const MerlTexel *tex, int n_mat, long long n,
+                                                                   const int32_t *mat, const float *u1a, const float *u2a, View vo, View vw_out,
+                                                                   View vi_out, float *out_pdf, MerlGuard g, int merl_exact)
+{
+	static_assert(PKIND == KIND_GGX || PKIND == KIND_BECKMANN, "the proxy of a MERL set is an analytic lobe");
+	constexpr bool GLIBCT = PKIND == KIND_BECKMANN;                                // logf / expf / powf of Beckmann's quantile functions
+	__shared__ double s_glibc[GLIBCT ? GLIBC_LDS_WORDS : 1];
+	__shared__ unsigned long long s_exp[GLIBCT ? 256 : 1];
+	__shared__ unsigned int s_q[BLOCK / 64][10][QCAP];
+	GlibcTabs gt = glibc_tabs_global();
+	if (GLIBCT) {
+		gt = glibc_tabs_to_lds(s_glibc, threadIdx.x, BLOCK);
+		const LdsTab e = glibc_exp_tab_to_lds(s_exp, threadIdx.x, BLOCK);
+		pb.exp_lds = e; gt.exp64 = e;
+		__syncthreads();
+	}
+	pb.atan_lds = 0u;
+
+	const unsigned int t = threadIdx.x, wave = t >> 6, lane = t & 63u;
+	unsigned int (&q)[10][QCAP] = s_q[wave];
+	unsigned int qn = 0;                                                           // wave-uniform
+	const long long stride = (long long)gridDim.x * BLOCK;
+	for (long long k0 = (long long)blockIdx.x * BLOCK; ; k0 += stride) {           // one extra trip flushes the queues
+		const bool last = k0 >= n;
+		bool amb = false;
+		unsigned int id = 0u;
+		v3 i_ = mk(0, 0, 0), o = mk(0, 0, 1); float pdf = 0.0f;                        // an inactive hit: +0 everywhere, nothing read
+		const long long k = k0 + t;
+		const unsigned int rem = last ? 0u : n - k0 >= (long long)BLOCK ? (unsigned int)BLOCK : (unsigned int)(n - k0);
+		if (t < rem) {
+			id = (unsigned int)__builtin_nontemporal_load(mat + k);
+			v3 w = mk(0, 0, 0);
+			if (id < (unsigned int)n_mat) {
+				const unsigned int toff = lane_byte_offset(t);
+				const float u1 = DENSE ? (*dense_off(u1a + k0, toff)) : u1a[k];
+				const float u2 = DENSE ? (*dense_off(u2a + k0, toff)) : u2a[k];
+				o = DENSE ? load3_dense_off(vo, k0, toff) : load3(vo, k);
+				const Params pp = params[id];
+				// ---- proxy: direction, then the pdf-only arm of mf_eval_pdf on (i, o)
+				i_ = mf_sample<PKIND>(pb, pp, u1, u2, o, gt);
+				if (!(i_.z <= 0.0f)) {                                                  // the side check; a NaN i.z is evaluated
+					v3 unused;
+					mf_eval_pdf<PKIND, 4>(pb, pp, i_, o, unused, pdf);
+					int idx = 0;
+					if (!merl_exact && merl_index_fast(i_, o, g, idx))
+						w = divs(scale(i_.z, merl_set_texel(tex, id, idx)), pdf);           // brdf::evalp = eval * i.z, dj_brdf.h:803-806
+					else amb = true;                                                    // the exact index finishes this pair (below)
+				}
+			}
+			const unsigned int soff = lane_byte_offset(t);                             // again: the stores sit in another block than the loads
+			if (DENSE) { store3_dense_off(vi_out, k0, soff, i_); (*dense_off(out_pdf + k0, soff)) = pdf; }
+			else { store3(vi_out, k, i_); out_pdf[k] = pdf; }
+			if (!amb) { if (DENSE) store3_dense_off(vw_out, k0, soff, w); else store3(vw_out, k, w); }
+		}
+		unsigned int rec[10];
+		rec_pack(rec, k, id, i_, o); rec[9] = __float_as_uint(pdf);
+		set_queue_push(q, qn, lane, amb, rec);
+		set_queue_drain(q, qn, lane, last, [&](const unsigned int *r) {
+			const v3 iq = rec_i(r);
+			const v3 e = merl_set_texel(tex, r[2], merl_index(iq, rec_o(r)));
+			store3(vw_out, rec_k(r), divs(scale(iq.z, e), __uint_as_float(r[9])));
+		});
+		if (last) break;
+	}
+}
+
+inline bool dense(const View &v) { return v.stride == 1; }
+
+template <int WANT>
+hipError_t launch_set_eval(hipStream_t s, const MerlTexel *tex, int n_mat, long long n, const int32_t *mat, const View &i, const View &o,
+                           const View &out, bool merl_exact)
+{
+	const MerlGuard g = MERL_GUARD_DEFAULT;
+	dim3 grid(djbk::grid_capped(n, BLOCK, GRID_CAP)), block(BLOCK);
+	if (dense(i) && dense(o) && dense(out))
+		hipLaunchKernelGGL((k_merl_set_fast<WANT, true>), grid, block, 0, s, tex, n_mat, n, mat, i, o, out, g, merl_exact ? 1 : 0);
+	else
+		hipLaunchKernelGGL((k_merl_set_fast<WANT, false>), grid, block, 0, s, tex, n_mat, n, mat, i, o, out, g, merl_exact ? 1 : 0);
+	return hipGetLastError();
+}
+
+template <int PKIND>
+hipError_t launch_set_proxy(hipStream_t s, const Brdf &pb, const Params *params, const MerlTexel *tex, int n_mat, long long n, const int32_t *mat,
+                            const float *u1, const float *u2, const View &o, const View &out_w, const View &out_i, float *out_pdf, bool merl_exact)
+{
+	const MerlGuard g = MERL_GUARD_DEFAULT;
+	dim3 grid(djbk::grid_capped(n, BLOCK, GRID_CAP)), block(BLOCK);
+	if (dense(o) && dense(out_w) && dense(out_i))
+		hipLaunchKernelGGL((k_evalp_is_proxy_merl_set<PKIND, true>), grid, block, 0, s, pb, params, tex, n_mat, n, mat, u1, u2, o, out_w, out_i, out_pdf, g, merl_exact ? 1 : 0);
+	else
+		hipLaunchKernelGGL((k_evalp_is_proxy_merl_set<PKIND, false>), grid, block, 0, s, pb, params, tex, n_mat, n, mat, u1, u2, o, out_w, out_i, out_pdf, g, merl_exact ? 1 : 0);
+	return hipGetLastError();
+}
+
+} // namespace
+
+namespace djbk {
+
+hipError_t launch_merl_set_eval(hipStream_t s, const djbdev::MerlTexel *tex, int n_mat, long long n, const int32_t *material, const View &i,
+                                const View &o, const View &out, bool want_cos, bool merl_exact)
+{
+	if (n <= 0) return hipSuccess;
+	return want_cos ? launch_set_eval<2>(s, tex, n_mat, n, material, i, o, out, merl_exact)
+	                : launch_set_eval<1>(s, tex, n_mat, n, material, i, o, out, merl_exact);
+}
+
+hipError_t launch_merl_set_evalp_is_proxy(hipStream_t s, const Brdf &proxy, const Params *params, const djbdev::MerlTexel *tex, int n_mat, long long n,
+                                          const int32_t *material, const float *u1, const float *u2, const View &o, const View &out_w,
+                                          const View &out_i, float *out_pdf, bool merl_exact)
+{
+	if (n <= 0) return hipSuccess;
+	switch (proxy.kind) {
+	case KIND_GGX: return launch_set_proxy<KIND_GGX>(s, proxy, params, tex, n_mat, n, material, u1, u2, o, out_w, out_i, out_pdf, merl_exact);
+	case KIND_BECKMANN: return launch_set_proxy<KIND_BECKMANN>(s, proxy, params, tex, n_mat, n, material, u1, u2, o, out_w, out_i, out_pdf, merl_exact);
+	}
+	return hipErrorInvalidValue;
+}
+
+} // namespace djbk

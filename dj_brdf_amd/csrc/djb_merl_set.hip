@@ -1,0 +1,207 @@
+// djb_merl_set.hip -- the C ABI of MERL material sets (include/djb_hip.h: djb_merl_set): M resident MERL tables in one block and one
+// resolved proxy parameter set per material, evaluated / importance-sampled per hit by material id.  Kernels: djb_kernels_merl_set.hip;
+// host loops (CPU contexts): djb_cpu.cpp.  A set has no host twin: on a GPU context a host batch of any size is staged to the device.
+#include "djb_host.hpp"
+
+using namespace djbh;
+using djbdev::MerlTexel;
+
+namespace {
+
+constexpr size_t TABLE_BYTES = sizeof(MerlTexel) * (size_t)MERL_N;
+
+// the set belongs to the call's context, as a djb_brdf does
+djb_status set_check(const djb_ctx *ctx, const djb_merl_set *s)
+{
+	if (!s) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null merl set");
+	if (!ctx) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null ctx");
+	if (is_cpu(ctx) != (s->device < 0))
+		return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: merl set and ctx belong to different back ends (CPU / GPU)");
+	if (s->ctx != ctx) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: the merl set belongs to another context");
+	return DJB_OK;
+}
+
+// n_mat plain parameter sets -> Params as the single-material calls of the set's back end resolve them
+djb_status resolve_all(bool cpu, int n_mat, const djb_params *in, std::vector<Params> *out)
+{
+	if (!in) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null proxy_params");
+	out->resize((size_t)n_mat);
+	for (int m = 0; m < n_mat; ++m) {
+		if (in[m].kind & DJB_PARAMS_RESOLVED_FOLLOWS)
+			return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: proxy_params[%d] carries DJB_PARAMS_RESOLVED_FOLLOWS: a merl set takes plain djb_params", m);
+		memset(&(*out)[m], 0, sizeof(Params));
+		djb_status st = cpu ? djbcpu::merl_set_resolve_params(&in[m], &(*out)[m]) : device_params(&in[m], &(*out)[m], DJB_KIND_GGX);
+		if (st != DJB_OK) return st;
+	}
+	return DJB_OK;
+}
+
+// replaces the resident parameters; a GPU set: one copy on the context's stream, finished when this returns
+djb_status install_params(djb_merl_set *s, const std::vector<Params> &p)
+{
+	if (s->device < 0) { memcpy(s->params, p.data(), sizeof(Params) * p.size()); s->has_params = true; return DJB_OK; }
+	HIP_TRY(hipSetDevice(s->device));
+	std::lock_guard<std::recursive_mutex> call_lock(s->ctx->call_mu);
+	HIP_TRY(hipMemcpyAsync(s->params, p.data(), sizeof(Params) * p.size(), hipMemcpyHostToDevice, s->ctx->stream));
+	HIP_TRY(hipStreamSynchronize(s->ctx->stream));        // `p` is pageable host memory of the caller's frame
+	s->has_params = true;
+	return DJB_OK;
+}
+
+// the n material ids of a batch where the kernels read them
+djb_status stage_material(Staged &sg, const int32_t *material, const int32_t **out)
+{
+	if (!material) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null material array");
+	if (sg.mem == DJB_MEM_DEVICE) { *out = material; return DJB_OK; }
+	int32_t *d = nullptr;
+	djb_status st = sg.alloc(sizeof(int32_t) * (size_t)sg.n, (void **)&d);
+	if (st != DJB_OK) return st;
+	if (sg.n && (st = sg.copy(d, material, sizeof(int32_t) * (size_t)sg.n, hipMemcpyHostToDevice)) != DJB_OK) return st;
+	*out = d;
+	return DJB_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+djb_status djb_merl_set_create(djb_ctx *ctx, int n_materials, const djb_brdf *const *merls, const djb_params *proxy_params, djb_merl_set **out)
+try {
+	if (!ctx || !out || !merls) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null argument");
+	*out = nullptr;
+	if (n_materials < 1 || n_materials > DJB_MERL_SET_MAX)
+		return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: a merl set holds 1 .. %d materials (got %d)", DJB_MERL_SET_MAX, n_materials);
+	const bool cpu = is_cpu(ctx);
+	djb_status st;
+	std::vector<const void *> src((size_t)n_materials);
+	for (int m = 0; m < n_materials; ++m) {
+		const djb_brdf *b = merls[m];
+		if (cpu) { if ((st = djbcpu::merl_set_member(ctx, b, m, &src[m])) != DJB_OK) return st; continue; }
+		if (!b) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: merl set member %d is a null brdf", m);
+		if (is_cpu(b) || b->ctx != ctx || b->device != ctx->device)
+			return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: merl set member %d belongs to another context", m);
+		if (b->dev.kind != DJB_KIND_MERL || b->dev.merl_sparse || !b->dev.merl)
+			return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: merl set member %d is not a dense merl brdf (kind %d)", m, b->dev.kind);
+		src[m] = b->dev.merl;
+	}
+	std::vector<Params> resolved;
+	if (proxy_params && (st = resolve_all(cpu, n_materials, proxy_params, &resolved)) != DJB_OK) return st;
+
+	djb_merl_set *s = new djb_merl_set();
+	s->device = cpu ? -1 : ctx->device;
+	s->ctx = ctx;
+	s->n_mat = n_materials;
+	const size_t tex_bytes = TABLE_BYTES * (size_t)n_materials, par_bytes = sizeof(Params) * (size_t)n_materials;
+	if (cpu) {
+		s->tex = (MerlTexel *)malloc(tex_bytes);
+		s->params = (Params *)calloc((size_t)n_materials, sizeof(Params));
+		if (!s->tex || !s->params) { djb_merl_set_destroy(s); return fail(DJB_ERR_OUT_OF_MEMORY, "djb_error: out of host memory (merl set of %d tables)", n_materials); }
+		for (int m = 0; m < n_materials; ++m) memcpy(s->tex + (size_t)m * (size_t)MERL_N, src[m], TABLE_BYTES);
+	} else {
+		if ((st = check_call(ctx, nullptr, 0, DJB_MEM_DEVICE)) != DJB_OK) { delete s; return st; }
+		std::lock_guard<std::recursive_mutex> call_lock(ctx->call_mu);
+		hipError_t e = hipMalloc((void **)&s->tex, tex_bytes);
+		if (e == hipSuccess) e = hipMalloc((void **)&s->params, par_bytes);
+		if (e == hipSuccess) e = hipMemsetAsync(s->params, 0, par_bytes, ctx->stream);
+		for (int m = 0; m < n_materials && e == hipSuccess; ++m)            // device to device, on the context's stream
+			e = hipMemcpyAsync(s->tex + (size_t)m * (size_t)MERL_N, src[m], TABLE_BYTES, hipMemcpyDeviceToDevice, ctx->stream);
+		if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);          // the sources may be destroyed as soon as this returns
+		if (e != hipSuccess) {
+			(void)hipGetLastError();
+			(void)hipStreamSynchronize(ctx->stream);
+			djb_merl_set_destroy(s);
+			return fail(DJB_ERR_HIP, "djb_error: HIP allocation / copy of a merl set of %d tables (%zu bytes): %s", n_materials, tex_bytes, hipGetErrorString(e));
+		}
+	}
+	if (proxy_params && (st = install_params(s, resolved)) != DJB_OK) { djb_merl_set_destroy(s); return st; }
+	*out = s;
+	return DJB_OK;
+}
+DJB_ABI_CATCH
+
+djb_status djb_merl_set_set_proxy_params(djb_merl_set *s, const djb_params *proxy_params)
+try {
+	if (!s) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null merl set");
+	std::vector<Params> resolved;
+	djb_status st = resolve_all(s->device < 0, s->n_mat, proxy_params, &resolved);
+	if (st != DJB_OK) return st;
+	return install_params(s, resolved);
+}
+DJB_ABI_CATCH
+
+djb_status djb_merl_set_info(const djb_merl_set *s, int *n_materials, int *has_proxy_params)
+try {
+	if (!s) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null merl set");
+	if (n_materials) *n_materials = s->n_mat;
+	if (has_proxy_params) *has_proxy_params = s->has_params ? 1 : 0;
+	return DJB_OK;
+}
+DJB_ABI_CATCH
+
+djb_status djb_merl_set_destroy(djb_merl_set *s)
+try {
+	if (!s) return DJB_OK;
+	if (s->device < 0) { free(s->tex); free(s->params); }
+	else {
+		(void)hipSetDevice(s->device);
+		if (s->tex) (void)hipFree(s->tex);
+		if (s->params) (void)hipFree(s->params);
+	}
+	delete s;
+	return DJB_OK;
+}
+DJB_ABI_CATCH
+
+djb_status djb_merl_set_eval_batch(djb_ctx *ctx, const djb_merl_set *s, int64_t n, const int32_t *material, const djb_vec3_view *i,
+                                   const djb_vec3_view *o, int want_cos, const djb_vec3_view *out_fr, int mem)
+try {
+	djb_status st = set_check(ctx, s);
+	if (st != DJB_OK) return st;
+	if (is_cpu(ctx)) return djbcpu::merl_set_eval(ctx, s->tex, s->n_mat, n, material, i, o, want_cos, out_fr);
+	if ((st = check_call(ctx, nullptr, n, mem)) != DJB_OK) return st;
+	std::lock_guard<std::recursive_mutex> call_lock(ctx->call_mu);
+	Staged sg(ctx, n, mem);
+	const int32_t *dmat; View vi, vo, vout;
+	if ((st = stage_material(sg, material, &dmat)) != DJB_OK) return st;
+	if ((st = sg.in_vec(i, &vi)) != DJB_OK) return st;
+	if ((st = sg.in_vec(o, &vo)) != DJB_OK) return st;
+	if ((st = sg.out_vec(out_fr, &vout)) != DJB_OK) return st;
+	HIP_TRY(djbk::launch_merl_set_eval(ctx->stream, s->tex, s->n_mat, n, dmat, vi, vo, vout, want_cos != 0, ctx->merl_exact_only != 0));
+	return sg.finish();
+}
+DJB_ABI_CATCH
+
+djb_status djb_merl_set_evalp_is_proxy_batch(djb_ctx *ctx, const djb_merl_set *s, const djb_brdf *proxy, int64_t n, const int32_t *material,
+                                             const float *u1, const float *u2, const djb_vec3_view *o, const djb_vec3_view *out_weight,
+                                             const djb_vec3_view *out_i, float *out_pdf, int mem)
+try {
+	djb_status st = set_check(ctx, s);
+	if (st != DJB_OK) return st;
+	if (!proxy) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null brdf (proxy)");
+	if ((st = cpu_pair_check(ctx, proxy)) != DJB_OK) return st;
+	const bool cpu = is_cpu(ctx);
+	if (!cpu && (proxy->ctx != ctx || proxy->device != ctx->device))
+		return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: merl set and proxy belong to different contexts");
+	const int pkind = cpu ? djbcpu::kind(proxy) : proxy->dev.kind;
+	if (pkind != DJB_KIND_GGX && pkind != DJB_KIND_BECKMANN)
+		return fail(DJB_ERR_NOT_IMPLEMENTED, "djb_error: evalp_is_proxy on a merl set takes a ggx or beckmann proxy (proxy kind %d)", pkind);
+	if (!s->has_params) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: the merl set has no proxy parameters (djb_merl_set_set_proxy_params)");
+	if (cpu) return djbcpu::merl_set_evalp_is_proxy(ctx, s->tex, s->params, s->n_mat, proxy, n, material, u1, u2, o, out_weight, out_i, out_pdf);
+	if ((st = check_call(ctx, proxy, n, mem)) != DJB_OK) return st;
+	std::lock_guard<std::recursive_mutex> call_lock(ctx->call_mu);
+	Staged sg(ctx, n, mem);
+	const int32_t *dmat; View vo, vi, vw; const float *d1, *d2; float *dpdf = nullptr;
+	if ((st = stage_material(sg, material, &dmat)) != DJB_OK) return st;
+	if ((st = sg.in_f(u1, &d1)) != DJB_OK) return st;
+	if ((st = sg.in_f(u2, &d2)) != DJB_OK) return st;
+	if ((st = sg.in_vec(o, &vo)) != DJB_OK) return st;
+	if ((st = sg.out_vec(out_i, &vi)) != DJB_OK) return st;
+	if ((st = sg.out_vec(out_weight, &vw)) != DJB_OK) return st;
+	if ((st = sg.out_arr(out_pdf, &dpdf)) != DJB_OK) return st;
+	HIP_TRY(djbk::launch_merl_set_evalp_is_proxy(ctx->stream, proxy->dev, s->params, s->tex, s->n_mat, n, dmat, d1, d2, vo, vw, vi, dpdf,
+	                                             ctx->merl_exact_only != 0));
+	return sg.finish();
+}
+DJB_ABI_CATCH
+
+} // extern "C"

@@ -1082,6 +1082,123 @@ class merl(brdf):
         return _get_samples(self)
 
 
+class merl_set:
+    """M MERL materials resident in ONE block on their context's device, with one fitted proxy parameter set per material: hits that
+    land on many measured materials are evaluated / importance-sampled in one call, each hit naming its material by id
+    (djb_merl_set, include/djb_hip.h).  An extension: the reference's objects are one material each.
+
+    ``material``: int32 ids, one per hit; an id outside [0, M) marks an inactive hit (a dead path), whose outputs are all +0.
+    An active hit gets the bits of the single-material call on its material.  Arrays: numpy (host) or torch CUDA (device), in the
+    layouts the other operators take; the ids travel in the memory space of the directions."""
+
+    def __init__(self, brdfs, proxy_params=None, ctx: Optional[Context] = None):
+        brdfs = list(brdfs)
+        self.ctx = ctx or (brdfs[0].ctx if brdfs else default_context())
+        self._h = C.c_void_p()
+        self._members = brdfs                      # kept for fit_proxies(); the set itself holds copies of their tables
+        ptrs = (C.c_void_p * max(len(brdfs), 1))(*[getattr(b._h, "value", None) for b in brdfs])
+        _lib.check(_lib.load().djb_merl_set_create(self.ctx._h, C.c_int(len(brdfs)), ptrs, self._params_array(proxy_params, len(brdfs)),
+                                                  C.byref(self._h)))
+        self.n_materials = len(brdfs)
+
+    @classmethod
+    def from_tables(cls, tables, proxy_params=None, ctx: Optional[Context] = None):
+        """the set of ``merl.from_table(t)`` for every MERL payload in ``tables`` (3 * 1458000 doubles each)"""
+        ctx = ctx or default_context()
+        return cls([merl.from_table(t, ctx=ctx) for t in tables], proxy_params, ctx)
+
+    @staticmethod
+    def _params_array(proxy_params, n):
+        if proxy_params is None:
+            return None
+        proxy_params = list(proxy_params)
+        if len(proxy_params) != n or not all(isinstance(p, microfacet.params) for p in proxy_params):
+            raise exc(1, f"djb_error: proxy_params must be {n} microfacet.params (one per material)")
+        return (_lib.Params * max(n, 1))(*[p._p for p in proxy_params])
+
+    @property
+    def has_proxy_params(self) -> bool:
+        n, has = C.c_int(), C.c_int()
+        _lib.check(_lib.load().djb_merl_set_info(self._h, C.byref(n), C.byref(has)))
+        return bool(has.value)
+
+    def set_proxy_params(self, proxy_params):
+        """one ``microfacet.params`` per material; replaces the resident set in stream order"""
+        _lib.check(_lib.load().djb_merl_set_set_proxy_params(self._h, self._params_array(proxy_params, self.n_materials)))
+
+    def fit_proxies(self, res: int = 90, shadow: bool = False):
+        """``fit_ggx_parameters(tabular(merl, res, shadow))`` of every member (mitsuba/dj_merl.cpp:32 for the whole set, one batched fit)
+        installed as ``params.isotropic(alpha_ggx)`` per material.  Returns (alpha_beckmann[M], alpha_ggx[M])."""
+        if any(not b._h for b in self._members):
+            raise exc(1, "djb_error: fit_proxies needs the member objects the set was built from (one was closed)")
+        uniq = list({id(b): b for b in self._members}.values())
+        ab_u, ag_u = fit_brdf_batch(uniq, res, shadow, ctx=self.ctx)
+        at = {id(b): k for k, b in enumerate(uniq)}
+        sel = [at[id(b)] for b in self._members]
+        ab, ag = ab_u[sel], ag_u[sel]
+        self.set_proxy_params([microfacet.params.isotropic(float(a)) for a in ag])
+        return ab, ag
+
+    @staticmethod
+    def _ids(material, like: _Vec):
+        if like.is_torch:
+            if not _is_dev(material):
+                material = torch.as_tensor(np.asarray(material.cpu() if hasattr(material, "cpu") else material).astype(np.int32), device=like.device)
+            material = material.to(torch.int32).contiguous()
+            n, ptr = material.numel(), material.data_ptr()
+        else:
+            material = np.ascontiguousarray(material.cpu().numpy() if hasattr(material, "cpu") else material, dtype=np.int32)
+            n, ptr = material.size, material.ctypes.data
+        if n != like.n or material.ndim != 1:
+            raise exc(1, f"djb_error: material must hold one int32 id per hit ({like.n}), got shape {tuple(material.shape)}")
+        return material, ptr
+
+    def _eval(self, material, i, o, want_cos):
+        vi, vo = _Vec(i), _Vec(o)
+        if vi.n != vo.n or vi.mem != vo.mem:
+            raise exc(1, "djb_error: i and o must have the same length and memory space")
+        keep, mp = self._ids(material, vi)
+        out = vi.like()
+        _lib.check(_lib.load().djb_merl_set_eval_batch(self.ctx._h, self._h, C.c_int64(vi.n), C.c_void_p(mp), C.byref(vi.view), C.byref(vo.view),
+                                                      C.c_int(want_cos), C.byref(out.view), C.c_int(vi.mem)))
+        del keep
+        return out.keep
+
+    def eval(self, material, i, o):
+        """f_r of material[k] at (i_k, o_k)"""
+        return self._eval(material, i, o, 0)
+
+    def evalp(self, material, i, o):
+        """f_r * cos(theta_i) of material[k] at (i_k, o_k)"""
+        return self._eval(material, i, o, 1)
+
+    def evalp_is_proxy(self, proxy, material, u1, u2, o):
+        """(weight, i, pdf) per hit as ``brdf.evalp_is_proxy``: direction and pdf from ``proxy`` (a ggx or beckmann object) with the
+        hit's material's proxy parameters, f_r cos from the hit's material.  One kernel launch on the GPU."""
+        vo = _Vec(o)
+        keep, mp = self._ids(material, vo)
+        k1, p1 = _scalar_in(u1, vo)
+        k2, p2 = _scalar_in(u2, vo)
+        w, i = vo.like(), vo.like()
+        pdf, pdf_ptr = vo.scalars()
+        _lib.check(_lib.load().djb_merl_set_evalp_is_proxy_batch(self.ctx._h, self._h, proxy._h, C.c_int64(vo.n), C.c_void_p(mp), C.c_void_p(p1),
+                                                                C.c_void_p(p2), C.byref(vo.view), C.byref(w.view), C.byref(i.view),
+                                                                C.c_void_p(pdf_ptr), C.c_int(vo.mem)))
+        del keep, k1, k2
+        return w.keep, i.keep, pdf
+
+    def close(self):
+        if self._h:
+            _lib.load().djb_merl_set_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class utia(brdf):
     """djb::utia(filename) (dj_brdf.h:136-146, 1039-1059)."""
 

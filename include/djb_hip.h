@@ -65,7 +65,11 @@ extern "C" {
  *        Behaviour under 235, no layout changed: a djb_params_cached is accepted for every set djb_params_resolve can return (rho == +-1 was
  *        refused); what makes it one is that `r` repeats the values of `p` (see djb_params_cached), no longer a range test.
  *        Additive under 235, no existing entry changed: djb_evalp_is_proxy_batch (proxy importance sampling: direction and pdf from a
- *        fitted lobe, f_r cos from a measured or data-driven BRDF, in one call). */
+ *        fitted lobe, f_r cos from a measured or data-driven BRDF, in one call).
+ *        Additive under 235, no existing entry changed: MERL material sets -- djb_merl_set, DJB_MERL_SET_MAX, djb_merl_set_create,
+ *        djb_merl_set_set_proxy_params, djb_merl_set_info, djb_merl_set_destroy, djb_merl_set_eval_batch,
+ *        djb_merl_set_evalp_is_proxy_batch (eval / evalp and proxy importance sampling of hits on M resident MERL tables by per-hit
+ *        material id, one call). */
 #define DJB_HIP_VERSION 235
 #define DJB_HIP_VERSION_MAJOR(v) ((v) / 100)
 
@@ -103,6 +107,7 @@ enum { DJB_MEM_DEVICE = 0, DJB_MEM_HOST = 1 };
 typedef struct djb_ctx djb_ctx;     /* one GPU + one HIP stream */
 typedef struct djb_brdf djb_brdf;   /* an immutable BRDF object resident in HBM (djb::brdf subclass) */
 typedef struct djb_leanmap djb_leanmap;   /* an immutable LEAN map (mip pyramid of slope moments) resident in HBM */
+typedef struct djb_merl_set djb_merl_set; /* M MERL tables in one resident block + one proxy parameter set per material */
 
 typedef struct { float *x, *y, *z; int64_t stride; } djb_vec3_view;
 
@@ -489,6 +494,52 @@ djb_status djb_sample_leanmap_batch(djb_ctx *, const djb_brdf *, const djb_leanm
                                     const djb_vec3_view *o, const float *uv, const float *lod, const djb_params *base, float scale,
                                     int lean_flags, const djb_vec3_view *out_w, const djb_vec3_view *out_i, float *out_pdf,
                                     float *out_pdfparams, int mem);
+
+/* ---- MERL material sets: the hit batch of a wavefront renderer lands on many measured materials; a set answers it in one call, each
+ * hit naming its material by id.  An extension with no counterpart in the reference (its objects are one material each).  For MERL
+ * the bin index depends on (i, o) alone, never on the material: the index is computed once per hit and the value gathered from
+ * table[material][index].
+ *
+ * Creation.  djb_merl_set_create copies the converted texel tables of n_materials dense merl objects into ONE contiguous block,
+ * MerlTexel[M][1458000] (12 bytes per texel, 17.5 MB per material, allocated once; no call allocates afterwards on device memory).
+ * Every source object must belong to the call's context (else DJB_ERR_INVALID_ARGUMENT, as for a non-merl member or a sparse per-slot
+ * object of the file pipeline); the same handle may appear more than once.  On a GPU context the copies are device-to-device on the
+ * context's stream, and the sources may be destroyed as soon as create returns.  The set belongs to its context as a djb_brdf does
+ * and may be destroyed after it.  1 <= M <= DJB_MERL_SET_MAX: with that cap material * 1458000 + index fits an int32 (the byte
+ * offset does not fit 32 bits beyond material 245; the gathers address in 64 bits).
+ *
+ * Proxy parameters.  One plain djb_params per material, of any kind djb_params_resolve accepts (a set DJB_PARAMS_RESOLVED_FOLLOWS flag
+ * is DJB_ERR_INVALID_ARGUMENT); proxy_params == NULL at creation: none yet.  They are resolved once on the host, exactly as the
+ * single-material call resolves them, and kept resident as Params[M].  djb_merl_set_set_proxy_params replaces them in stream order on
+ * the context's stream (the set's context must still exist) and returns when the copy has finished.
+ *
+ * material: n int32 values in the memory space `mem` names.  A hit with 0 <= material[k] < M gets, bit for bit, what the
+ * single-material call returns for unit k's inputs:
+ *   djb_merl_set_eval_batch             djb_eval_batch (djb_evalp_batch when want_cos != 0) on material m
+ *   djb_merl_set_evalp_is_proxy_batch   djb_evalp_is_proxy_batch(target = material m, proxy, ..., proxy_params = params[m]), including the
+ *                                       side check (i stored, weight 0, pdf 0 where i.z <= 0), the unguarded o and the IEEE division by
+ *                                       a zero pdf
+ * A hit whose id is outside [0, M) is INACTIVE: every output of that hit is +0.0f (fr; or weight, i and pdf) and no table or parameter
+ * entry is read for it.  Inactive ids are how a renderer marks dead paths: a defined input, not an error.
+ *
+ * `proxy` must be a ggx or beckmann object of the call's context (any other kind: DJB_ERR_NOT_IMPLEMENTED); sampling on a set without
+ * proxy parameters is DJB_ERR_INVALID_ARGUMENT.  DJB_OPT_MERL_EXACT_ONLY sends every active hit through the exact index, as for the
+ * single-material calls; DJB_OPT_CONTRACT_1E5 changes nothing.  CPU contexts serve both calls with the host instantiation of the same
+ * per-unit code.  On a GPU context a device-memory batch is ONE kernel launch, with no allocation and no host read-back (it can be
+ * captured into a hipGraph); a host-memory batch of any size is staged through HBM (a set has no host twin). */
+#define DJB_MERL_SET_MAX 1024
+djb_status djb_merl_set_create(djb_ctx *, int n_materials, const djb_brdf *const *merls,
+                               const djb_params *proxy_params /* n_materials, or NULL */, djb_merl_set **out);
+djb_status djb_merl_set_set_proxy_params(djb_merl_set *, const djb_params *proxy_params /* n_materials */);
+djb_status djb_merl_set_info(const djb_merl_set *, int *n_materials, int *has_proxy_params);
+djb_status djb_merl_set_destroy(djb_merl_set *);
+djb_status djb_merl_set_eval_batch(djb_ctx *, const djb_merl_set *, int64_t n, const int32_t *material,
+                                   const djb_vec3_view *i, const djb_vec3_view *o, int want_cos,
+                                   const djb_vec3_view *out_fr, int mem);
+djb_status djb_merl_set_evalp_is_proxy_batch(djb_ctx *, const djb_merl_set *, const djb_brdf *proxy, int64_t n,
+                                             const int32_t *material, const float *u1, const float *u2,
+                                             const djb_vec3_view *o, const djb_vec3_view *out_weight,
+                                             const djb_vec3_view *out_i, float *out_pdf, int mem);
 
 /* beckmann::lrep algebra on {E1..E5} (host scalars; dj_brdf.h:330-356, 1959-2051).  b may be NULL
  * (= the default lrep(0,0,1,1,0)); x (and y) are the scalar arguments of mul / shear / scale.

@@ -1242,6 +1242,59 @@ private:
 	int m_elev, m_azim;
 };
 
+/* M MERL materials resident in one block on their context's device, with one fitted proxy parameter set per material
+ * (include/djb_hip.h, djb_merl_set): the hits of a wavefront renderer land on many measured materials; each hit names its material
+ * by id and the whole batch is one call.  An extension with no counterpart in the reference, whose objects are one material each.
+ * An id outside [0, size()) marks an inactive hit: every output of it is +0.  An active hit gets the bits of the single-material
+ * call on its material (merl::eval / evalp, brdf::evalp_is_proxy with the material's parameters). */
+class merl_set {
+public:
+	/* the tables of n merl objects are copied: the objects may be destroyed afterwards.  proxy_params: n sets, or NULL (none yet) */
+	merl_set(size_t n, const merl *const *materials, const microfacet::params *proxy_params = NULL, hip::context *c = NULL)
+		: m_ctx(c), m_h(NULL)
+	{
+		std::vector<const djb_brdf *> h(n);
+		for (size_t k = 0; k < n; ++k) h[k] = materials[k] ? materials[k]->handle() : NULL;
+		std::vector<djb_params> p = plain(n, proxy_params);
+		hip::check(djb_merl_set_create(ctx(), (int)n, h.data(), proxy_params ? p.data() : NULL, &m_h));
+	}
+	~merl_set() { djb_merl_set_destroy(m_h); }
+	merl_set(merl_set &&o) noexcept : m_ctx(o.m_ctx), m_h(o.m_h) { o.m_h = NULL; }
+	merl_set &operator=(merl_set &&o) noexcept { if (this != &o) { djb_merl_set_destroy(m_h); m_ctx = o.m_ctx; m_h = o.m_h; o.m_h = NULL; } return *this; }
+	merl_set(const merl_set &) = delete;
+	merl_set &operator=(const merl_set &) = delete;
+	const djb_merl_set *get() const { return m_h; }
+	int size() const { int v; hip::check(djb_merl_set_info(m_h, &v, NULL)); return v; }
+	bool has_proxy_params() const { int v; hip::check(djb_merl_set_info(m_h, NULL, &v)); return v != 0; }
+	/* one set per material, e.g. tabular::fit_ggx_parameters(tabular(merl, 90, false)) of each (mitsuba/dj_merl.cpp:32) */
+	void set_proxy_params(const microfacet::params *proxy_params)
+	{ std::vector<djb_params> p = plain((size_t)size(), proxy_params); hip::check(djb_merl_set_set_proxy_params(m_h, p.data())); }
+	// ---- host arrays
+	void eval(size_t n, const int32_t *material, const vec3 *i, const vec3 *o, vec3 *out) const { eval_views(n, material, hip::view(i), hip::view(o), hip::view(out), 0, DJB_MEM_HOST); }
+	void evalp(size_t n, const int32_t *material, const vec3 *i, const vec3 *o, vec3 *out) const { eval_views(n, material, hip::view(i), hip::view(o), hip::view(out), 1, DJB_MEM_HOST); }
+	void evalp_is_proxy(const microfacet &proxy, size_t n, const int32_t *material, const float_t *u1, const float_t *u2, const vec3 *o,
+	                    vec3 *out_weight, vec3 *out_i, float_t *out_pdf) const
+	{ evalp_is_proxy_views(proxy, (int64_t)n, material, u1, u2, hip::view(o), hip::view(out_weight), hip::view(out_i), out_pdf, DJB_MEM_HOST); }
+	// ---- views (SoA or strided), in host memory or in HBM (mem = DJB_MEM_DEVICE: asynchronous on the context's stream, one launch)
+	void eval_views(int64_t n, const int32_t *material, const djb_vec3_view &i, const djb_vec3_view &o, const djb_vec3_view &out,
+	                int want_cos, int mem) const
+	{ hip::check(djb_merl_set_eval_batch(ctx(), m_h, n, material, &i, &o, want_cos, &out, mem)); }
+	void evalp_is_proxy_views(const microfacet &proxy, int64_t n, const int32_t *material, const float_t *u1, const float_t *u2,
+	                          const djb_vec3_view &o, const djb_vec3_view &out_weight, const djb_vec3_view &out_i, float_t *out_pdf, int mem) const
+	{ hip::check(djb_merl_set_evalp_is_proxy_batch(ctx(), m_h, proxy.handle(), n, material, u1, u2, &o, &out_weight, &out_i, out_pdf, mem)); }
+private:
+	// the facade's params carry their resolved form; a set takes the plain parameter sets and resolves them itself
+	static std::vector<djb_params> plain(size_t n, const microfacet::params *p)
+	{
+		std::vector<djb_params> v(p ? n : 0);
+		for (size_t k = 0; k < v.size(); ++k) { v[k] = *p[k].desc(); v[k].kind = DJB_PARAMS_KIND(v[k].kind); }
+		return v;
+	}
+	djb_ctx *ctx() const { return (m_ctx ? *m_ctx : hip::context::standard()).get(); }
+	hip::context *m_ctx;
+	djb_merl_set *m_h;
+};
+
 } // namespace djb
 
 #endif // DJB_HIP_HPP

@@ -72,7 +72,7 @@ EXPORTS = [
     "djb_dmap_to_nmap", "djb_leanmap_create_from_nmap", "djb_leanmap_create_from_dmap", "djb_leanmap_create_from_moments", "djb_leanmap_info",
     "djb_leanmap_get_level", "djb_leanmap_destroy", "djb_leanmap_lookup_batch", "djb_eval_leanmap_batch", "djb_sample_leanmap_batch",
     "djb_merl_set_create", "djb_merl_set_set_proxy_params", "djb_merl_set_info", "djb_merl_set_destroy", "djb_merl_set_eval_batch",
-    "djb_merl_set_evalp_is_proxy_batch",
+    "djb_merl_set_evalp_is_proxy_batch", "djb_merl_set_evalp_pdf_proxy_batch",
 ]
 
 _lib = None

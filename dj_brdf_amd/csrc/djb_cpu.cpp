@@ -1019,6 +1019,49 @@ djb_status merl_set_evalp_is_proxy(djb_ctx *ctx, const void *texels, const void 
 	return DJB_OK;
 }
 
+// the light sample: evalp of the hit's table and the proxy's pdf with the hit's parameters for a given pair; dj_merl's guard
+// (cosTheta(wi) <= 0 || cosTheta(wo) <= 0 -> 0, a NaN z evaluated) applied to both
+template <int PK>
+void merl_set_light_loop(const MerlTexel *tex, const Params *params, int n_mat, const Brdf &pb, long long k0, long long k1, const int32_t *material,
+                         const View &vi, const View &vo, const View &vout, float *out_pdf)
+{
+	Brdf tb; memset(&tb, 0, sizeof tb); tb.kind = KIND_MERL;
+	Params tp; memset(&tp, 0, sizeof tp);
+	for (long long k = k0; k < k1; ++k) {
+		v3 fr = mk(0, 0, 0); float pdf = 0.0f;
+		const unsigned int m = (unsigned int)material[k];
+		if (m < (unsigned int)n_mat) {
+			const v3 i = load3(vi, k), o = load3(vo, k);
+			if (!(i.z <= 0.0f || o.z <= 0.0f)) {
+				v3 unused_fr = mk(0, 0, 0); float unused_pdf = 0.0f;
+				tb.merl = tex + (size_t)m * (size_t)MERL_N;
+				eval_one<PK, 4>(pb, params[m], i, o, unused_fr, pdf);
+				eval_one<KIND_MERL, 2>(tb, tp, i, o, fr, unused_pdf);
+			}
+		}
+		store3(vout, k, fr); out_pdf[k] = pdf;
+	}
+}
+djb_status merl_set_evalp_pdf(djb_ctx *ctx, const void *texels, const void *params_, int n_mat, const djb_brdf *proxy, int64_t n,
+                              const int32_t *material, const djb_vec3_view *i, const djb_vec3_view *o, const djb_vec3_view *out_fr,
+                              float *out_pdf)
+{
+	if (n < 0) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: negative batch size");
+	if (!material) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null material array");
+	if (!valid(i) || !valid(o)) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null vec3 view");
+	if (!valid(out_fr) || !out_pdf) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null output");
+	if (B(proxy)->ctx != C(ctx)) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: merl set and proxy belong to different contexts");
+	const Brdf &pb = B(proxy)->dev;
+	const View vi = view_of(i), vo = view_of(o), vout = view_of(out_fr);
+	const MerlTexel *tex = (const MerlTexel *)texels;
+	const Params *params = (const Params *)params_;
+	parallel_for(C(ctx), n, 2048, [&](long long k0, long long k1) {
+		if (pb.kind == KIND_GGX) merl_set_light_loop<KIND_GGX>(tex, params, n_mat, pb, k0, k1, material, vi, vo, vout, out_pdf);
+		else merl_set_light_loop<KIND_BECKMANN>(tex, params, n_mat, pb, k0, k1, material, vi, vo, vout, out_pdf);
+	});
+	return DJB_OK;
+}
+
 djb_status eval_pp(djb_ctx *ctx, const djb_brdf *b_, int64_t n, const djb_vec3_view *i, const djb_vec3_view *o, const float *rec,
                    int mode, const float *base5, float scale, int lean_flags, int want, const djb_vec3_view *out_fr, float *out_pdf,
                    float *out_pp)

@@ -98,6 +98,9 @@ djb_status merl_set_eval(djb_ctx *, const void *texels, int n_mat, int64_t n, co
 djb_status merl_set_evalp_is_proxy(djb_ctx *, const void *texels, const void *params, int n_mat, const djb_brdf *proxy, int64_t n,
                                    const int32_t *material, const float *u1, const float *u2, const djb_vec3_view *o,
                                    const djb_vec3_view *out_w, const djb_vec3_view *out_i, float *out_pdf);
+djb_status merl_set_evalp_pdf(djb_ctx *, const void *texels, const void *params, int n_mat, const djb_brdf *proxy, int64_t n,
+                              const int32_t *material, const djb_vec3_view *i, const djb_vec3_view *o, const djb_vec3_view *out_fr,
+                              float *out_pdf);
 djb_status eval_pp(djb_ctx *, const djb_brdf *, int64_t n, const djb_vec3_view *i, const djb_vec3_view *o, const float *rec,
                    int mode, const float *base5, float scale, int lean_flags, int want, const djb_vec3_view *out_fr, float *out_pdf,
                    float *out_pp);

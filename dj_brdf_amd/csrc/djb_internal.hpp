@@ -65,6 +65,10 @@ hipError_t launch_merl_set_eval(hipStream_t s, const djbdev::MerlTexel *tex, int
 hipError_t launch_merl_set_evalp_is_proxy(hipStream_t s, const Brdf &proxy, const Params *params, const djbdev::MerlTexel *tex, int n_mat, long long n,
                                           const int32_t *material, const float *u1, const float *u2, const View &o, const View &out_w,
                                           const View &out_i, float *out_pdf, bool merl_exact);
+// the light sample per hit: evalp from table[material] and the proxy's pdf with params[material] of a GIVEN pair, both +0 where
+// i.z <= 0 || o.z <= 0.  One launch
+hipError_t launch_merl_set_evalp_pdf(hipStream_t s, const Brdf &proxy, const Params *params, const djbdev::MerlTexel *tex, int n_mat, long long n,
+                                     const int32_t *material, const View &i, const View &o, const View &out_fr, float *out_pdf, bool merl_exact);
 
 // per-pair params: rec = n x 5 floats; mode 0 = pdfparams records, mode 1 = LEAN texel moments composed with
 // base5 = params_to_lrep(base) (unscaled), scale = dmapscale, lean_flags = DJB_LEAN_* as dj_beckmannconductor does;

@@ -2,12 +2,14 @@
 //
 // The bin of a MERL look-up depends on (i, o) alone (merl_index_fast / merl_index), never on the material: a mixed batch computes
 // the index once and gathers from table[material][index].  No kind dispatch, no divergence beyond the one the single-material kernels
-// have.  Two kernels, both with the two-tier shape of k_merl_fast (djb_kernels_merl.hip) and k_evalp_is_proxy<.., KIND_MERL, ..>
+// have.  Three kernels, all with the two-tier shape of k_merl_fast (djb_kernels_merl.hip) and k_evalp_is_proxy<.., KIND_MERL, ..>
 // (djb_kernels_proxy.hip): tier 1 in place, the pairs it declines wait in a per-wave LDS queue -- the record carries the material id --
 // and one drain site finishes them with the exact index as dense waves.
 //   k_merl_set_fast<WANT>                      eval (WANT 1) / evalp (WANT 2) per hit
 //   k_evalp_is_proxy_merl_set<PKIND, DENSE>    the per-bounce step of dj_merl per hit: direction and pdf from a GGX or Beckmann lobe
 //                                              whose Params come per lane from the resident Params[M], f_r cos from table[material]
+//   k_merl_set_evalp_pdf<PKIND, DENSE>         the light-sample step of dj_merl per hit, for a GIVEN pair: f_r cos from table[material] and
+//                                              the proxy lobe's pdf with Params[material], both +0 where i or o is not above the horizon
 // A hit whose id is outside [0, M) is inactive: every output is +0.0f, no table or parameter entry is read, nothing is queued.
 // The per-unit functions are the ones the single-material kernels call (mf_sample, the pdf arm of mf_eval_pdf, merl_index_fast,
 // merl_index, scale, divs), so an active hit has the bits of the single-material route.
@@ -188,6 +190,67 @@ __global__ __launch_bounds__(BLOCK) void k_evalp_is_proxy_merl_set(Brdf pb, cons
 	}
 }
 
+// ---- the light sample (next-event estimation / MIS) per hit: for a given pair, evalp from table[material] and the proxy's pdf with
+// params[material]; dj_merl::eval / ::pdf return 0 where cosTheta(wi) <= 0 || cosTheta(wo) <= 0 (a NaN z is evaluated).  The pdf needs
+// no table: it is stored at once and the queue's record is the 9 words of k_merl_set_fast.  The texel of a pair tier 1 decides is asked
+// for BEFORE the pdf arithmetic and consumed after it.  Beckmann: the pdf arm calls exp alone -- its table is staged, the log / pow
+// tables of mf_sample are not.
+template <int PKIND, bool DENSE>
+__global__ __launch_bounds__(BLOCK) void k_merl_set_evalp_pdf(Brdf pb, const Params *params, const MerlTexel *tex, int n_mat, long long n,
+                                                              const int32_t *mat, View vi, View vo, View vout, float *out_pdf, MerlGuard g,
+                                                              int merl_exact)
+{
+	static_assert(PKIND == KIND_GGX || PKIND == KIND_BECKMANN, "the proxy of a MERL set is an analytic lobe");
+	constexpr bool EXPT = PKIND == KIND_BECKMANN;
+	__shared__ unsigned long long s_exp[EXPT ? 256 : 1];
+	__shared__ unsigned int s_q[BLOCK / 64][9][QCAP];
+	if (EXPT) {
+		pb.exp_lds = glibc_exp_tab_to_lds(s_exp, threadIdx.x, BLOCK);
+		__syncthreads();
+	}
+	pb.atan_lds = 0u;
+
+	const unsigned int t = threadIdx.x, wave = t >> 6, lane = t & 63u;
+	unsigned int (&q)[9][QCAP] = s_q[wave];
+	unsigned int qn = 0;                                                           // wave-uniform
+	const long long stride = (long long)gridDim.x * BLOCK;
+	for (long long k0 = (long long)blockIdx.x * BLOCK; ; k0 += stride) {           // workgroup-uniform trip count; one extra trip flushes the queues
+		const bool last = k0 >= n;
+		bool amb = false;
+		unsigned int id = 0u;
+		v3 i = mk(0, 0, 1), o = mk(0, 0, 1);
+		const long long k = k0 + t;
+		const unsigned int rem = last ? 0u : n - k0 >= (long long)BLOCK ? (unsigned int)BLOCK : (unsigned int)(n - k0);
+		if (t < rem) {
+			id = (unsigned int)__builtin_nontemporal_load(mat + k);
+			i = DENSE ? load3_dense_nt(vi, k0, t) : load3(vi, k); o = DENSE ? load3_dense_nt(vo, k0, t) : load3(vo, k);
+			v3 fr = mk(0, 0, 0); float pdf = 0.0f;                                     // inactive, or below the horizon: +0, nothing read
+			if (id < (unsigned int)n_mat && !(i.z <= 0.0f || o.z <= 0.0f)) {           // dj_merl.cpp:57-60, 69-72; a NaN z is evaluated
+				const Params pp = params[id];                                           // asked for first: loads return in order, and the
+				int idx = 0;                                                            // pdf must not wait for the texel behind them
+				const bool decided = !merl_exact && merl_index_fast(i, o, g, idx);
+				v3 e = mk(0, 0, 0);
+				if (decided) e = merl_set_texel(tex, id, idx);                          // in flight across the pdf
+				v3 unused;
+				mf_eval_pdf<PKIND, 4>(pb, pp, i, o, unused, pdf);                       // microfacet::pdf, dj_brdf.h:1713-1730
+				if (decided) fr = scale(i.z, e);                                        // brdf::evalp, dj_brdf.h:803-806
+				else amb = true;                                                        // the exact index finishes this pair
+			}
+			if (DENSE) __builtin_nontemporal_store(pdf, dense_at(out_pdf + k0, t)); else __builtin_nontemporal_store(pdf, out_pdf + k);
+			if (!amb) { if (DENSE) store3_dense_nt(vout, k0, t, fr); else store3(vout, k, fr); }
+		}
+		unsigned int rec[9];                                                       // built here, from values that live across the branches (see k_merl_set_fast)
+		rec_pack(rec, k, id, i, o);
+		set_queue_push(q, qn, lane, amb, rec);
+		set_queue_drain(q, qn, lane, last, [&](const unsigned int *r) {
+			const v3 iq = rec_i(r);
+			const v3 e = merl_set_texel(tex, r[2], merl_index(iq, rec_o(r)));
+			store3(vout, rec_k(r), scale(iq.z, e));
+		});
+		if (last) break;
+	}
+}
+
 inline bool dense(const View &v) { return v.stride == 1; }
 
 template <int WANT>
@@ -216,6 +279,19 @@ hipError_t launch_set_proxy(hipStream_t s, const Brdf &pb, const Params *params,
 	return hipGetLastError();
 }
 
+template <int PKIND>
+hipError_t launch_set_evalp_pdf(hipStream_t s, const Brdf &pb, const Params *params, const MerlTexel *tex, int n_mat, long long n, const int32_t *mat,
+                                const View &i, const View &o, const View &out, float *out_pdf, bool merl_exact)
+{
+	const MerlGuard g = MERL_GUARD_DEFAULT;
+	dim3 grid(djbk::grid_capped(n, BLOCK, GRID_CAP)), block(BLOCK);
+	if (dense(i) && dense(o) && dense(out))
+		hipLaunchKernelGGL((k_merl_set_evalp_pdf<PKIND, true>), grid, block, 0, s, pb, params, tex, n_mat, n, mat, i, o, out, out_pdf, g, merl_exact ? 1 : 0);
+	else
+		hipLaunchKernelGGL((k_merl_set_evalp_pdf<PKIND, false>), grid, block, 0, s, pb, params, tex, n_mat, n, mat, i, o, out, out_pdf, g, merl_exact ? 1 : 0);
+	return hipGetLastError();
+}
+
 } // namespace
 
 namespace djbk {
@@ -236,6 +312,17 @@ hipError_t launch_merl_set_evalp_is_proxy(hipStream_t s, const Brdf &proxy, cons
 	switch (proxy.kind) {
 	case KIND_GGX: return launch_set_proxy<KIND_GGX>(s, proxy, params, tex, n_mat, n, material, u1, u2, o, out_w, out_i, out_pdf, merl_exact);
 	case KIND_BECKMANN: return launch_set_proxy<KIND_BECKMANN>(s, proxy, params, tex, n_mat, n, material, u1, u2, o, out_w, out_i, out_pdf, merl_exact);
+	}
+	return hipErrorInvalidValue;
+}
+
+hipError_t launch_merl_set_evalp_pdf(hipStream_t s, const Brdf &proxy, const Params *params, const djbdev::MerlTexel *tex, int n_mat, long long n,
+                                     const int32_t *material, const View &i, const View &o, const View &out_fr, float *out_pdf, bool merl_exact)
+{
+	if (n <= 0) return hipSuccess;
+	switch (proxy.kind) {
+	case KIND_GGX: return launch_set_evalp_pdf<KIND_GGX>(s, proxy, params, tex, n_mat, n, material, i, o, out_fr, out_pdf, merl_exact);
+	case KIND_BECKMANN: return launch_set_evalp_pdf<KIND_BECKMANN>(s, proxy, params, tex, n_mat, n, material, i, o, out_fr, out_pdf, merl_exact);
 	}
 	return hipErrorInvalidValue;
 }

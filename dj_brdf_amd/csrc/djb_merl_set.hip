@@ -204,4 +204,35 @@ try {
 }
 DJB_ABI_CATCH
 
+djb_status djb_merl_set_evalp_pdf_proxy_batch(djb_ctx *ctx, const djb_merl_set *s, const djb_brdf *proxy, int64_t n, const int32_t *material,
+                                              const djb_vec3_view *i, const djb_vec3_view *o, const djb_vec3_view *out_fr, float *out_pdf, int mem)
+try {
+	djb_status st = set_check(ctx, s);
+	if (st != DJB_OK) return st;
+	if (!proxy) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null brdf (proxy)");
+	if ((st = cpu_pair_check(ctx, proxy)) != DJB_OK) return st;
+	const bool cpu = is_cpu(ctx);
+	if (!cpu && (proxy->ctx != ctx || proxy->device != ctx->device))
+		return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: merl set and proxy belong to different contexts");
+	const int pkind = cpu ? djbcpu::kind(proxy) : proxy->dev.kind;
+	if (pkind != DJB_KIND_GGX && pkind != DJB_KIND_BECKMANN)
+		return fail(DJB_ERR_NOT_IMPLEMENTED, "djb_error: evalp_pdf_proxy on a merl set takes a ggx or beckmann proxy (proxy kind %d)", pkind);
+	if (!s->has_params) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: the merl set has no proxy parameters (djb_merl_set_set_proxy_params)");
+	if (!out_pdf) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null out_pdf (evalp alone: djb_merl_set_eval_batch)");
+	if (cpu) return djbcpu::merl_set_evalp_pdf(ctx, s->tex, s->params, s->n_mat, proxy, n, material, i, o, out_fr, out_pdf);
+	if ((st = check_call(ctx, proxy, n, mem)) != DJB_OK) return st;
+	std::lock_guard<std::recursive_mutex> call_lock(ctx->call_mu);
+	Staged sg(ctx, n, mem);
+	const int32_t *dmat; View vi, vo, vout; float *dpdf = nullptr;
+	if ((st = stage_material(sg, material, &dmat)) != DJB_OK) return st;
+	if ((st = sg.in_vec(i, &vi)) != DJB_OK) return st;
+	if ((st = sg.in_vec(o, &vo)) != DJB_OK) return st;
+	if ((st = sg.out_vec(out_fr, &vout)) != DJB_OK) return st;
+	if ((st = sg.out_arr(out_pdf, &dpdf)) != DJB_OK) return st;
+	HIP_TRY(djbk::launch_merl_set_evalp_pdf(ctx->stream, proxy->dev, s->params, s->tex, s->n_mat, n, dmat, vi, vo, vout, dpdf,
+	                                        ctx->merl_exact_only != 0));
+	return sg.finish();
+}
+DJB_ABI_CATCH
+
 } // extern "C"

@@ -19,6 +19,7 @@ All arithmetic happens in the HIP kernels; nothing here evaluates a BRDF on the 
 """
 from __future__ import annotations
 
+import mmap
 import threading
 import ctypes as C
 from typing import Optional, Sequence
@@ -147,6 +148,19 @@ def device_count() -> int:
 
 
 # --------------------------------------------------------------------------- array plumbing
+def _host_output(shape, dtype=np.float32):
+    """np.empty for an output batch.  A large one (>= 64 KB) gets pages of its own -- it starts on a page boundary inside a block with
+    a page to spare at either end --: the chunked pipeline of large host batches (djb_host_ops.hip: host_pipeline) is only taken when
+    no input shares a host page with an output, and whether two heap blocks of a few hundred KB do is a matter of the heap's history."""
+    nbytes = int(np.prod(shape)) * np.dtype(dtype).itemsize
+    if nbytes < (1 << 16):
+        return np.empty(shape, dtype=dtype)
+    page = mmap.PAGESIZE
+    raw = np.empty(nbytes + 2 * page, dtype=np.uint8)
+    lo = -raw.ctypes.data % page
+    return raw[lo:lo + nbytes].view(dtype).reshape(shape)
+
+
 class _Vec:
     """A vec3 batch resolved to (view, memory space, n, how to build a like-shaped output)."""
 
@@ -186,14 +200,14 @@ class _Vec:
         shape = (self.n, 3) if self.aos else (3, self.n)
         if self.is_torch:
             return _Vec(torch.empty(shape, dtype=torch.float32, device=self.device))
-        return _Vec(np.empty(shape, dtype=np.float32))
+        return _Vec(_host_output(shape))
 
     def scalars(self, dtype=np.float32):
         if self.is_torch:
             tdt = torch.float32 if dtype == np.float32 else torch.int32
             t = torch.empty((self.n,), dtype=tdt, device=self.device)
             return t, t.data_ptr()
-        a = np.empty((self.n,), dtype=dtype)
+        a = _host_output((self.n,), dtype)
         return a, a.ctypes.data
 
 
@@ -1084,7 +1098,7 @@ class merl(brdf):
 
 class merl_set:
     """M MERL materials resident in ONE block on their context's device, with one fitted proxy parameter set per material: hits that
-    land on many measured materials are evaluated / importance-sampled in one call, each hit naming its material by id
+    land on many measured materials are evaluated / importance-sampled / light-sampled in one call, each hit naming its material by id
     (djb_merl_set, include/djb_hip.h).  An extension: the reference's objects are one material each.
 
     ``material``: int32 ids, one per hit; an id outside [0, M) marks an inactive hit (a dead path), whose outputs are all +0.
@@ -1186,6 +1200,21 @@ class merl_set:
                                                                 C.c_void_p(pdf_ptr), C.c_int(vo.mem)))
         del keep, k1, k2
         return w.keep, i.keep, pdf
+
+    def evalp_pdf_proxy(self, proxy, material, i, o):
+        """(fr, pdf) per hit for GIVEN pairs, the light sample of dj_merl (next-event estimation / MIS): f_r * cos(theta_i) of
+        material[k] and the pdf of ``proxy`` (a ggx or beckmann object) with the hit's material's proxy parameters; both are +0 where
+        i.z <= 0 or o.z <= 0, as the plugin's eval() / pdf() return.  One kernel launch on the GPU."""
+        vi, vo = _Vec(i), _Vec(o)
+        if vi.n != vo.n or vi.mem != vo.mem:
+            raise exc(1, "djb_error: i and o must have the same length and memory space")
+        keep, mp = self._ids(material, vi)
+        fr = vi.like()
+        pdf, pdf_ptr = vi.scalars()
+        _lib.check(_lib.load().djb_merl_set_evalp_pdf_proxy_batch(self.ctx._h, self._h, proxy._h, C.c_int64(vi.n), C.c_void_p(mp), C.byref(vi.view),
+                                                                 C.byref(vo.view), C.byref(fr.view), C.c_void_p(pdf_ptr), C.c_int(vi.mem)))
+        del keep
+        return fr.keep, pdf
 
     def close(self):
         if self._h:

@@ -69,7 +69,9 @@ extern "C" {
  *        Additive under 235, no existing entry changed: MERL material sets -- djb_merl_set, DJB_MERL_SET_MAX, djb_merl_set_create,
  *        djb_merl_set_set_proxy_params, djb_merl_set_info, djb_merl_set_destroy, djb_merl_set_eval_batch,
  *        djb_merl_set_evalp_is_proxy_batch (eval / evalp and proxy importance sampling of hits on M resident MERL tables by per-hit
- *        material id, one call). */
+ *        material id, one call).
+ *        Additive under 235, no existing entry changed: djb_merl_set_evalp_pdf_proxy_batch (the light-sample step on a MERL set: evalp of
+ *        the hit's material and the proxy's pdf with the hit's parameters for a given pair, one call). */
 #define DJB_HIP_VERSION 235
 #define DJB_HIP_VERSION_MAJOR(v) ((v) / 100)
 
@@ -519,12 +521,17 @@ djb_status djb_sample_leanmap_batch(djb_ctx *, const djb_brdf *, const djb_leanm
  *   djb_merl_set_evalp_is_proxy_batch   djb_evalp_is_proxy_batch(target = material m, proxy, ..., proxy_params = params[m]), including the
  *                                       side check (i stored, weight 0, pdf 0 where i.z <= 0), the unguarded o and the IEEE division by
  *                                       a zero pdf
+ *   djb_merl_set_evalp_pdf_proxy_batch  the light sample (next-event estimation / MIS) of mitsuba/dj_merl.cpp:56-107 for a GIVEN pair:
+ *                                       out_fr = djb_evalp_batch on material m, out_pdf = djb_pdf_batch(proxy, i, o, params[m]); and, as
+ *                                       dj_merl's eval() / pdf() guard both, out_fr = +0 and out_pdf = +0 where i.z <= 0 || o.z <= 0
+ *                                       (nothing is read for such a hit; a NaN z does not take the guard).  out_fr and out_pdf may not be
+ *                                       NULL: a caller who wants evalp alone has djb_merl_set_eval_batch
  * A hit whose id is outside [0, M) is INACTIVE: every output of that hit is +0.0f (fr; or weight, i and pdf) and no table or parameter
  * entry is read for it.  Inactive ids are how a renderer marks dead paths: a defined input, not an error.
  *
- * `proxy` must be a ggx or beckmann object of the call's context (any other kind: DJB_ERR_NOT_IMPLEMENTED); sampling on a set without
- * proxy parameters is DJB_ERR_INVALID_ARGUMENT.  DJB_OPT_MERL_EXACT_ONLY sends every active hit through the exact index, as for the
- * single-material calls; DJB_OPT_CONTRACT_1E5 changes nothing.  CPU contexts serve both calls with the host instantiation of the same
+ * `proxy` must be a ggx or beckmann object of the call's context (any other kind: DJB_ERR_NOT_IMPLEMENTED); sampling or the light sample on
+ * a set without proxy parameters is DJB_ERR_INVALID_ARGUMENT.  DJB_OPT_MERL_EXACT_ONLY sends every active hit through the exact index, as for the
+ * single-material calls; DJB_OPT_CONTRACT_1E5 changes nothing.  CPU contexts serve the three calls with the host instantiation of the same
  * per-unit code.  On a GPU context a device-memory batch is ONE kernel launch, with no allocation and no host read-back (it can be
  * captured into a hipGraph); a host-memory batch of any size is staged through HBM (a set has no host twin). */
 #define DJB_MERL_SET_MAX 1024
@@ -540,6 +547,9 @@ djb_status djb_merl_set_evalp_is_proxy_batch(djb_ctx *, const djb_merl_set *, co
                                              const int32_t *material, const float *u1, const float *u2,
                                              const djb_vec3_view *o, const djb_vec3_view *out_weight,
                                              const djb_vec3_view *out_i, float *out_pdf, int mem);
+djb_status djb_merl_set_evalp_pdf_proxy_batch(djb_ctx *, const djb_merl_set *, const djb_brdf *proxy, int64_t n,
+                                              const int32_t *material, const djb_vec3_view *i, const djb_vec3_view *o,
+                                              const djb_vec3_view *out_fr, float *out_pdf, int mem);
 
 /* beckmann::lrep algebra on {E1..E5} (host scalars; dj_brdf.h:330-356, 1959-2051).  b may be NULL
  * (= the default lrep(0,0,1,1,0)); x (and y) are the scalar arguments of mul / shear / scale.

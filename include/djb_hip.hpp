@@ -1275,6 +1275,10 @@ public:
 	void evalp_is_proxy(const microfacet &proxy, size_t n, const int32_t *material, const float_t *u1, const float_t *u2, const vec3 *o,
 	                    vec3 *out_weight, vec3 *out_i, float_t *out_pdf) const
 	{ evalp_is_proxy_views(proxy, (int64_t)n, material, u1, u2, hip::view(o), hip::view(out_weight), hip::view(out_i), out_pdf, DJB_MEM_HOST); }
+	/* the light sample of dj_merl for given pairs: out_fr = evalp of material[k], out_pdf = proxy.pdf(i, o, params[material[k]]), both 0
+	 * where i.z <= 0 || o.z <= 0 (mitsuba/dj_merl.cpp:56-107) */
+	void evalp_pdf_proxy(const microfacet &proxy, size_t n, const int32_t *material, const vec3 *i, const vec3 *o, vec3 *out_fr, float_t *out_pdf) const
+	{ evalp_pdf_proxy_views(proxy, (int64_t)n, material, hip::view(i), hip::view(o), hip::view(out_fr), out_pdf, DJB_MEM_HOST); }
 	// ---- views (SoA or strided), in host memory or in HBM (mem = DJB_MEM_DEVICE: asynchronous on the context's stream, one launch)
 	void eval_views(int64_t n, const int32_t *material, const djb_vec3_view &i, const djb_vec3_view &o, const djb_vec3_view &out,
 	                int want_cos, int mem) const
@@ -1282,6 +1286,9 @@ public:
 	void evalp_is_proxy_views(const microfacet &proxy, int64_t n, const int32_t *material, const float_t *u1, const float_t *u2,
 	                          const djb_vec3_view &o, const djb_vec3_view &out_weight, const djb_vec3_view &out_i, float_t *out_pdf, int mem) const
 	{ hip::check(djb_merl_set_evalp_is_proxy_batch(ctx(), m_h, proxy.handle(), n, material, u1, u2, &o, &out_weight, &out_i, out_pdf, mem)); }
+	void evalp_pdf_proxy_views(const microfacet &proxy, int64_t n, const int32_t *material, const djb_vec3_view &i, const djb_vec3_view &o,
+	                           const djb_vec3_view &out_fr, float_t *out_pdf, int mem) const
+	{ hip::check(djb_merl_set_evalp_pdf_proxy_batch(ctx(), m_h, proxy.handle(), n, material, &i, &o, &out_fr, out_pdf, mem)); }
 private:
 	// the facade's params carry their resolved form; a set takes the plain parameter sets and resolves them itself
 	static std::vector<djb_params> plain(size_t n, const microfacet::params *p)

@@ -64,7 +64,7 @@ EXPORTS = [
     "djb_brdf_create_abc_from_params",
     "djb_brdf_destroy", "djb_brdf_kind", "djb_brdf_get_samples", "djb_brdf_get_shadow", "djb_brdf_set_shadow", "djb_brdf_set_fresnel", "djb_brdf_get_fresnel", "djb_eval_batch", "djb_evalp_batch",
     "djb_pdf_batch", "djb_eval_pdf_batch", "djb_sample_batch", "djb_sample_rng_batch",
-    "djb_evalp_is_batch", "djb_evalp_is_proxy_batch", "djb_io_to_hd_batch", "djb_hd_to_io_batch", "djb_merl_index_batch", "djb_query_batch",
+    "djb_evalp_is_batch", "djb_evalp_is_proxy_batch", "djb_evalp_pdf_proxy_batch", "djb_io_to_hd_batch", "djb_hd_to_io_batch", "djb_merl_index_batch", "djb_query_batch",
     "djb_params_resolve", "djb_tabular_get", "djb_tabular_fit", "djb_fit_merl_batch", "djb_fit_brdf_batch",
     "djb_gen_directions", "djb_gen_uniforms", "djb_histogram_xy", "djb_helper",
     "djb_set_file_map_observer", "djb_brdf_create_user_microfacet", "djb_fit_query_dirs", "djb_fit_aniso_query_dirs", "djb_brdf_create_tabular_from_samples",

@@ -928,6 +928,49 @@ djb_status evalp_is_proxy(djb_ctx *ctx, const djb_brdf *target, const djb_brdf *
 	return DJB_OK;
 }
 
+// the light sample of the same plugins: evalp of the target and the proxy's pdf for a given pair, any pair of kinds; the plugins' guard
+// (cosTheta(wi) <= 0 || cosTheta(wo) <= 0 -> 0, a NaN z evaluated) applied to both
+template <int PK, int TK>
+void proxy_light_loop(const Brdf &tb, const Params &tp, const Brdf &pb, const Params &pp, long long k0, long long k1, const View &vi, const View &vo,
+                      const View &vout, float *out_pdf)
+{
+	for (long long k = k0; k < k1; ++k) {
+		v3 fr = mk(0, 0, 0); float pdf = 0.0f;
+		const v3 i = load3(vi, k), o = load3(vo, k);
+		if (!(i.z <= 0.0f || o.z <= 0.0f)) {
+			v3 unused_fr = mk(0, 0, 0); float unused_pdf = 0.0f;
+			eval_one<PK, 4>(pb, pp, i, o, unused_fr, pdf);
+			eval_one<TK, 2>(tb, tp, i, o, fr, unused_pdf);
+		}
+		store3(vout, k, fr); out_pdf[k] = pdf;
+	}
+}
+template <int PK>
+void proxy_light_target(const Brdf &tb, const Params &tp, const Brdf &pb, const Params &pp, long long k0, long long k1, const View &vi, const View &vo,
+                        const View &vout, float *out_pdf)
+{
+	DJB_KIND_SWITCH(tb.kind, (proxy_light_loop<PK, K>(tb, tp, pb, pp, k0, k1, vi, vo, vout, out_pdf)))
+}
+djb_status evalp_pdf_proxy(djb_ctx *ctx, const djb_brdf *target, const djb_brdf *proxy, int64_t n, const djb_vec3_view *i, const djb_vec3_view *o,
+                           const djb_params *target_params, const djb_params *proxy_params, const djb_vec3_view *out_fr, float *out_pdf)
+{
+	if (!target || !proxy) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null brdf (%s)", !target ? "target" : "proxy");
+	if (n < 0) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: negative batch size");
+	if (B(target)->ctx != B(proxy)->ctx) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: target and proxy belong to different contexts");
+	if (!valid(out_fr) || !out_pdf) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null output");
+	const Brdf &tb = B(target)->dev, &pb = B(proxy)->dev;
+	Params tp, pp;
+	djb_status st = params_for(target_params, tb.kind, &tp);
+	if (st != DJB_OK) return st;
+	if ((st = params_for(proxy_params, pb.kind, &pp)) != DJB_OK) return st;
+	if (!valid(i) || !valid(o)) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null vec3 view");
+	const View vi = view_of(i), vo = view_of(o), vout = view_of(out_fr);
+	parallel_for(C(ctx), n, 2048, [&](long long k0, long long k1) {
+		DJB_KIND_SWITCH(pb.kind, (proxy_light_target<K>(tb, tp, pb, pp, k0, k1, vi, vo, vout, out_pdf)))
+	});
+	return DJB_OK;
+}
+
 // ------------------------------------------------------------------ MERL material sets: the two loops above per hit, the table and the proxy's
 // parameters selected by the hit's material id; an id outside [0, n_mat) is an inactive hit (+0 in every output, nothing read)
 djb_status merl_set_member(const djb_ctx *ctx, const djb_brdf *b, int index, const void **texels)

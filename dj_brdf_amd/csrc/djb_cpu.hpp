@@ -87,6 +87,9 @@ djb_status sample(djb_ctx *, const djb_brdf *, int64_t n, const float *u1, const
 djb_status evalp_is_proxy(djb_ctx *, const djb_brdf *target, const djb_brdf *proxy, int64_t n, const float *u1, const float *u2,
                           const djb_vec3_view *o, const djb_params *target_params, const djb_params *proxy_params,
                           const djb_vec3_view *out_w, const djb_vec3_view *out_i, float *out_pdf);
+// the light sample: fr = target.evalp(i, o), pdf = proxy.pdf(i, o) of a given pair; +0 and +0 where i.z <= 0 || o.z <= 0.  Every pair of kinds
+djb_status evalp_pdf_proxy(djb_ctx *, const djb_brdf *target, const djb_brdf *proxy, int64_t n, const djb_vec3_view *i, const djb_vec3_view *o,
+                           const djb_params *target_params, const djb_params *proxy_params, const djb_vec3_view *out_fr, float *out_pdf);
 // MERL material sets on the host (include/djb_hip.h: djb_merl_set).  texels = MerlTexel[n_mat][1458000], params = djbdev::Params[n_mat]
 // (both host memory, typed in djb_device.hpp); a hit whose id is outside [0, n_mat) gets +0 in every output.
 // merl_set_member: the converted table of a dense MERL object of `ctx` (what djb_merl_set_create copies), or the reason it is refused

@@ -523,6 +523,63 @@ try {
 }
 DJB_ABI_CATCH
 
+// the light sample of the same plugins: fr = target.evalp(i, o) and pdf = proxy.pdf(i, o) of a GIVEN pair, both +0 where i.z <= 0 || o.z <= 0
+// (a NaN z is evaluated).  evalp_is_proxy_common step for step; one launch for device memory (djb_kernels_proxy_light.hip), no allocation after
+// the first call, no read-back.  The two outputs are required before anything else: nothing is written on an error
+static djb_status evalp_pdf_proxy_common(djb_ctx *ctx, const djb_brdf *target, const djb_brdf *proxy, int64_t n, const djb_vec3_view *i,
+                                         const djb_vec3_view *o, const djb_params *target_params, const djb_params *proxy_params,
+                                         const djb_vec3_view *out_fr, float *out_pdf, int mem)
+{
+	if (!target || !proxy) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null brdf (%s)", !target ? "target" : "proxy");
+	if (!ctx) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null ctx");
+	if (!out_fr) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null out_fr (the pdf alone: djb_pdf_batch)");
+	if (!out_pdf) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null out_pdf (evalp alone: djb_evalp_batch)");
+	djb_status st = cpu_pair_check(ctx, target);
+	if (st != DJB_OK) return st;
+	if ((st = cpu_pair_check(ctx, proxy)) != DJB_OK) return st;
+	if (is_cpu(ctx)) return djbcpu::evalp_pdf_proxy(ctx, target, proxy, n, i, o, target_params, proxy_params, out_fr, out_pdf);
+	if (target->ctx != proxy->ctx || target->device != proxy->device)
+		return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: target and proxy belong to different contexts");
+	if (const djb_brdf *tt = scalar_twin(ctx, target, n, mem)) {
+		const djb_brdf *pt = scalar_twin(ctx, proxy, n, mem);
+		if (pt) return djbcpu::evalp_pdf_proxy(djbcpu::twin_ctx(), tt, pt, n, i, o, target_params, proxy_params, out_fr, out_pdf);
+	}
+	if ((st = check_call(ctx, target, n, mem)) != DJB_OK) return st;
+	if ((st = check_call(ctx, proxy, n, mem)) != DJB_OK) return st;
+	if (!djbk::evalp_is_proxy_supported(target->dev.kind, proxy->dev.kind) || (target->dev.kind == DJB_KIND_MERL && target->dev.merl_sparse))
+		return fail(DJB_ERR_NOT_IMPLEMENTED, "djb_error: evalp_pdf_proxy on the GPU takes a merl / utia / sgd / abc target and a ggx / beckmann / tabular / "
+		            "tabular_anisotropic proxy (target kind %d, proxy kind %d)", target->dev.kind, proxy->dev.kind);
+	std::lock_guard<std::recursive_mutex> call_lock(ctx->call_mu);
+	Params tp, pp;
+	if ((st = device_params(target_params, &tp, target->dev.kind)) != DJB_OK) return st;
+	if ((st = device_params(proxy_params, &pp, proxy->dev.kind)) != DJB_OK) return st;
+	if (mem == DJB_MEM_HOST && n > SMALL_N && i && o) {                          // large host batch: chunked, both PCIe directions busy
+		bool taken = false;
+		std::vector<PipeArr> ins{ PipeArr::vec(i), PipeArr::vec(o) }, outs{ PipeArr::vec(out_fr), PipeArr::arr(out_pdf) };
+		st = host_pipeline(ctx, n, ins, outs, [&](long long m, int s) {
+			djb_vec3_view dvi = ins[0].view(s), dvo = ins[1].view(s), dvf = outs[0].view(s);
+			return evalp_pdf_proxy_common(ctx, target, proxy, m, &dvi, &dvo, target_params, proxy_params, &dvf, outs[1].dev[s], DJB_MEM_DEVICE);
+		}, &taken);
+		if (taken || st != DJB_OK) return st;
+	}
+	Staged sg(ctx, n, mem);
+	View vi, vo, vout; float *dpdf = nullptr;
+	if ((st = sg.in_vec(i, &vi)) != DJB_OK) return st;
+	if ((st = sg.in_vec(o, &vo)) != DJB_OK) return st;
+	if ((st = sg.out_vec(out_fr, &vout)) != DJB_OK) return st;
+	if ((st = sg.out_arr(out_pdf, &dpdf)) != DJB_OK) return st;
+	HIP_TRY(djbk::launch_evalp_pdf_proxy(ctx->stream, target->dev, tp, proxy->dev, pp, n, vi, vo, vout, dpdf, ctx->merl_exact_only != 0));
+	return sg.finish();
+}
+
+djb_status djb_evalp_pdf_proxy_batch(djb_ctx *ctx, const djb_brdf *target, const djb_brdf *proxy, int64_t n, const djb_vec3_view *i,
+                                     const djb_vec3_view *o, const djb_params *target_params, const djb_params *proxy_params,
+                                     const djb_vec3_view *out_fr, float *out_pdf, int mem)
+try {
+	return evalp_pdf_proxy_common(ctx, target, proxy, n, i, o, target_params, proxy_params, out_fr, out_pdf, mem);
+}
+DJB_ABI_CATCH
+
 djb_status djb_sample_rng_batch(djb_ctx *ctx, const djb_brdf *b, int64_t n, uint32_t seed_u1, uint32_t seed_u2,
                                 uint64_t start, const djb_vec3_view *o, const djb_params *params,
                                 const djb_vec3_view *out_i)

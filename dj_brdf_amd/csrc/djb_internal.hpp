@@ -56,6 +56,10 @@ bool evalp_is_proxy_supported(int target_kind, int proxy_kind);
 hipError_t launch_evalp_is_proxy(hipStream_t s, const Brdf &target, const Params &target_p, const Brdf &proxy, const Params &proxy_p, long long n,
                                  const float *u1, const float *u2, const View &o, const View &out_w, const View &out_i, float *out_pdf,
                                  bool merl_exact);
+// the light sample of the same plugins (djb_kernels_proxy_light.hip): fr = target.evalp(i, o), pdf = proxy.pdf(i, o) of a GIVEN pair, both +0
+// where i.z <= 0 || o.z <= 0 -- one launch, the pairs of kinds of evalp_is_proxy_supported
+hipError_t launch_evalp_pdf_proxy(hipStream_t s, const Brdf &target, const Params &target_p, const Brdf &proxy, const Params &proxy_p, long long n,
+                                  const View &i, const View &o, const View &out_fr, float *out_pdf, bool merl_exact);
 
 // MERL material sets (djb_kernels_merl_set.hip): tex = MerlTexel[n_mat][1458000], material = n ids (outside [0, n_mat): an inactive hit,
 // every output +0); eval / evalp per hit, and launch_evalp_is_proxy per hit with params[material] as the proxy's parameters.  One launch each;

@@ -436,6 +436,22 @@ class brdf:
         del k1, k2
         return w.keep, i.keep, pdf
 
+    def evalp_pdf_proxy(self, proxy, i, o, user_param=None, proxy_param=None):
+        """(fr, pdf) for GIVEN pairs, the light sample of the dj_merl / dj_utia / dj_sgd / dj_abc plugins (next-event estimation / MIS):
+        fr = self.evalp(i, o, user_param), pdf = proxy.pdf(i, o, proxy_param); both are +0 where i.z <= 0 or o.z <= 0, as the plugins'
+        eval() / pdf() return (a NaN z is evaluated).  One kernel launch on the GPU (djb_evalp_pdf_proxy_batch)."""
+        if not isinstance(proxy, brdf) or not proxy._h or not self._h:     # host code on either side (a user_brdf)
+            return _evalp_pdf_proxy_composed(self, proxy, i, o, user_param, proxy_param)
+        vi, vo = _Vec(i), _Vec(o)
+        if vi.n != vo.n or vi.mem != vo.mem:
+            raise exc(1, "djb_error: i and o must have the same length and memory space")
+        fr = vi.like()
+        pdf, pdf_ptr = vi.scalars()
+        _lib.check(_lib.load().djb_evalp_pdf_proxy_batch(self.ctx._h, self._h, proxy._h, C.c_int64(vi.n), C.byref(vi.view), C.byref(vo.view),
+                                                        _params_ptr(user_param), _params_ptr(proxy_param), C.byref(fr.view),
+                                                        C.c_void_p(pdf_ptr), C.c_int(vi.mem)))
+        return fr.keep, pdf
+
     # ---- static utilities (dj_brdf.h:99-100)
     @staticmethod
     def io_to_hd(i, o, ctx: Optional[Context] = None):
@@ -1290,6 +1306,18 @@ def _evalp_is_proxy_composed(target, proxy, u1, u2, o, user_param, proxy_param):
     w[side] = 0
     pdf_[side] = 0
     return w, i_, pdf_
+
+
+def _evalp_pdf_proxy_composed(target, proxy, i, o, user_param, proxy_param):
+    """evalp_pdf_proxy where an object is host code (a user_brdf): the objects' own operators on host arrays, the guard applied last."""
+    i = np.ascontiguousarray(i, np.float32).reshape(-1, 3)
+    o = np.ascontiguousarray(o, np.float32).reshape(-1, 3)
+    fr = np.array(target.evalp(i, o, user_param), np.float32).reshape(-1, 3)
+    pdf_ = np.array(proxy.pdf(i, o, proxy_param), np.float32)
+    below = (i[:, 2] <= 0) | (o[:, 2] <= 0)   # the plugins' guard (a NaN z does not take it)
+    fr[below] = 0
+    pdf_[below] = 0
+    return fr, pdf_
 
 
 class user_brdf(brdf):

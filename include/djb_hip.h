@@ -71,7 +71,9 @@ extern "C" {
  *        djb_merl_set_evalp_is_proxy_batch (eval / evalp and proxy importance sampling of hits on M resident MERL tables by per-hit
  *        material id, one call).
  *        Additive under 235, no existing entry changed: djb_merl_set_evalp_pdf_proxy_batch (the light-sample step on a MERL set: evalp of
- *        the hit's material and the proxy's pdf with the hit's parameters for a given pair, one call). */
+ *        the hit's material and the proxy's pdf with the hit's parameters for a given pair, one call).
+ *        Additive under 235, no existing entry changed: djb_evalp_pdf_proxy_batch (the light-sample step on a single merl / utia / sgd /
+ *        abc object: evalp of the target and the proxy's pdf for a given pair, guarded, one call). */
 #define DJB_HIP_VERSION 235
 #define DJB_HIP_VERSION_MAJOR(v) ((v) / 100)
 
@@ -389,6 +391,24 @@ djb_status djb_evalp_is_proxy_batch(djb_ctx *, const djb_brdf *target, const djb
                                     const djb_params *target_params, const djb_params *proxy_params,
                                     const djb_vec3_view *out_weight, const djb_vec3_view *out_i,
                                     float *out_pdf, int mem);
+/* the light sample (next-event estimation / MIS) of dj_merl / dj_utia / dj_abc / dj_sgd for a GIVEN pair: f_r cos from `target`, the pdf
+ * the BSDF sampling of djb_evalp_is_proxy_batch would have had for that pair from `proxy`.  Per unit
+ *     out_fr  = target.evalp(i, o, target_params)
+ *     out_pdf = proxy.pdf(i, o, proxy_params)                    (microfacet::pdf: dot(i, h) in the denominator, no saturation)
+ * and out_fr = (+0, +0, +0), out_pdf = +0 where i.z <= 0 || o.z <= 0 (the plugins' guard, mitsuba/dj_merl.cpp:33-42).  A NaN z does
+ * not take the guard: such a pair is evaluated.  A guarded pair reads no table.  Bit-identical to djb_evalp_batch on the target and
+ * djb_pdf_batch on the proxy followed by that guard; DJB_OPT_CONTRACT_1E5 does not affect it (there is no approximate tier), and
+ * DJB_OPT_MERL_EXACT_ONLY sends every unguarded pair of a merl target through the exact bin index.  out_fr and out_pdf are both
+ * required (NULL: DJB_ERR_INVALID_ARGUMENT, nothing written; evalp alone is djb_evalp_batch, the pdf alone djb_pdf_batch); both objects
+ * must belong to the call's context; a sparse merl target is refused; n == 0 is DJB_OK and touches nothing.  On a GPU context a batch
+ * in device memory -- or a host batch above DJB_OPT_HOST_BATCH_MAX -- is ONE kernel launch (asynchronous for device memory, no
+ * allocation after the first call, no read-back: it can be captured into a graph) and takes a merl, utia, sgd or abc target with a
+ * ggx, beckmann, tabular or tabular_anisotropic proxy (any other pair: DJB_ERR_NOT_IMPLEMENTED); CPU contexts and scalar-size host
+ * batches serve every pair of kinds.  40 B per pair cross HBM (24 read, 16 written) against 64 for the two calls and a guard pass. */
+djb_status djb_evalp_pdf_proxy_batch(djb_ctx *, const djb_brdf *target, const djb_brdf *proxy, int64_t n,
+                                     const djb_vec3_view *i, const djb_vec3_view *o,
+                                     const djb_params *target_params, const djb_params *proxy_params,
+                                     const djb_vec3_view *out_fr, float *out_pdf, int mem);
 /* microfacet and radial queries, batched (dj_brdf.h:258-276, 307-314, 366, 384).  a/b/c are the
  * call's arguments in declaration order, each as a vec3 view (scalars in .x, (x,y) slopes in
  * .x/.y, qf2_radial's (u, cos, sin) in .x/.y/.z); the result is written to out.x (Fresnel: xyz).

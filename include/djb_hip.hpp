@@ -393,6 +393,39 @@ public:
 		checked(djb_evalp_is_proxy_batch(ctx(), m_h, proxy.m_h, n, u1, u2, &o, params_of(user_param), proxy.params_of(proxy_param),
 		                                 &out_weight, &out_i, out_pdf, DJB_MEM_DEVICE));
 	}
+	// ---- the light sample (next-event estimation / MIS) of the same plugins for a GIVEN pair: f_r cos from this object, the pdf from
+	// `proxy`; both 0 where i.z <= 0 || o.z <= 0, a NaN z is evaluated (djb_evalp_pdf_proxy_batch)
+	vec3 evalp_pdf_proxy(const brdf &proxy, const vec3 &i, const vec3 &o, float_t *pdf, const void *user_param = NULL,
+	                     const void *proxy_param = NULL) const
+	{
+		vec3 fr; float_t pdf_ = 0;
+		evalp_pdf_proxy(proxy, 1, &i, &o, &fr, &pdf_, user_param, proxy_param);
+		if (pdf) *pdf = pdf_;
+		return fr;
+	}
+	void evalp_pdf_proxy(const brdf &proxy, size_t n, const vec3 *i, const vec3 *o, vec3 *out_fr, float_t *out_pdf,
+	                     const void *user_param = NULL, const void *proxy_param = NULL) const
+	{
+		if (!resident() || !proxy.resident()) {          // host code on either side: the objects' own virtuals, composed per unit
+			for (size_t k = 0; k < n; ++k) {
+				out_fr[k] = vec3(0); out_pdf[k] = 0;
+				if (i[k].z <= 0 || o[k].z <= 0) continue;
+				out_pdf[k] = proxy.pdf(i[k], o[k], proxy_param);
+				out_fr[k] = evalp(i[k], o[k], user_param);
+			}
+			return;
+		}
+		djb_vec3_view vi = hip::view(i), vo = hip::view(o), vr = hip::view(out_fr);
+		checked(djb_evalp_pdf_proxy_batch(ctx(), m_h, proxy.m_h, (int64_t)n, &vi, &vo, params_of(user_param), proxy.params_of(proxy_param),
+		                                  &vr, out_pdf, DJB_MEM_HOST));
+	}
+	void evalp_pdf_proxy_device(const brdf &proxy, int64_t n, const djb_vec3_view &i, const djb_vec3_view &o, const djb_vec3_view &out_fr,
+	                            float_t *out_pdf, const void *user_param = NULL, const void *proxy_param = NULL) const
+	{
+		need_resident("evalp_pdf_proxy_device"); proxy.need_resident("evalp_pdf_proxy_device");
+		checked(djb_evalp_pdf_proxy_batch(ctx(), m_h, proxy.m_h, n, &i, &o, params_of(user_param), proxy.params_of(proxy_param),
+		                                  &out_fr, out_pdf, DJB_MEM_DEVICE));
+	}
 	// ---- batch, device-resident (SoA or strided views in HBM; asynchronous on the context stream): resident objects only
 	void eval_device(int64_t n, const djb_vec3_view &i, const djb_vec3_view &o, const djb_vec3_view &out,
 	                 const void *user_param = NULL) const

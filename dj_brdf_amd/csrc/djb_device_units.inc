@@ -55,6 +55,21 @@ DJB_DEV void store3_dense_nt(const View &v, long long k0, unsigned int t, v3 a)
 	float *x = v.x + k0, *y = v.y + k0, *z = v.z + k0;
 	__builtin_nontemporal_store(a.x, dense_at(x, t)); __builtin_nontemporal_store(a.y, dense_at(y, t)); __builtin_nontemporal_store(a.z, dense_at(z, t));
 }
+// ... and addressed as SGPR base + the lane's 32-bit byte offset taken through lane_byte_offset() once per block of accesses.
+// k_evalp_pdf_proxy uses them with a merl or utia target: there load3_dense_nt's addresses were kept as 64-bit values across the body
+// (80 / 103 VGPRs against 63 / 85).  With an sgd or abc target it is the other way round -- the opaque offset costs 121 / 73 VGPRs
+// against 92 / 59 -- so those keep load3_dense_nt / store3_dense_nt.  Register counts from the compiler's resource remarks; the two
+// forms were not timed against each other.
+DJB_DEV v3 load3_dense_off_nt(const View &v, long long k0, unsigned int off)
+{
+	return mk(__builtin_nontemporal_load(dense_off(v.x + k0, off)), __builtin_nontemporal_load(dense_off(v.y + k0, off)),
+	          __builtin_nontemporal_load(dense_off(v.z + k0, off)));
+}
+DJB_DEV void store3_dense_off_nt(const View &v, long long k0, unsigned int off, v3 a)
+{
+	__builtin_nontemporal_store(a.x, dense_off(v.x + k0, off)); __builtin_nontemporal_store(a.y, dense_off(v.y + k0, off));
+	__builtin_nontemporal_store(a.z, dense_off(v.z + k0, off));
+}
 #endif
 
 // ------------------------------------------------------------------ counter-based RNG (synth.py)

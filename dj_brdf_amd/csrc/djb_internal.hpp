@@ -22,6 +22,11 @@ inline int grid_capped(long long n, int block, long long cap)
 	return (int)blocks;
 }
 
+// dense batches address their arrays as uniform base + lane offset (load3_dense / store3_dense, djb_device_units.inc).  Two meanings:
+// dense_strict -- the view is there and has stride 1; dense_or_null -- ... or the view is absent (an output the call does not ask for)
+inline bool dense_strict(const View &v) { return v.stride == 1; }
+inline bool dense_or_null(const View &v) { return v.stride == 1 || v.x == nullptr; }
+
 // WANT bits: 1 eval, 2 evalp, 4 pdf (1 and 2 are exclusive)
 hipError_t launch_eval(hipStream_t s, const Brdf &b, const Params &p, long long n,
                        const View &i, const View &o, const View &out_fr, float *out_pdf, int want);

@@ -5,6 +5,7 @@
 // object and the microfacet parameters arrive as kernel arguments (SGPRs).  There is no
 // inter-lane communication: the path is elementwise (+ one cache-resident gather for MERL/UTIA).
 #include "djb_internal.hpp"
+#include "djb_worklist.hpp"
 
 using namespace djbdev;
 
@@ -26,9 +27,6 @@ inline int grid_full(long long n)
 	if (blocks < 1) blocks = 1;
 	return (int)blocks;
 }
-
-// load3_dense / store3_dense (djb_device_units.inc): dense batches address their arrays as uniform base + lane offset
-inline bool dense(const View &v) { return v.stride == 1 || v.x == nullptr; }
 
 // min-waves hint per kind, measured (round 2; ms per 1e8 pairs at 1 / 4 / 8 waves; the rates themselves are bench.py legs now): the analytic /
 // tabulated microfacet kernels fit 128 VGPRs (4); utia 3.34 / 2.93 / 10.5 and sgd 4.46 / 4.17 / 8.3 want 4
@@ -75,12 +73,7 @@ __global__ __launch_bounds__(eval_block(KIND), eval_min_waves(KIND)) void k_eval
 	__shared__ float s_tab[TAB_LDS ? TAB_LDS : 1];
 	if (TAB_LDS) {
 		int used = 0;
-		auto stage = [&](const float *&src, int count) {
-			if (src == nullptr || count <= 0 || used + count > TAB_LDS) return;
-			float *dst = s_tab + used;
-			for (int k = threadIdx.x; k < count; k += BS) dst[k] = src[k];
-			src = dst; used += count;
-		};
+		auto stage = [&](const float *&src, int count) { stage_table<BS>(s_tab, used, src, count); };
 		if (KIND == KIND_TABULAR) { stage(b.p22, b.n_p22); stage(b.sigma, b.n_sigma); }
 		if (KIND == KIND_TABULAR_ANISO) { stage(b.sigma, b.elev * b.azim); stage(b.p22, b.elev * b.azim); }
 		if (FRK == FR_SPLINE) stage(b.fr.pts, 3 * b.fr.npts);
@@ -237,7 +230,7 @@ hipError_t launch_eval_kind_fr(hipStream_t s, const Brdf &b, const Params &p, lo
 {
 	dim3 g((KIND == KIND_BECKMANN || KIND == KIND_GGX) ? grid_full(n) : djbk::grid_capped(n, BLOCK, GRID_CAP)), t(eval_block(KIND));
 	if (eval_block(KIND) != BLOCK) { long long bl = (n + eval_block(KIND) - 1) / eval_block(KIND); g = dim3((unsigned int)(bl < 1 ? 1 : bl > 2048 ? 2048 : bl)); }
-	const bool dn = dense(i) && dense(o) && dense(out);
+	const bool dn = djbk::dense_or_null(i) && djbk::dense_or_null(o) && djbk::dense_or_null(out);
 	if constexpr (KIND == KIND_BECKMANN && (FRK == FR_IDEAL || FRK == FR_SCHLICK || FRK == FR_UNPOLARIZED)) {
 		if (beckmann_sharp_supported(b, p) && n >= (1LL << 16)) {
 			// persistent grid, ~32 tiles per workgroup: the queue needs iterations to fill
@@ -415,12 +408,7 @@ __global__ __launch_bounds__(BLOCK) void k_sample(Brdf b, Params p, long long n,
 	__shared__ float s_tab[TAB_LDS ? TAB_LDS : 1];
 	if (TAB_LDS) {
 		int used = 0;
-		auto stage = [&](const float *&src, int count) {
-			if (src == nullptr || count <= 0 || used + count > TAB_LDS) return;
-			float *dst = s_tab + used;
-			for (int k = threadIdx.x; k < count; k += BLOCK) dst[k] = src[k];
-			src = dst; used += count;
-		};
+		auto stage = [&](const float *&src, int count) { stage_table<BLOCK>(s_tab, used, src, count); };
 		if (KIND == KIND_TABULAR) stage(b.qf, b.n_qf);
 		if (KIND == KIND_TABULAR_ANISO) { stage(b.a_qf2, b.elev * b.azim); stage(b.a_qf1, b.n_a_qf1); }
 	}
@@ -456,7 +444,7 @@ hipError_t launch_sample_kind(hipStream_t s, const Brdf &b, const Params &p, lon
 	dim3 g((KIND == KIND_BECKMANN || KIND == KIND_GGX) ? grid_full(n) : djbk::grid_capped(n, BLOCK, GRID_CAP)), t(BLOCK);
 	View w = out_w ? *out_w : View{ nullptr, nullptr, nullptr, 0 };
 	const bool is = out_w != nullptr, rng = u1 == nullptr;
-	const bool dn = dense(o) && dense(out_i) && dense(w);
+	const bool dn = djbk::dense_or_null(o) && djbk::dense_or_null(out_i) && djbk::dense_or_null(w);
 	// evalp_is evaluates the Fresnel term of the sampled pair: specialised like k_eval
 	constexpr bool analytic = KIND == KIND_BECKMANN || KIND == KIND_GGX;
 	constexpr bool fitted = KIND == KIND_TABULAR || KIND == KIND_TABULAR_ANISO;
@@ -736,7 +724,7 @@ hipError_t launch_sample(hipStream_t s, const Brdf &b, const Params &p, long lon
 		CtParams ct;
 		if (contract && out_w && contract_params(b, p, nullptr, &ct)) {      // evalp_is under DJB_OPT_CONTRACT_1E5: exact direction, contract tail
 			const dim3 g(grid_full(n)), t(BLOCK);
-			const bool rng = u1 == nullptr, dn = dense(o) && dense(out_i) && dense(*out_w);
+			const bool rng = u1 == nullptr, dn = djbk::dense_or_null(o) && djbk::dense_or_null(out_i) && djbk::dense_or_null(*out_w);
 #define DJB_IS_CT(FRK_) do { \
 			if (rng) { if (dn) hipLaunchKernelGGL((k_evalp_is_ggx_ct<true, FRK_, true>), g, t, 0, s, b, p, ct, n, u1, u2, s1, s2, start, o, out_i, *out_w, out_pdf); \
 			           else hipLaunchKernelGGL((k_evalp_is_ggx_ct<true, FRK_, false>), g, t, 0, s, b, p, ct, n, u1, u2, s1, s2, start, o, out_i, *out_w, out_pdf); } \

@@ -16,6 +16,7 @@
 // Addressing: material * 1458000 + index fits an int32 up to DJB_MERL_SET_MAX = 1024 tables, the BYTE offset (x 12) does not beyond
 // table 245 -- merl_set_texel forms the element index in 64 bits.
 #include "djb_internal.hpp"
+#include "djb_worklist.hpp"
 
 using namespace djbdev;
 
@@ -31,51 +32,12 @@ DJB_DEV v3 merl_set_texel(const MerlTexel *tex, unsigned int material, int idx)
 	return mk(t.x, t.y, t.z);
 }
 
-// ---- the per-wave queue of the pairs tier 1 declines, W words per record.  Fewer than 64 wait when an iteration starts and an
-// iteration adds at most 64 (one unit per lane).  One wave, in-order LDS: no barrier, no atomics.
-constexpr unsigned int QCAP = 128;
-template <int W>
-DJB_DEV void set_queue_push(unsigned int (&q)[W][QCAP], unsigned int &qn, unsigned int lane, bool amb, const unsigned int (&rec)[W])
-{
-	const unsigned long long mask = __ballot(amb);
-	if (!mask) return;
-	if (amb) {
-		const unsigned int j = qn + (unsigned int)__popcll(mask & ((1ull << lane) - 1ull));
-#pragma unroll
-		for (int w = 0; w < W; ++w) q[w][j] = rec[w];
-	}
-	qn += (unsigned int)__popcll(mask);
-}
-// while a full wave of records waits -- or, on the last trip, any -- hand `finish` one record per lane
-template <int W, class Finish>
-DJB_DEV void set_queue_drain(unsigned int (&q)[W][QCAP], unsigned int &qn, unsigned int lane, bool last, Finish finish)
-{
-	while (qn >= 64u || (last && qn)) {
-		const unsigned int cnt = qn < 64u ? qn : 64u;
-		qn -= cnt;
-		__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-		__builtin_amdgcn_wave_barrier();
-		if (lane < cnt) {
-			unsigned int rec[W];
-#pragma unroll
-			for (int w = 0; w < W; ++w) rec[w] = q[w][qn + lane];
-			finish(rec);
-		}
-		__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-		__builtin_amdgcn_wave_barrier();
-	}
-}
-// the part of a record both kernels share: {k lo, k hi, material, i.xyz, o.xyz}
+// the queue of the pairs tier 1 declines (djb_worklist.hpp: recq_push / recq_drain).  The part of a record all three kernels share:
+// {k lo, k hi, material, i.xyz, o.xyz}
 DJB_DEV void rec_pack(unsigned int *rec, long long k, unsigned int material, v3 i, v3 o)
 {
-	rec[0] = (unsigned int)((unsigned long long)k & 0xffffffffull); rec[1] = (unsigned int)((unsigned long long)k >> 32);
-	rec[2] = material;
-	rec[3] = __float_as_uint(i.x); rec[4] = __float_as_uint(i.y); rec[5] = __float_as_uint(i.z);
-	rec[6] = __float_as_uint(o.x); rec[7] = __float_as_uint(o.y); rec[8] = __float_as_uint(o.z);
+	rec_put_k(rec, k); rec[2] = material; rec_put_v3(rec, 3, i); rec_put_v3(rec, 6, o);
 }
-DJB_DEV long long rec_k(const unsigned int *rec) { return (long long)(((unsigned long long)rec[1] << 32) | rec[0]); }
-DJB_DEV v3 rec_i(const unsigned int *rec) { return mk(__uint_as_float(rec[3]), __uint_as_float(rec[4]), __uint_as_float(rec[5])); }
-DJB_DEV v3 rec_o(const unsigned int *rec) { return mk(__uint_as_float(rec[6]), __uint_as_float(rec[7]), __uint_as_float(rec[8])); }
 
 // ---- eval / evalp.  DENSE: every view has stride 1 -- the 40 B/hit streams (id, i, o, out) are touched once: non-temporal, so that
 // they leave the L2 to the table gathers
@@ -83,9 +45,9 @@ template <int WANT, bool DENSE>
 __global__ __launch_bounds__(BLOCK) void k_merl_set_fast(const MerlTexel *tex, int n_mat, long long n, const int32_t *mat, View vi, View vo, View vout,
                                                          MerlGuard g, int merl_exact)
 {
-	__shared__ unsigned int s_q[BLOCK / 64][9][QCAP];
+	__shared__ unsigned int s_q[BLOCK / 64][9][RECQ_CAP];
 	const unsigned int t = threadIdx.x, wave = t >> 6, lane = t & 63u;
-	unsigned int (&q)[9][QCAP] = s_q[wave];
+	unsigned int (&q)[9][RECQ_CAP] = s_q[wave];
 	unsigned int qn = 0;                                                           // wave-uniform
 	const long long stride = (long long)gridDim.x * BLOCK;
 	for (long long k0 = (long long)blockIdx.x * BLOCK; ; k0 += stride) {           // workgroup-uniform trip count; one extra trip flushes the queues
@@ -108,14 +70,12 @@ __global__ __launch_bounds__(BLOCK) void k_merl_set_fast(const MerlTexel *tex, i
 			}
 			if (!amb) { if (DENSE) store3_dense_nt(vout, k0, t, fr); else store3(vout, k, fr); }
 		}
-		// the record is built HERE, from values that live across the branches above, as merl_queue's callers pass k, i, o: packed inside
-		// the declining branch, the k word of a pair tier 1 declined came out as 0 in the generated code (the fp64-only path kept it)
-		unsigned int rec[9];
+		unsigned int rec[9];                                                       // built here, outside the branches above (djb_worklist.hpp)
 		rec_pack(rec, k, id, i, o);
-		set_queue_push(q, qn, lane, amb, rec);
-		set_queue_drain(q, qn, lane, last, [&](const unsigned int *r) {
-			const v3 i = rec_i(r);
-			const v3 e = merl_set_texel(tex, r[2], merl_index(i, rec_o(r)));
+		recq_push(q, qn, lane, amb, rec);
+		recq_drain(q, qn, lane, last, [&](const unsigned int *r) {
+			const v3 i = rec_v3(r, 3);
+			const v3 e = merl_set_texel(tex, r[2], merl_index(i, rec_v3(r, 6)));
 			store3(vout, rec_k(r), (WANT & 2) ? scale(i.z, e) : e);
 		});
 		if (last) break;
@@ -132,7 +92,7 @@ __global__ __launch_bounds__(BLOCK) void k_evalp_is_proxy_merl_set(Brdf pb, cons
 	constexpr bool GLIBCT = PKIND == KIND_BECKMANN;                                // logf / expf / powf of Beckmann's quantile functions
 	__shared__ double s_glibc[GLIBCT ? GLIBC_LDS_WORDS : 1];
 	__shared__ unsigned long long s_exp[GLIBCT ? 256 : 1];
-	__shared__ unsigned int s_q[BLOCK / 64][10][QCAP];
+	__shared__ unsigned int s_q[BLOCK / 64][10][RECQ_CAP];
 	GlibcTabs gt = glibc_tabs_global();
 	if (GLIBCT) {
 		gt = glibc_tabs_to_lds(s_glibc, threadIdx.x, BLOCK);
@@ -143,7 +103,7 @@ __global__ __launch_bounds__(BLOCK) void k_evalp_is_proxy_merl_set(Brdf pb, cons
 	pb.atan_lds = 0u;
 
 	const unsigned int t = threadIdx.x, wave = t >> 6, lane = t & 63u;
-	unsigned int (&q)[10][QCAP] = s_q[wave];
+	unsigned int (&q)[10][RECQ_CAP] = s_q[wave];
 	unsigned int qn = 0;                                                           // wave-uniform
 	const long long stride = (long long)gridDim.x * BLOCK;
 	for (long long k0 = (long long)blockIdx.x * BLOCK; ; k0 += stride) {           // one extra trip flushes the queues
@@ -180,10 +140,10 @@ __global__ __launch_bounds__(BLOCK) void k_evalp_is_proxy_merl_set(Brdf pb, cons
 		}
 		unsigned int rec[10];
 		rec_pack(rec, k, id, i_, o); rec[9] = __float_as_uint(pdf);
-		set_queue_push(q, qn, lane, amb, rec);
-		set_queue_drain(q, qn, lane, last, [&](const unsigned int *r) {
-			const v3 iq = rec_i(r);
-			const v3 e = merl_set_texel(tex, r[2], merl_index(iq, rec_o(r)));
+		recq_push(q, qn, lane, amb, rec);
+		recq_drain(q, qn, lane, last, [&](const unsigned int *r) {
+			const v3 iq = rec_v3(r, 3);
+			const v3 e = merl_set_texel(tex, r[2], merl_index(iq, rec_v3(r, 6)));
 			store3(vw_out, rec_k(r), divs(scale(iq.z, e), __uint_as_float(r[9])));
 		});
 		if (last) break;
@@ -203,7 +163,7 @@ __global__ __launch_bounds__(BLOCK) void k_merl_set_evalp_pdf(Brdf pb, const Par
 	static_assert(PKIND == KIND_GGX || PKIND == KIND_BECKMANN, "the proxy of a MERL set is an analytic lobe");
 	constexpr bool EXPT = PKIND == KIND_BECKMANN;
 	__shared__ unsigned long long s_exp[EXPT ? 256 : 1];
-	__shared__ unsigned int s_q[BLOCK / 64][9][QCAP];
+	__shared__ unsigned int s_q[BLOCK / 64][9][RECQ_CAP];
 	if (EXPT) {
 		pb.exp_lds = glibc_exp_tab_to_lds(s_exp, threadIdx.x, BLOCK);
 		__syncthreads();
@@ -211,7 +171,7 @@ __global__ __launch_bounds__(BLOCK) void k_merl_set_evalp_pdf(Brdf pb, const Par
 	pb.atan_lds = 0u;
 
 	const unsigned int t = threadIdx.x, wave = t >> 6, lane = t & 63u;
-	unsigned int (&q)[9][QCAP] = s_q[wave];
+	unsigned int (&q)[9][RECQ_CAP] = s_q[wave];
 	unsigned int qn = 0;                                                           // wave-uniform
 	const long long stride = (long long)gridDim.x * BLOCK;
 	for (long long k0 = (long long)blockIdx.x * BLOCK; ; k0 += stride) {           // workgroup-uniform trip count; one extra trip flushes the queues
@@ -239,19 +199,17 @@ __global__ __launch_bounds__(BLOCK) void k_merl_set_evalp_pdf(Brdf pb, const Par
 			if (DENSE) __builtin_nontemporal_store(pdf, dense_at(out_pdf + k0, t)); else __builtin_nontemporal_store(pdf, out_pdf + k);
 			if (!amb) { if (DENSE) store3_dense_nt(vout, k0, t, fr); else store3(vout, k, fr); }
 		}
-		unsigned int rec[9];                                                       // built here, from values that live across the branches (see k_merl_set_fast)
+		unsigned int rec[9];                                                       // built here, outside the branches above (djb_worklist.hpp)
 		rec_pack(rec, k, id, i, o);
-		set_queue_push(q, qn, lane, amb, rec);
-		set_queue_drain(q, qn, lane, last, [&](const unsigned int *r) {
-			const v3 iq = rec_i(r);
-			const v3 e = merl_set_texel(tex, r[2], merl_index(iq, rec_o(r)));
+		recq_push(q, qn, lane, amb, rec);
+		recq_drain(q, qn, lane, last, [&](const unsigned int *r) {
+			const v3 iq = rec_v3(r, 3);
+			const v3 e = merl_set_texel(tex, r[2], merl_index(iq, rec_v3(r, 6)));
 			store3(vout, rec_k(r), scale(iq.z, e));
 		});
 		if (last) break;
 	}
 }
-
-inline bool dense(const View &v) { return v.stride == 1; }
 
 template <int WANT>
 hipError_t launch_set_eval(hipStream_t s, const MerlTexel *tex, int n_mat, long long n, const int32_t *mat, const View &i, const View &o,
@@ -259,7 +217,7 @@ hipError_t launch_set_eval(hipStream_t s, const MerlTexel *tex, int n_mat, long 
 {
 	const MerlGuard g = MERL_GUARD_DEFAULT;
 	dim3 grid(djbk::grid_capped(n, BLOCK, GRID_CAP)), block(BLOCK);
-	if (dense(i) && dense(o) && dense(out))
+	if (djbk::dense_strict(i) && djbk::dense_strict(o) && djbk::dense_strict(out))
 		hipLaunchKernelGGL((k_merl_set_fast<WANT, true>), grid, block, 0, s, tex, n_mat, n, mat, i, o, out, g, merl_exact ? 1 : 0);
 	else
 		hipLaunchKernelGGL((k_merl_set_fast<WANT, false>), grid, block, 0, s, tex, n_mat, n, mat, i, o, out, g, merl_exact ? 1 : 0);
@@ -272,7 +230,7 @@ hipError_t launch_set_proxy(hipStream_t s, const Brdf &pb, const Params *params,
 {
 	const MerlGuard g = MERL_GUARD_DEFAULT;
 	dim3 grid(djbk::grid_capped(n, BLOCK, GRID_CAP)), block(BLOCK);
-	if (dense(o) && dense(out_w) && dense(out_i))
+	if (djbk::dense_strict(o) && djbk::dense_strict(out_w) && djbk::dense_strict(out_i))
 		hipLaunchKernelGGL((k_evalp_is_proxy_merl_set<PKIND, true>), grid, block, 0, s, pb, params, tex, n_mat, n, mat, u1, u2, o, out_w, out_i, out_pdf, g, merl_exact ? 1 : 0);
 	else
 		hipLaunchKernelGGL((k_evalp_is_proxy_merl_set<PKIND, false>), grid, block, 0, s, pb, params, tex, n_mat, n, mat, u1, u2, o, out_w, out_i, out_pdf, g, merl_exact ? 1 : 0);
@@ -285,7 +243,7 @@ hipError_t launch_set_evalp_pdf(hipStream_t s, const Brdf &pb, const Params *par
 {
 	const MerlGuard g = MERL_GUARD_DEFAULT;
 	dim3 grid(djbk::grid_capped(n, BLOCK, GRID_CAP)), block(BLOCK);
-	if (dense(i) && dense(o) && dense(out))
+	if (djbk::dense_strict(i) && djbk::dense_strict(o) && djbk::dense_strict(out))
 		hipLaunchKernelGGL((k_merl_set_evalp_pdf<PKIND, true>), grid, block, 0, s, pb, params, tex, n_mat, n, mat, i, o, out, out_pdf, g, merl_exact ? 1 : 0);
 	else
 		hipLaunchKernelGGL((k_merl_set_evalp_pdf<PKIND, false>), grid, block, 0, s, pb, params, tex, n_mat, n, mat, i, o, out, out_pdf, g, merl_exact ? 1 : 0);

@@ -14,6 +14,7 @@
 // direction already stored -- in a per-wave LDS queue and is finished by the exact index (merl_index) in dense waves, as in
 // k_merl_fast.  The other targets run eval_one in place, sgd / abc with their decided fast tier as in k_eval.
 #include "djb_internal.hpp"
+#include "djb_worklist.hpp"
 
 using namespace djbdev;
 
@@ -26,11 +27,11 @@ constexpr int proxy_block(int pkind, int tkind) { return pkind == KIND_TABULAR_A
 // floats of table staging: what k_sample stages for the kind (qf | qf2 grid + qf1) plus what k_eval stages (p22 + sigma | both grids)
 constexpr int proxy_tab_lds(int pkind) { return pkind == KIND_TABULAR ? 2048 + 3072 : pkind == KIND_TABULAR_ANISO ? 8192 + 1024 + 16384 + 768 : 0; }
 
-inline bool dense(const View &v) { return v.stride == 1; }
-
-// the queue of the pairs MERL's tier 1 declines: {k lo, k hi, i.xyz, o.xyz, pdf}; fewer than 64 wait when an iteration starts and
-// an iteration adds at most 64
-constexpr unsigned int QCAP = 128;
+// the queue of the pairs MERL's tier 1 declines, 9 words per record: {k lo, k hi, i.xyz, o.xyz, pdf}.  It is the extra-trip record queue of
+// djb_worklist.hpp written out: through recq_push / recq_drain the eight MERL-target instantiations took 2 more VGPRs each (63 -> 65,
+// 65 -> 67, 67 -> 69: the lane's slot address hoisted out of the batch loop, the pdf word read before merl_index instead of after it),
+// and the form of the drain that reads the record in place moved the code of every other kernel that uses the helper
+// (profiles/wave_queue/proxy_trial.txt).  The five other kernels use the helper; this one keeps its own copy until a form exists that costs nothing.
 
 template <int PKIND, int TKIND, bool DENSE>
 __global__ __launch_bounds__(proxy_block(PKIND, TKIND)) void k_evalp_is_proxy(Brdf pb, Params pp, Brdf tb, Params tp, long long n,
@@ -47,7 +48,7 @@ __global__ __launch_bounds__(proxy_block(PKIND, TKIND)) void k_evalp_is_proxy(Br
 	__shared__ unsigned long long s_exp[EXPT ? 256 : 1];
 	__shared__ double s_pow[POWT ? 384 : 1];
 	__shared__ double s_atan[ATANT ? 16 : 1];
-	__shared__ unsigned int s_q[MERLQ ? BS / 64 : 1][9][MERLQ ? QCAP : 1];
+	__shared__ unsigned int s_q[MERLQ ? BS / 64 : 1][9][MERLQ ? RECQ_CAP : 1];
 	GlibcTabs gt = glibc_tabs_global();
 	if (GLIBCT) gt = glibc_tabs_to_lds(s_glibc, threadIdx.x, BS);
 	if (EXPT) { const LdsTab e = glibc_exp_tab_to_lds(s_exp, threadIdx.x, BS); pb.exp_lds = tb.exp_lds = e; if (GLIBCT) gt.exp64 = e; }
@@ -57,19 +58,14 @@ __global__ __launch_bounds__(proxy_block(PKIND, TKIND)) void k_evalp_is_proxy(Br
 	__shared__ float s_tab[TAB_LDS ? TAB_LDS : 1];
 	if (TAB_LDS) {
 		int used = 0;
-		auto stage = [&](const float *&src, int count) {
-			if (src == nullptr || count <= 0 || used + count > TAB_LDS) return;     // a table that does not fit stays in global memory
-			float *dst = s_tab + used;
-			for (int k = threadIdx.x; k < count; k += BS) dst[k] = src[k];
-			src = dst; used += count;
-		};
+		auto stage = [&](const float *&src, int count) { stage_table<BS>(s_tab, used, src, count); };
 		if (PKIND == KIND_TABULAR) { stage(pb.qf, pb.n_qf); stage(pb.p22, pb.n_p22); stage(pb.sigma, pb.n_sigma); }
 		if (PKIND == KIND_TABULAR_ANISO) { stage(pb.a_qf2, pb.elev * pb.azim); stage(pb.a_qf1, pb.n_a_qf1); stage(pb.sigma, pb.elev * pb.azim); stage(pb.p22, pb.elev * pb.azim); }
 	}
 	if (GLIBCT || EXPT || POWT || ATANT || TAB_LDS) __syncthreads();
 
 	const unsigned int t = threadIdx.x, wave = t >> 6, lane = t & 63u;
-	unsigned int (&q)[9][MERLQ ? QCAP : 1] = s_q[MERLQ ? wave : 0];
+	unsigned int (&q)[9][MERLQ ? RECQ_CAP : 1] = s_q[MERLQ ? wave : 0];
 	unsigned int qn = 0;                                                               // wave-uniform
 	const long long stride = (long long)gridDim.x * BS;
 	for (long long k0 = (long long)blockIdx.x * BS; ; k0 += stride) {                  // k0: workgroup-uniform; MERL: one extra trip flushes the queues
@@ -151,7 +147,7 @@ hipError_t launch_pair(hipStream_t s, const Brdf &pb, const Params &pp, const Br
 	constexpr int BS = proxy_block(PKIND, TKIND);
 	const MerlGuard g = MERL_GUARD_DEFAULT;
 	dim3 grid(djbk::grid_capped(n, BS, 256LL * 16 * 256 / BS)), block(BS);   // 16 workgroups of 256 per CU's worth, grid-stride beyond
-	if (dense(o) && dense(out_w) && dense(out_i))
+	if (djbk::dense_strict(o) && djbk::dense_strict(out_w) && djbk::dense_strict(out_i))
 		hipLaunchKernelGGL((k_evalp_is_proxy<PKIND, TKIND, true>), grid, block, 0, s, pb, pp, tb, tp, n, u1, u2, o, out_w, out_i, out_pdf, g, merl_exact ? 1 : 0);
 	else
 		hipLaunchKernelGGL((k_evalp_is_proxy<PKIND, TKIND, false>), grid, block, 0, s, pb, pp, tb, tp, n, u1, u2, o, out_w, out_i, out_pdf, g, merl_exact ? 1 : 0);

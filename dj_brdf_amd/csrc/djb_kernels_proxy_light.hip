@@ -3,8 +3,8 @@
 //     fr  = target.evalp(i, o)                                 brdf::evalp, dj_brdf.h:803-806
 //     pdf = proxy.pdf(i, o, proxy_params)                      microfacet::pdf, dj_brdf.h:1713-1730 (dot(i, h), no sat)
 // with fr = +0 and pdf = +0 where i.z <= 0 || o.z <= 0 (the plugins' guard, mitsuba/dj_merl.cpp:33-42; a NaN z does not take it).
-// The other half of the per-bounce step is k_evalp_is_proxy (djb_kernels_proxy.hip); this kernel has its pairs of kinds, its workgroup
-// sizes and its queue, in a translation unit of its own so that the code of those kernels cannot move.  The per-unit functions are the
+// The other half of the per-bounce step is k_evalp_is_proxy (djb_kernels_proxy.hip); this kernel has its pairs of kinds and its workgroup
+// sizes, in a translation unit of its own so that the code of those kernels cannot move; the queue is the shared one of djb_worklist.hpp.  The per-unit functions are the
 // ones the separate operators call (the pdf arm of mf_eval_pdf, eval_one, merl_index_fast / merl_index, scale), so every float is the
 // one djb_evalp_batch and djb_pdf_batch produce; what is saved is the traffic -- 40 B per pair instead of 64 -- a launch and the
 // caller's guard pass.
@@ -15,6 +15,7 @@
 // Staging: what the PDF side of the proxy and the target's evalp need, no more: none of the sampler's tables (Beckmann's logf / powf
 // tables, qf of tabular, qf2 / qf1 of tabular_anisotropic).
 #include "djb_internal.hpp"
+#include "djb_worklist.hpp"
 
 using namespace djbdev;
 
@@ -26,68 +27,7 @@ constexpr int light_block(int pkind, int tkind) { return pkind == KIND_TABULAR_A
 // floats of table staging: what k_eval stages for the kind (p22 + sigma | both grids)
 constexpr int light_tab_lds(int pkind) { return pkind == KIND_TABULAR ? 3072 : pkind == KIND_TABULAR_ANISO ? 16384 : 0; }
 
-inline bool dense(const View &v) { return v.stride == 1; }
-
-// dense streams with the non-temporal hint, addressed as SGPR base + the lane's 32-bit byte offset taken through lane_byte_offset()
-// once per block of accesses (djb_device_units.inc).  The kernel uses them with a merl or utia target (OFFS): there load3_dense_nt's
-// addresses were kept as 64-bit values across the body (80 / 103 VGPRs against 63 / 85).  With an sgd or abc target it is the other
-// way round -- the opaque offset costs 121 / 73 VGPRs against 92 / 59 -- so those keep load3_dense_nt / store3_dense_nt.  Register
-// counts from the compiler's resource remarks; the two forms were not timed against each other.
-DJB_DEV v3 load3_dense_off_nt(const View &v, long long k0, unsigned int off)
-{
-	return mk(__builtin_nontemporal_load(dense_off(v.x + k0, off)), __builtin_nontemporal_load(dense_off(v.y + k0, off)),
-	          __builtin_nontemporal_load(dense_off(v.z + k0, off)));
-}
-DJB_DEV void store3_dense_off_nt(const View &v, long long k0, unsigned int off, v3 a)
-{
-	__builtin_nontemporal_store(a.x, dense_off(v.x + k0, off)); __builtin_nontemporal_store(a.y, dense_off(v.y + k0, off));
-	__builtin_nontemporal_store(a.z, dense_off(v.z + k0, off));
-}
-
-// ---- the per-wave queue of the pairs MERL's tier 1 declines, as in djb_kernels_merl_set.hip.  Fewer than 64 wait when an iteration
-// starts and an iteration adds at most 64 (one unit per lane).  One wave, in-order LDS: no barrier, no atomics.
-constexpr unsigned int QCAP = 128;
-constexpr int QW = 8;                                                              // {k lo, k hi, i.xyz, o.xyz}
-template <int W, unsigned int CAP>
-DJB_DEV void light_queue_push(unsigned int (&q)[W][CAP], unsigned int &qn, unsigned int lane, bool amb, const unsigned int (&rec)[W])
-{
-	const unsigned long long mask = __ballot(amb);
-	if (!mask) return;
-	if (amb) {
-		const unsigned int j = qn + (unsigned int)__popcll(mask & ((1ull << lane) - 1ull));
-#pragma unroll
-		for (int w = 0; w < W; ++w) q[w][j] = rec[w];
-	}
-	qn += (unsigned int)__popcll(mask);
-}
-// while a full wave of records waits -- or, on the last trip, any -- hand `finish` one record per lane
-template <int W, unsigned int CAP, class Finish>
-DJB_DEV void light_queue_drain(unsigned int (&q)[W][CAP], unsigned int &qn, unsigned int lane, bool last, Finish finish)
-{
-	while (qn >= 64u || (last && qn)) {
-		const unsigned int cnt = qn < 64u ? qn : 64u;
-		qn -= cnt;
-		__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-		__builtin_amdgcn_wave_barrier();
-		if (lane < cnt) {
-			unsigned int rec[W];
-#pragma unroll
-			for (int w = 0; w < W; ++w) rec[w] = q[w][qn + lane];
-			finish(rec);
-		}
-		__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-		__builtin_amdgcn_wave_barrier();
-	}
-}
-DJB_DEV void rec_pack(unsigned int *rec, long long k, v3 i, v3 o)
-{
-	rec[0] = (unsigned int)((unsigned long long)k & 0xffffffffull); rec[1] = (unsigned int)((unsigned long long)k >> 32);
-	rec[2] = __float_as_uint(i.x); rec[3] = __float_as_uint(i.y); rec[4] = __float_as_uint(i.z);
-	rec[5] = __float_as_uint(o.x); rec[6] = __float_as_uint(o.y); rec[7] = __float_as_uint(o.z);
-}
-DJB_DEV long long rec_k(const unsigned int *rec) { return (long long)(((unsigned long long)rec[1] << 32) | rec[0]); }
-DJB_DEV v3 rec_i(const unsigned int *rec) { return mk(__uint_as_float(rec[2]), __uint_as_float(rec[3]), __uint_as_float(rec[4])); }
-DJB_DEV v3 rec_o(const unsigned int *rec) { return mk(__uint_as_float(rec[5]), __uint_as_float(rec[6]), __uint_as_float(rec[7])); }
+constexpr int QW = 8;                                                              // the queue's record: {k lo, k hi, i.xyz, o.xyz}
 
 // DENSE: every view has stride 1 -- the 40 B/pair streams (i, o, fr, pdf) are touched once: non-temporal, so that they leave the L2 to
 // the table gathers
@@ -104,7 +44,7 @@ __global__ __launch_bounds__(light_block(PKIND, TKIND)) void k_evalp_pdf_proxy(B
 	__shared__ unsigned long long s_exp[EXPT ? 256 : 1];
 	__shared__ double s_pow[POWT ? 384 : 1];
 	__shared__ double s_atan[ATANT ? 16 : 1];
-	__shared__ unsigned int s_q[MERLQ ? BS / 64 : 1][QW][MERLQ ? QCAP : 1];
+	__shared__ unsigned int s_q[MERLQ ? BS / 64 : 1][QW][MERLQ ? RECQ_CAP : 1];
 	if (EXPT) pb.exp_lds = tb.exp_lds = glibc_exp_tab_to_lds(s_exp, threadIdx.x, BS);
 	if (POWT) tb.pow_lds = glibc_pow_tab_to_lds(s_pow, threadIdx.x, BS);
 	pb.atan_lds = tb.atan_lds = ATANT ? atan_tab_to_lds(s_atan, threadIdx.x) : 0u;
@@ -112,19 +52,14 @@ __global__ __launch_bounds__(light_block(PKIND, TKIND)) void k_evalp_pdf_proxy(B
 	__shared__ float s_tab[TAB_LDS ? TAB_LDS : 1];
 	if (TAB_LDS) {
 		int used = 0;
-		auto stage = [&](const float *&src, int count) {
-			if (src == nullptr || count <= 0 || used + count > TAB_LDS) return;     // a table that does not fit stays in global memory
-			float *dst = s_tab + used;
-			for (int k = threadIdx.x; k < count; k += BS) dst[k] = src[k];
-			src = dst; used += count;
-		};
+		auto stage = [&](const float *&src, int count) { stage_table<BS>(s_tab, used, src, count); };
 		if (PKIND == KIND_TABULAR) { stage(pb.p22, pb.n_p22); stage(pb.sigma, pb.n_sigma); }
 		if (PKIND == KIND_TABULAR_ANISO) { stage(pb.sigma, pb.elev * pb.azim); stage(pb.p22, pb.elev * pb.azim); }
 	}
 	if (EXPT || POWT || ATANT || TAB_LDS) __syncthreads();
 
 	const unsigned int t = threadIdx.x, wave = t >> 6, lane = t & 63u;
-	unsigned int (&q)[QW][MERLQ ? QCAP : 1] = s_q[MERLQ ? wave : 0];
+	unsigned int (&q)[QW][MERLQ ? RECQ_CAP : 1] = s_q[MERLQ ? wave : 0];
 	unsigned int qn = 0;                                                               // wave-uniform
 	const long long stride = (long long)gridDim.x * BS;
 	for (long long k0 = (long long)blockIdx.x * BS; ; k0 += stride) {                  // k0: workgroup-uniform; MERL: one extra trip flushes the queues
@@ -160,14 +95,12 @@ __global__ __launch_bounds__(light_block(PKIND, TKIND)) void k_evalp_pdf_proxy(B
 			if (!amb) { if (!DENSE) store3(vout, k, fr); else if (OFFS) store3_dense_off_nt(vout, k0, soff, fr); else store3_dense_nt(vout, k0, t, fr); }
 		}
 		if (MERLQ) {
-			// the record is built HERE, from values that live across the branches above (see k_merl_set_fast): packed inside the
-			// declining branch, the k word came out wrong in the generated code
-			unsigned int rec[QW];
-			rec_pack(rec, k, i, o);
-			light_queue_push(q, qn, lane, amb, rec);
-			light_queue_drain(q, qn, lane, last, [&](const unsigned int *r) {
-				const v3 iq = rec_i(r);
-				const MerlTexel tx = tb.merl[merl_index(iq, rec_o(r))];
+			unsigned int rec[QW];                                                      // built here, outside the branches above (djb_worklist.hpp)
+			rec_put_k(rec, k); rec_put_v3(rec, 2, i); rec_put_v3(rec, 5, o);
+			recq_push(q, qn, lane, amb, rec);
+			recq_drain(q, qn, lane, last, [&](const unsigned int *r) {
+				const v3 iq = rec_v3(r, 2);
+				const MerlTexel tx = tb.merl[merl_index(iq, rec_v3(r, 5))];
 				store3(vout, rec_k(r), scale(iq.z, mk(tx.x, tx.y, tx.z)));
 			});
 			if (last) break;
@@ -182,7 +115,7 @@ hipError_t launch_pair(hipStream_t s, const Brdf &pb, const Params &pp, const Br
 	constexpr int BS = light_block(PKIND, TKIND);
 	const MerlGuard g = MERL_GUARD_DEFAULT;
 	dim3 grid(djbk::grid_capped(n, BS, 256LL * 16 * 256 / BS)), block(BS);   // 16 workgroups of 256 per CU's worth, grid-stride beyond
-	if (dense(i) && dense(o) && dense(out_fr))
+	if (djbk::dense_strict(i) && djbk::dense_strict(o) && djbk::dense_strict(out_fr))
 		hipLaunchKernelGGL((k_evalp_pdf_proxy<PKIND, TKIND, true>), grid, block, 0, s, pb, pp, tb, tp, n, i, o, out_fr, out_pdf, g, merl_exact ? 1 : 0);
 	else
 		hipLaunchKernelGGL((k_evalp_pdf_proxy<PKIND, TKIND, false>), grid, block, 0, s, pb, pp, tb, tp, n, i, o, out_fr, out_pdf, g, merl_exact ? 1 : 0);

@@ -14,7 +14,6 @@ constexpr int BLOCK = 256;
 #endif
 
 constexpr long long GRID_CAP = 256LL * 64;   // 4 workgroups per CU resident, 16 rounds of them (2.58 ms per 1e8 pairs; 4096: 2.66, 1024: 2.94, one per tile: 2.75)
-inline bool dense(const View &v) { return v.stride == 1 || v.x == nullptr; }
 
 // utia::eval, two-tier.  Tier 1 (k_utia_v2) decides every pair it can with cheap arithmetic and lists the rest (the index of every pair
 // with an angle next to a float rounding boundary, a cell estimate next to a cell boundary, a guarded shortcut that wants its exact
@@ -189,7 +188,7 @@ hipError_t launch_utia_tt(hipStream_t s, const Brdf &b, long long n, const View 
 	hipError_t e = hipMemsetAsync(count, 0, 16, s);
 	if (e != hipSuccess) return e;
 	dim3 g(djbk::grid_capped(n, BLOCK, GRID_CAP)), t(BLOCK);
-	const bool dn = dense(i) && dense(o) && dense(out);
+	const bool dn = djbk::dense_or_null(i) && djbk::dense_or_null(o) && djbk::dense_or_null(out);
 	if (contract) {
 		if (dn) hipLaunchKernelGGL((k_utia_v2<WANT, true, true>), g, t, 0, s, b, n, i, o, out, out_pdf, list, cap, count);
 		else hipLaunchKernelGGL((k_utia_v2<WANT, true, false>), g, t, 0, s, b, n, i, o, out, out_pdf, list, cap, count);

@@ -1017,6 +1017,48 @@ djb_status merl_set_eval(djb_ctx *ctx, const void *texels, int n_mat, int64_t n,
 	});
 	return DJB_OK;
 }
+// ------------------------------------------------------------------ UTIA material sets: eval_one<KIND_UTIA> per hit on the record table the
+// hit's id selects (records = float4[n_mat][288 * 288 * 8]); an id outside [0, n_mat) is an inactive hit (+0, nothing read)
+djb_status utia_set_member(const djb_ctx *ctx, const djb_brdf *b, int index, const void **records)
+{
+	if (!b) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: utia set member %d is a null brdf", index);
+	if (!is_cpu(b) || B(b)->ctx != (const CpuCtx *)ctx)
+		return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: utia set member %d belongs to another context", index);
+	if (B(b)->dev.kind != KIND_UTIA || !B(b)->dev.utia)
+		return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: utia set member %d is not a utia brdf (kind %d)", index, B(b)->dev.kind);
+	*records = B(b)->dev.utia;
+	return DJB_OK;
+}
+template <int WANT>
+void utia_set_eval_loop(const float4 *tab, int n_mat, long long k0, long long k1, const int32_t *material, const View &vi, const View &vo, const View &vout)
+{
+	Brdf tb; memset(&tb, 0, sizeof tb); tb.kind = KIND_UTIA;
+	Params tp; memset(&tp, 0, sizeof tp);
+	for (long long k = k0; k < k1; ++k) {
+		v3 fr = mk(0, 0, 0); float unused_pdf = 0.0f;
+		const unsigned int m = (unsigned int)material[k];
+		if (m < (unsigned int)n_mat) {
+			tb.utia = tab + (size_t)m * 8 * (size_t)(UTIA_N / 3);
+			eval_one<KIND_UTIA, WANT>(tb, tp, load3(vi, k), load3(vo, k), fr, unused_pdf);
+		}
+		store3(vout, k, fr);
+	}
+}
+djb_status utia_set_eval(djb_ctx *ctx, const void *records, int n_mat, int64_t n, const int32_t *material, const djb_vec3_view *i,
+                         const djb_vec3_view *o, int want_cos, const djb_vec3_view *out_fr)
+{
+	if (n < 0) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: negative batch size");
+	if (!material) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null material array");
+	if (!valid(i) || !valid(o)) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null vec3 view");
+	if (!valid(out_fr)) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null output vec3 view");
+	const View vi = view_of(i), vo = view_of(o), vout = view_of(out_fr);
+	const float4 *tab = (const float4 *)records;
+	parallel_for(C(ctx), n, 4096, [&](long long k0, long long k1) {
+		if (want_cos) utia_set_eval_loop<2>(tab, n_mat, k0, k1, material, vi, vo, vout);
+		else utia_set_eval_loop<1>(tab, n_mat, k0, k1, material, vi, vo, vout);
+	});
+	return DJB_OK;
+}
 template <int PK>
 void merl_set_proxy_loop(const MerlTexel *tex, const Params *params, int n_mat, const Brdf &pb, long long k0, long long k1, const int32_t *material,
                          const float *u1a, const float *u2a, const View &vo, const View &vw_out, const View &vi_out, float *out_pdf)

@@ -104,6 +104,11 @@ djb_status merl_set_evalp_is_proxy(djb_ctx *, const void *texels, const void *pa
 djb_status merl_set_evalp_pdf(djb_ctx *, const void *texels, const void *params, int n_mat, const djb_brdf *proxy, int64_t n,
                               const int32_t *material, const djb_vec3_view *i, const djb_vec3_view *o, const djb_vec3_view *out_fr,
                               float *out_pdf);
+// UTIA material sets on the host (include/djb_hip.h: djb_utia_set).  records = float4[n_mat][288 * 288 * 8] in host memory; a hit whose id
+// is outside [0, n_mat) gets +0.  utia_set_member: the converted record table of a utia object of `ctx`, or the reason it is refused
+djb_status utia_set_member(const djb_ctx *ctx, const djb_brdf *b, int index, const void **records);
+djb_status utia_set_eval(djb_ctx *, const void *records, int n_mat, int64_t n, const int32_t *material, const djb_vec3_view *i,
+                         const djb_vec3_view *o, int want_cos, const djb_vec3_view *out_fr);
 djb_status eval_pp(djb_ctx *, const djb_brdf *, int64_t n, const djb_vec3_view *i, const djb_vec3_view *o, const float *rec,
                    int mode, const float *base5, float scale, int lean_flags, int want, const djb_vec3_view *out_fr, float *out_pdf,
                    float *out_pp);

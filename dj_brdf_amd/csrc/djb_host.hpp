@@ -134,6 +134,15 @@ struct djb_merl_set {
 	Params *params = nullptr;
 };
 
+// a UTIA material set (djb_utia_set.hip): the converted record tables of M utia objects in one block, float4[M][288 * 288 * 8], where the
+// set's context computes (HBM, or host memory for a CPU context).  Immutable after its constructor returned.
+struct djb_utia_set {
+	int device;                      // of the creating context, < 0: a CPU context's set (kept here: the handle may outlive its context)
+	djb_ctx *ctx;                    // the creating context: compared by the batch call
+	int n_mat = 0;
+	float4 *tab = nullptr;
+};
+
 namespace djbh {
 
 djb_status fail(djb_status st, const char *fmt, ...);     // sets the thread's djb_last_error() message (djb_host.hip)
@@ -377,6 +386,18 @@ inline djb_status stage_leanmap_coords(Staged &sg, const float *uv, const float 
 	src->uv = d;
 	src->lod = nullptr;
 	if (lod && (st = sg.in_f(lod, &src->lod)) != DJB_OK) return st;
+	return DJB_OK;
+}
+// material sets (djb_merl_set.hip, djb_utia_set.hip): the n material ids of a batch where the kernels read them
+inline djb_status stage_material(Staged &sg, const int32_t *material, const int32_t **out)
+{
+	if (!material) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null material array");
+	if (sg.mem == DJB_MEM_DEVICE) { *out = material; return DJB_OK; }
+	int32_t *d = nullptr;
+	djb_status st = sg.alloc(sizeof(int32_t) * (size_t)sg.n, (void **)&d);
+	if (st != DJB_OK) return st;
+	if (sg.n && (st = sg.copy(d, material, sizeof(int32_t) * (size_t)sg.n, hipMemcpyHostToDevice)) != DJB_OK) return st;
+	*out = d;
 	return DJB_OK;
 }
 // object construction helpers (djb_host.hip)

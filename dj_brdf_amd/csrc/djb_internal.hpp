@@ -134,6 +134,11 @@ hipError_t launch_gen_uniforms(hipStream_t s, long long n, uint32_t seed, unsign
 // sRGB power of the decode on the fast transcendentals, everything else (cells, weights, the 16-tap sums) the reference's bits
 hipError_t launch_utia_twotier(hipStream_t s, const Brdf &b, long long n, const View &i, const View &o, const View &out,
                                float *out_pdf, int want, unsigned int *list, unsigned int cap, unsigned int *count, bool contract);
+// UTIA material sets (djb_kernels_utia_set.hip): tab = float4[n_mat][288 * 288 * 8], material = n ids (outside [0, n_mat): an inactive hit,
+// +0); eval / evalp per hit with the two tiers of launch_utia_twotier (list / cap / count as there).  exact_only: the tier-2 kernel alone
+// on every hit (reads a hit before it writes it; list and count are not used)
+hipError_t launch_utia_set_eval(hipStream_t s, const float4 *tab, int n_mat, long long n, const int32_t *material, const View &i, const View &o,
+                                const View &out, bool want_cos, unsigned int *list, unsigned int cap, unsigned int *count, bool exact_only);
 hipError_t launch_fast_trig_selftest(hipStream_t s, long long n, int mode, uint32_t first, uint32_t seed, unsigned long long *counters4);
 // DJB_OPT_CONTRACT_1E5 (djb_kernels_contract.hip): GGX eval / evalp / pdf inside the 1e-5 value contract, two-tier like
 // the MERL lookup, with a sharded worklist (list: cap records of 32 bytes in total, count: CONTRACT_SHARDS uint32, CONTRACT_COUNTER_STRIDE words apart: the record

@@ -48,19 +48,6 @@ djb_status install_params(djb_merl_set *s, const std::vector<Params> &p)
 	return DJB_OK;
 }
 
-// the n material ids of a batch where the kernels read them
-djb_status stage_material(Staged &sg, const int32_t *material, const int32_t **out)
-{
-	if (!material) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null material array");
-	if (sg.mem == DJB_MEM_DEVICE) { *out = material; return DJB_OK; }
-	int32_t *d = nullptr;
-	djb_status st = sg.alloc(sizeof(int32_t) * (size_t)sg.n, (void **)&d);
-	if (st != DJB_OK) return st;
-	if (sg.n && (st = sg.copy(d, material, sizeof(int32_t) * (size_t)sg.n, hipMemcpyHostToDevice)) != DJB_OK) return st;
-	*out = d;
-	return DJB_OK;
-}
-
 } // namespace
 
 extern "C" {

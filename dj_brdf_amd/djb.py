@@ -1265,6 +1265,70 @@ class utia(brdf):
         return _get_samples(self)
 
 
+class utia_set:
+    """M UTIA materials resident in ONE block on their context's device: hits that land on many measured materials are evaluated in one
+    call, each hit naming its material by id (djb_utia_set, include/djb_hip.h).  An extension: the reference's objects are one material
+    each.  ``eval`` / ``evalp`` are all that dj_utia asks of its table (it samples the cosine hemisphere), so there is no proxy.
+
+    ``material``: int32 ids, one per hit; an id outside [0, M) marks an inactive hit (a dead path), whose output is +0.  An active
+    hit gets the bits of the single-material call on its material.  Arrays: numpy (host) or torch CUDA (device), in the layouts the
+    other operators take; the ids travel in the memory space of the directions."""
+
+    def __init__(self, brdfs, ctx: Optional[Context] = None):
+        brdfs = list(brdfs)
+        self.ctx = ctx or (brdfs[0].ctx if brdfs else default_context())
+        self._h = C.c_void_p()
+        ptrs = (C.c_void_p * max(len(brdfs), 1))(*[getattr(b._h, "value", None) for b in brdfs])
+        _lib.check(_lib.load().djb_utia_set_create(self.ctx._h, C.c_int(len(brdfs)), ptrs, C.byref(self._h)))
+
+    @classmethod
+    def from_tables(cls, tables, ctx: Optional[Context] = None):
+        """the set of ``utia.from_table(t)`` for every UTIA payload in ``tables`` (3 * 288 * 288 doubles each)"""
+        ctx = ctx or default_context()
+        members = [utia.from_table(t, ctx=ctx) for t in tables]
+        try:
+            return cls(members, ctx)
+        finally:
+            for b in members:                      # the set holds copies of their tables
+                b.close()
+
+    @property
+    def n_materials(self) -> int:
+        n = C.c_int()
+        _lib.check(_lib.load().djb_utia_set_info(self._h, C.byref(n)))
+        return n.value
+
+    def _eval(self, material, i, o, want_cos):
+        vi, vo = _Vec(i), _Vec(o)
+        if vi.n != vo.n or vi.mem != vo.mem:
+            raise exc(1, "djb_error: i and o must have the same length and memory space")
+        keep, mp = merl_set._ids(material, vi)
+        out = vi.like()
+        _lib.check(_lib.load().djb_utia_set_eval_batch(self.ctx._h, self._h, C.c_int64(vi.n), C.c_void_p(mp), C.byref(vi.view), C.byref(vo.view),
+                                                      C.c_int(want_cos), C.byref(out.view), C.c_int(vi.mem)))
+        del keep
+        return out.keep
+
+    def eval(self, material, i, o):
+        """f_r of material[k] at (i_k, o_k)"""
+        return self._eval(material, i, o, 0)
+
+    def evalp(self, material, i, o):
+        """f_r * cos(theta_i) of material[k] at (i_k, o_k)"""
+        return self._eval(material, i, o, 1)
+
+    def close(self):
+        if self._h:
+            _lib.load().djb_utia_set_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # --------------------------------------------------------------------------- user-defined BRDFs (dj_brdf.h:74-109)
 def fit_query_dirs(resolution: int):
     """The (i, o) pairs at which ``tabular(src, resolution)`` evaluates its source, in the reference's call order

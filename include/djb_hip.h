@@ -73,7 +73,10 @@ extern "C" {
  *        Additive under 235, no existing entry changed: djb_merl_set_evalp_pdf_proxy_batch (the light-sample step on a MERL set: evalp of
  *        the hit's material and the proxy's pdf with the hit's parameters for a given pair, one call).
  *        Additive under 235, no existing entry changed: djb_evalp_pdf_proxy_batch (the light-sample step on a single merl / utia / sgd /
- *        abc object: evalp of the target and the proxy's pdf for a given pair, guarded, one call). */
+ *        abc object: evalp of the target and the proxy's pdf for a given pair, guarded, one call).
+ *        Additive under 235, no existing entry changed: UTIA material sets -- djb_utia_set, DJB_UTIA_SET_MAX, djb_utia_set_create,
+ *        djb_utia_set_info, djb_utia_set_destroy, djb_utia_set_eval_batch (eval / evalp of hits on M resident UTIA tables by per-hit
+ *        material id, one call). */
 #define DJB_HIP_VERSION 235
 #define DJB_HIP_VERSION_MAJOR(v) ((v) / 100)
 
@@ -112,6 +115,7 @@ typedef struct djb_ctx djb_ctx;     /* one GPU + one HIP stream */
 typedef struct djb_brdf djb_brdf;   /* an immutable BRDF object resident in HBM (djb::brdf subclass) */
 typedef struct djb_leanmap djb_leanmap;   /* an immutable LEAN map (mip pyramid of slope moments) resident in HBM */
 typedef struct djb_merl_set djb_merl_set; /* M MERL tables in one resident block + one proxy parameter set per material */
+typedef struct djb_utia_set djb_utia_set; /* M UTIA record tables in one resident block */
 
 typedef struct { float *x, *y, *z; int64_t stride; } djb_vec3_view;
 
@@ -570,6 +574,37 @@ djb_status djb_merl_set_evalp_is_proxy_batch(djb_ctx *, const djb_merl_set *, co
 djb_status djb_merl_set_evalp_pdf_proxy_batch(djb_ctx *, const djb_merl_set *, const djb_brdf *proxy, int64_t n,
                                               const int32_t *material, const djb_vec3_view *i, const djb_vec3_view *o,
                                               const djb_vec3_view *out_fr, float *out_pdf, int mem);
+
+/* ---- UTIA material sets: djb_merl_set's answer for the other tabulated family.  The cells, angles, weights and tap order of a UTIA
+ * look-up depend on (i, o) alone, never on the material: they are computed once per hit and only the base of the hit's two 128-byte
+ * records moves with its id.  mitsuba/dj_utia.cpp asks its table for eval and evalp alone (its sampling is the cosine hemisphere, whose
+ * pdf i.z / pi needs no table): a set with eval / evalp is the whole plugin per hit.  There is no proxy and no parameter block.
+ *
+ * Creation.  djb_utia_set_create copies the converted record tables of n_materials utia objects into ONE contiguous block,
+ * float4[M][288 * 288 * 8] (10 616 832 bytes per material, allocated once).  Every source object must be a utia object of the call's
+ * context (any other kind or context: DJB_ERR_INVALID_ARGUMENT); the same handle may appear more than once.  On a GPU context the copies
+ * are device-to-device on the context's stream, and the sources may be destroyed as soon as create returns.  The set belongs to its
+ * context as a djb_brdf does and may be destroyed after it.  1 <= M <= DJB_UTIA_SET_MAX: with that cap the byte offset of any record
+ * chunk stays below 2^32 (it passes 2^31: formed unsigned), which keeps the kernels' uniform-base + 32-bit-offset addressing.
+ *
+ * material: n int32 values in the memory space `mem` names.  A hit with 0 <= material[k] < M gets, bit for bit, what djb_eval_batch
+ * (djb_evalp_batch when want_cos != 0) returns for unit k's inputs on material m.  A hit whose id is outside [0, M) is INACTIVE: out_fr
+ * of that hit is +0.0f and no table entry is read for it -- how a renderer marks dead paths: a defined input, not an error.
+ *
+ * Options.  DJB_OPT_UTIA_EXACT_ONLY sends every active hit through the exact kernel alone, as for the single-material call, and so does
+ * a device-memory call whose output arrays overlap an input array, the ids included (index-aligned in-place views are the only
+ * supported overlap).  DJB_OPT_TEST_WORKLIST_CAP is honoured.  DJB_OPT_CONTRACT_1E5 changes nothing: a set has no contract-mode
+ * kernels, every active hit has the reference's bits.  CPU contexts serve the call with the host instantiation of the same per-unit
+ * code.  On a GPU context a device-memory batch is one hipMemsetAsync and two kernel launches per 2^31 hits, with no
+ * host read-back and no allocation once the context's worklist scratch has its size (n / 256 + 4096 entries: after one call of that
+ * size it can be captured into a hipGraph); a host-memory batch of any size is staged through HBM (a set has no host twin). */
+#define DJB_UTIA_SET_MAX 256
+djb_status djb_utia_set_create(djb_ctx *, int n_materials, const djb_brdf *const *utias, djb_utia_set **out);
+djb_status djb_utia_set_info(const djb_utia_set *, int *n_materials);
+djb_status djb_utia_set_destroy(djb_utia_set *);
+djb_status djb_utia_set_eval_batch(djb_ctx *, const djb_utia_set *, int64_t n, const int32_t *material,
+                                   const djb_vec3_view *i, const djb_vec3_view *o, int want_cos,
+                                   const djb_vec3_view *out_fr, int mem);
 
 /* beckmann::lrep algebra on {E1..E5} (host scalars; dj_brdf.h:330-356, 1959-2051).  b may be NULL
  * (= the default lrep(0,0,1,1,0)); x (and y) are the scalar arguments of mul / shear / scale.

@@ -585,6 +585,9 @@ class utia : public brdf {
 public:
 	utia(const char *filename, hip::context *c = NULL) : brdf(c)
 	{ checked(djb_brdf_create_utia_from_file(ctx(), filename, &m_h)); }
+	/* the file's payload in memory: 3 * 288 * 288 doubles, planes R, G, B (an extension, as merl's) */
+	explicit utia(const double *samples, hip::context *c = NULL) : brdf(c)
+	{ checked(djb_brdf_create_utia_from_memory(ctx(), samples, &m_h)); }
 	const std::vector<double> &get_samples() const { return hip::fetch_samples(m_h, m_samples); }   // dj_brdf.h:143
 	DJB_HIP_RESIDENT_EVAL
 private:
@@ -1333,6 +1336,39 @@ private:
 	djb_ctx *ctx() const { return (m_ctx ? *m_ctx : hip::context::standard()).get(); }
 	hip::context *m_ctx;
 	djb_merl_set *m_h;
+};
+
+/* M UTIA materials resident in one block on their context's device (include/djb_hip.h, djb_utia_set): each hit names its material by
+ * id and the whole batch is one call.  An extension with no counterpart in the reference.  eval / evalp are all that dj_utia asks of
+ * its table (mitsuba/dj_utia.cpp samples the cosine hemisphere): no proxy, no parameters.  An id outside [0, size()) marks an inactive
+ * hit: its output is +0.  An active hit gets the bits of utia::eval / evalp on its material. */
+class utia_set {
+public:
+	/* the record tables of n utia objects are copied: the objects may be destroyed afterwards */
+	utia_set(size_t n, const utia *const *materials, hip::context *c = NULL) : m_ctx(c), m_h(NULL)
+	{
+		std::vector<const djb_brdf *> h(n);
+		for (size_t k = 0; k < n; ++k) h[k] = materials[k] ? materials[k]->handle() : NULL;
+		hip::check(djb_utia_set_create(ctx(), (int)n, h.data(), &m_h));
+	}
+	~utia_set() { djb_utia_set_destroy(m_h); }
+	utia_set(utia_set &&o) noexcept : m_ctx(o.m_ctx), m_h(o.m_h) { o.m_h = NULL; }
+	utia_set &operator=(utia_set &&o) noexcept { if (this != &o) { djb_utia_set_destroy(m_h); m_ctx = o.m_ctx; m_h = o.m_h; o.m_h = NULL; } return *this; }
+	utia_set(const utia_set &) = delete;
+	utia_set &operator=(const utia_set &) = delete;
+	const djb_utia_set *get() const { return m_h; }
+	int size() const { int v; hip::check(djb_utia_set_info(m_h, &v)); return v; }
+	// ---- host arrays
+	void eval(size_t n, const int32_t *material, const vec3 *i, const vec3 *o, vec3 *out) const { eval_views((int64_t)n, material, hip::view(i), hip::view(o), hip::view(out), 0, DJB_MEM_HOST); }
+	void evalp(size_t n, const int32_t *material, const vec3 *i, const vec3 *o, vec3 *out) const { eval_views((int64_t)n, material, hip::view(i), hip::view(o), hip::view(out), 1, DJB_MEM_HOST); }
+	// ---- views (SoA or strided), in host memory or in HBM (mem = DJB_MEM_DEVICE: asynchronous on the context's stream)
+	void eval_views(int64_t n, const int32_t *material, const djb_vec3_view &i, const djb_vec3_view &o, const djb_vec3_view &out,
+	                int want_cos, int mem) const
+	{ hip::check(djb_utia_set_eval_batch(ctx(), m_h, n, material, &i, &o, want_cos, &out, mem)); }
+private:
+	djb_ctx *ctx() const { return (m_ctx ? *m_ctx : hip::context::standard()).get(); }
+	hip::context *m_ctx;
+	djb_utia_set *m_h;
 };
 
 } // namespace djb

@@ -1059,6 +1059,60 @@ djb_status utia_set_eval(djb_ctx *ctx, const void *records, int n_mat, int64_t n
 	});
 	return DJB_OK;
 }
+// ------------------------------------------------------------------ SGD / ABC model sets: eval_one<KIND_SGD / KIND_ABC> per hit on a Brdf whose
+// `model` is the row the hit's id selects and whose Fresnel operands are create_model's for that row (rows = double[n_mat][33 or 9]); an id
+// outside [0, n_mat) is an inactive hit (+0, nothing read)
+djb_status model_set_member(const djb_ctx *ctx, const djb_brdf *b, int index, int *kind, const double **row)
+{
+	if (!b) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: model set member %d is a null brdf", index);
+	if (!is_cpu(b) || B(b)->ctx != (const CpuCtx *)ctx)
+		return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: model set member %d belongs to another context", index);
+	const int k = B(b)->dev.kind;
+	if ((k != KIND_SGD && k != KIND_ABC) || B(b)->model.size() != (size_t)(k == KIND_SGD ? 33 : 9))
+		return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: model set member %d is not an sgd or abc brdf (kind %d)", index, k);
+	*kind = k;
+	*row = B(b)->model.data();
+	return DJB_OK;
+}
+template <int KIND, int WANT>
+void model_set_eval_loop(const double *rows, int n_mat, long long k0, long long k1, const int32_t *material, const View &vi, const View &vo, const View &vout)
+{
+	constexpr int STRIDE = KIND == KIND_SGD ? 33 : 9;
+	Brdf tb; memset(&tb, 0, sizeof tb); tb.kind = KIND;
+	tb.fr.kind = KIND == KIND_SGD ? FR_SGD : FR_UNPOLARIZED;
+	Params tp; memset(&tp, 0, sizeof tp);
+	for (long long k = k0; k < k1; ++k) {
+		v3 fr = mk(0, 0, 0); float unused_pdf = 0.0f;
+		const unsigned int m = (unsigned int)material[k];
+		if (m < (unsigned int)n_mat) {
+			const double *row = rows + (size_t)m * STRIDE;
+			tb.model = row;
+			if (KIND == KIND_SGD) { for (int c = 0; c < 3; ++c) { tb.fr.a[c] = (float)row[12 + c]; tb.fr.b[c] = (float)row[15 + c]; } }
+			else { for (int c = 0; c < 3; ++c) tb.fr.a[c] = (float)row[8]; }
+			eval_one<KIND, WANT>(tb, tp, load3(vi, k), load3(vo, k), fr, unused_pdf);
+		}
+		store3(vout, k, fr);
+	}
+}
+djb_status model_set_eval(djb_ctx *ctx, int kind, const double *rows, int n_mat, int64_t n, const int32_t *material, const djb_vec3_view *i,
+                          const djb_vec3_view *o, int want_cos, const djb_vec3_view *out_fr)
+{
+	if (n < 0) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: negative batch size");
+	if (!material) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null material array");
+	if (!valid(i) || !valid(o)) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null vec3 view");
+	if (!valid(out_fr)) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null output vec3 view");
+	const View vi = view_of(i), vo = view_of(o), vout = view_of(out_fr);
+	parallel_for(C(ctx), n, 4096, [&](long long k0, long long k1) {
+		if (kind == KIND_SGD) {
+			if (want_cos) model_set_eval_loop<KIND_SGD, 2>(rows, n_mat, k0, k1, material, vi, vo, vout);
+			else model_set_eval_loop<KIND_SGD, 1>(rows, n_mat, k0, k1, material, vi, vo, vout);
+		} else {
+			if (want_cos) model_set_eval_loop<KIND_ABC, 2>(rows, n_mat, k0, k1, material, vi, vo, vout);
+			else model_set_eval_loop<KIND_ABC, 1>(rows, n_mat, k0, k1, material, vi, vo, vout);
+		}
+	});
+	return DJB_OK;
+}
 template <int PK>
 void merl_set_proxy_loop(const MerlTexel *tex, const Params *params, int n_mat, const Brdf &pb, long long k0, long long k1, const int32_t *material,
                          const float *u1a, const float *u2a, const View &vo, const View &vw_out, const View &vi_out, float *out_pdf)

@@ -109,6 +109,11 @@ djb_status merl_set_evalp_pdf(djb_ctx *, const void *texels, const void *params,
 djb_status utia_set_member(const djb_ctx *ctx, const djb_brdf *b, int index, const void **records);
 djb_status utia_set_eval(djb_ctx *, const void *records, int n_mat, int64_t n, const int32_t *material, const djb_vec3_view *i,
                          const djb_vec3_view *o, int want_cos, const djb_vec3_view *out_fr);
+// SGD / ABC model sets on the host (include/djb_hip.h: djb_model_set).  rows = double[n_mat][33 (sgd) or 9 (abc)] in host memory; a hit whose
+// id is outside [0, n_mat) gets +0.  model_set_member: kind and row of an sgd / abc object of `ctx`, or the reason it is refused
+djb_status model_set_member(const djb_ctx *ctx, const djb_brdf *b, int index, int *kind, const double **row);
+djb_status model_set_eval(djb_ctx *, int kind, const double *rows, int n_mat, int64_t n, const int32_t *material, const djb_vec3_view *i,
+                          const djb_vec3_view *o, int want_cos, const djb_vec3_view *out_fr);
 djb_status eval_pp(djb_ctx *, const djb_brdf *, int64_t n, const djb_vec3_view *i, const djb_vec3_view *o, const float *rec,
                    int mode, const float *base5, float scale, int lean_flags, int want, const djb_vec3_view *out_fr, float *out_pdf,
                    float *out_pp);

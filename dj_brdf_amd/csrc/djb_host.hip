@@ -755,6 +755,7 @@ try {
 		ctx->ct_key = 0; ctx->ct_key_share = 0.0; ctx->ct_hopeless_calls = 0; ctx->wl_note_key = 0;
 		return DJB_OK;
 	}
+	if (option == DJB_OPT_MODEL_SET_ROWS_GLOBAL) { ctx->model_set_rows_global = value != 0; return DJB_OK; }
 	if (option == DJB_OPT_TEST_WORKLIST_CAP) { ctx->test_worklist_cap = value; return DJB_OK; }
 	return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: unknown option %d", option);
 }

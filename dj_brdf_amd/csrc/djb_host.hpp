@@ -57,6 +57,7 @@ struct djb_ctx {
 	double wl_last_share = 0.0;            // tier-2 pairs / pairs of the last large two-tier call
 	unsigned long long wl_note_key = 0, ct_key = 0; double ct_key_share = 0.0;   // contract mode: (lobe, params) of that call and its share
 	unsigned int ct_hopeless_calls = 0;        // calls answered by the exact kernel because of ct_key_share: every 16th re-probes
+	int model_set_rows_global = 0;   // DJB_OPT_MODEL_SET_ROWS_GLOBAL: model-set kernels read their rows from global memory whatever M is (tests, A/B timing)
 	long long test_worklist_cap = -1;   // DJB_OPT_TEST_WORKLIST_CAP (tests): >= 0 overrides the tier-2 worklist capacity
 	int contract_1e5 = 0;      // DJB_OPT_CONTRACT_1E5: dense GGX eval batches run the two-tier value-contract kernels
 	std::atomic<long long> host_batch_max{DJB_SCALAR_HOST_MAX};   // DJB_OPT_HOST_BATCH_MAX: host-array calls up to this size are answered by the host twin
@@ -141,6 +142,17 @@ struct djb_utia_set {
 	djb_ctx *ctx;                    // the creating context: compared by the batch call
 	int n_mat = 0;
 	float4 *tab = nullptr;
+};
+
+// an SGD / ABC model set (djb_model_set.hip): M parameter rows of one kind in one block where the set's context computes.  GPU context:
+// double[M][stride] in HBM, each row as create_model uploads the single one (sgd: 61 doubles, abc: 9).  CPU context: the rows as given,
+// double[M][33 or 9] in host memory.  Immutable after its constructor returned.
+struct djb_model_set {
+	int device;                      // of the creating context, < 0: a CPU context's set (kept here: the handle may outlive its context)
+	djb_ctx *ctx;                    // the creating context: compared by the batch call
+	int kind = 0;                    // DJB_KIND_SGD or DJB_KIND_ABC
+	int n_mat = 0;
+	double *rows = nullptr;
 };
 
 namespace djbh {
@@ -388,7 +400,7 @@ inline djb_status stage_leanmap_coords(Staged &sg, const float *uv, const float 
 	if (lod && (st = sg.in_f(lod, &src->lod)) != DJB_OK) return st;
 	return DJB_OK;
 }
-// material sets (djb_merl_set.hip, djb_utia_set.hip): the n material ids of a batch where the kernels read them
+// material sets (djb_merl_set.hip, djb_utia_set.hip, djb_model_set.hip): the n material ids of a batch where the kernels read them
 inline djb_status stage_material(Staged &sg, const int32_t *material, const int32_t **out)
 {
 	if (!material) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null material array");

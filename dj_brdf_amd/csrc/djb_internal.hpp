@@ -139,6 +139,12 @@ hipError_t launch_utia_twotier(hipStream_t s, const Brdf &b, long long n, const 
 // on every hit (reads a hit before it writes it; list and count are not used)
 hipError_t launch_utia_set_eval(hipStream_t s, const float4 *tab, int n_mat, long long n, const int32_t *material, const View &i, const View &o,
                                 const View &out, bool want_cos, unsigned int *list, unsigned int cap, unsigned int *count, bool exact_only);
+// SGD / ABC model sets (djb_kernels_model_set.hip): rows = double[n_mat][model_set_row_stride(kind)] as create_model builds the single row
+// (sgd: the 33 doubles + the fast tier's constants, abc: the 9 doubles), material = n ids (outside [0, n_mat): an inactive hit, +0); eval /
+// evalp per hit, one launch.  rows_global: read the rows from global memory whatever n_mat is (DJB_OPT_MODEL_SET_ROWS_GLOBAL)
+int model_set_row_stride(int kind);
+hipError_t launch_model_set_eval(hipStream_t s, int kind, const double *rows, int n_mat, bool rows_global, long long n, const int32_t *material,
+                                 const View &i, const View &o, const View &out, bool want_cos);
 hipError_t launch_fast_trig_selftest(hipStream_t s, long long n, int mode, uint32_t first, uint32_t seed, unsigned long long *counters4);
 // DJB_OPT_CONTRACT_1E5 (djb_kernels_contract.hip): GGX eval / evalp / pdf inside the 1e-5 value contract, two-tier like
 // the MERL lookup, with a sharded worklist (list: cap records of 32 bytes in total, count: CONTRACT_SHARDS uint32, CONTRACT_COUNTER_STRIDE words apart: the record

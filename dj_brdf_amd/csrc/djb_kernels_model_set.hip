@@ -1,0 +1,151 @@
+// djb_kernels_model_set.hip -- SGD / ABC model sets: a batch of hits that lands on M resident parameter rows of ONE kind, eval / evalp per hit.
+//
+// For the single-material kernels (k_eval<KIND_SGD / KIND_ABC>, djb_kernels_eval.hip) the row is launch-uniform: b.model is one pointer,
+// its doubles are scalar loads and SGPR operands.  Here the row moves with the hit's id, so every coefficient is per-lane data: a load
+// per use (ds_read_b64 from the copy in LDS, global_load_dwordx2 otherwise) into a VGPR pair.  Nothing else changes:
+//   k_model_set<KIND, WANT, DENSE>   KIND sgd / abc, WANT 1 eval / 2 evalp: one hit per lane, k_eval's loop shape, k_eval's staged tables
+//                                    (exp and pow, the arctangent core's for sgd), eval_one<KIND, WANT> -- the function k_eval calls -- on a
+//                                    lane-private Brdf whose `model` is the hit's row and whose Fresnel operands are that row's
+// so an active hit has the bits of the single-material call.  The path was read for launch-uniform assumptions: sgd_g1_rgb / sgd_ndf_rgb
+// branch on m[SGD_FAST_FLAG] (now a divergent branch: a wave that mixes rows runs both sides, each lane its own), fresnel_eval tests
+// a[0] == a[1] == a[2] per lane, the fma_sk addends are literals, fdiv_r is not on this path, and nothing reads a row value from one lane.
+// A translation unit of its own: the code of k_eval does not move with this one.
+//
+// rows = double[M][STRIDE], built on the host exactly as create_model builds the single row (djb_model_set.hip): STRIDE = SGD_FAST_ROW
+// = 61 for sgd (the 33 doubles, then the constants of the decided fast tier; [33] = 0 for a row outside that tier's domain), 9 for abc.
+// Both strides are odd: rows start 2 (mod 4) banks apart for the 64-bank ds_read_b64, so lanes that read one coefficient of different
+// rows spread over 32 bank pairs.  The byte offset material * STRIDE * 8 is below 2^25 at DJB_MODEL_SET_MAX = 65536: 32-bit offsets.
+// The Fresnel operands are converted per lane, (float)row[12 + c] / (float)row[15 + c] (sgd) and (float)row[8] (abc): create_model's conversions.
+//
+// Rows in LDS.  When M <= rows_lds(KIND) the workgroup copies the block into (dynamic) LDS once and the lanes read their coefficients from
+// there; the launch asks for M * STRIDE * 8 bytes, so a small set costs no occupancy.  The budget is what the kind's occupancy leaves of
+// the CU's 160 KiB next to the staged tables (5248 B sgd, 5128 B abc):
+//   sgd  its 124 / 127 VGPRs allow 4 waves per SIMD (k_eval<SGD> runs 5 at 87) = 4 workgroups per CU up to 73 rows of 488 B; the budget
+//        is 101 rows = 3 workgroups per CU (54613 B each, 49365 B for rows), so that the 100 published rows fit: measured at M = 100,
+//        random ids, 4.42 ms per 1e8 hits from LDS at 3 workgroups against 7.49 ms from global memory at 4
+//   abc  8 waves per SIMD (as k_eval<ABC>) = 8 workgroups per CU: 20480 B each, 15352 B for rows = 213 rows of 72 B
+// Larger sets, and every set under DJB_OPT_MODEL_SET_ROWS_GLOBAL, read their rows from global memory (L2 / Infinity-Cache resident): 15-50 %
+// slower where both were measured.  The branch is workgroup-uniform (a kernel argument); each side is eval_one inlined with pointers of
+// one address space (ds_read_b64 / global_load_dwordx2 with the set's base in SGPRs; no flat loads).
+//
+// A hit whose id is outside [0, M) is inactive, as is a lane past the end of the batch: +0.0f in the three outputs (nothing, past the
+// end), no address formed from its id, no row read; a wave without an active lane skips the arithmetic.  Every lane reads its hit before
+// it writes it: index-aligned in-place calls are supported.  Streams are non-temporal: 4 (id) + 24 + 12 = 40 B per hit.
+#include "djb_internal.hpp"
+#include <string.h>
+
+using namespace djbdev;
+
+namespace {
+
+constexpr int BLOCK = 256;
+constexpr long long GRID_CAP = 256LL * 16;                 // as k_eval for these kinds (djb_kernels_eval.hip)
+
+constexpr int row_stride(int kind) { return kind == KIND_SGD ? (int)SGD_FAST_ROW : 9; }                 // doubles per resident row
+constexpr int rows_lds(int kind) { return kind == KIND_SGD ? 101 : 213; }                                 // the LDS budget, in rows (above)
+// Registers (tools/kernel_resources.sh, profiles/model_set/kernel_resources.txt): the coefficients that k_eval holds in SGPRs are VGPR pairs
+// here.  sgd: 124 (dense) / 127 (strided) VGPRs against k_eval<SGD>'s 87 / 73 -- 4 waves per SIMD instead of 5 / 6, no scratch; abc: 64 (dense,
+// 8 waves, k_eval<ABC>: 57) / 70 (strided: 7 waves, k_eval<ABC>: 61 -- at the hint 8 the strided form kept 32 bytes of scratch).  The dense
+// accesses take their lane offset through lane_byte_offset(): with load3_dense_nt the sgd kernel kept 64-bit addresses across the body
+// (48 bytes of scratch at 128 VGPRs).
+constexpr int min_waves(int kind) { return kind == KIND_SGD ? 4 : 7; }
+static_assert(2048 + 3072 + 128 + 8 * rows_lds(KIND_SGD) * row_stride(KIND_SGD) <= 163840 / 3, "sgd: three workgroups per CU");
+static_assert(2048 + 3072 + 8 + 8 * rows_lds(KIND_ABC) * row_stride(KIND_ABC) <= 163840 / 8, "abc: eight workgroups per CU");
+static_assert(65536ull * 8ull * (unsigned long long)row_stride(KIND_SGD) < (1ull << 31), "the byte offset of the last row fits 32 bits");
+
+// one active hit: the hit's row becomes the lane's Brdf -- `model` and the Fresnel operands create_model derives from the row
+template <int KIND, int WANT>
+DJB_DEV void unit(Brdf b, const double *m, v3 i, v3 o, v3 &fr)
+{
+	b.model = m;
+	b.fr.kind = KIND == KIND_SGD ? FR_SGD : FR_UNPOLARIZED;      // a compile-time constant here: fresnel_eval's switch folds to the kind's term
+	if (KIND == KIND_SGD) {
+#pragma unroll
+		for (int c = 0; c < 3; ++c) { b.fr.a[c] = (float)m[12 + c]; b.fr.b[c] = (float)m[15 + c]; }
+	} else b.fr.a[0] = b.fr.a[1] = b.fr.a[2] = (float)m[8];
+	const Params none = {};
+	float pdf = 0.0f;
+	eval_one<KIND, WANT>(b, none, i, o, fr, pdf);
+}
+
+template <int KIND, int WANT, bool DENSE>
+__global__ __launch_bounds__(BLOCK, min_waves(KIND)) void k_model_set(Brdf b, const double *rows, int n_mat, int in_lds, long long n, const int32_t *mat,
+                                                                      View vi, View vo, View vout)
+{
+	constexpr unsigned int STRIDE = (unsigned int)row_stride(KIND);
+	__shared__ unsigned long long s_exp[256];
+	__shared__ double s_pow[384];
+	__shared__ double s_atan[KIND == KIND_SGD ? 16 : 1];
+	extern __shared__ double s_rows[];                                            // n_mat * STRIDE doubles when in_lds, else none (launch_set)
+	b.exp_lds = glibc_exp_tab_to_lds(s_exp, threadIdx.x, BLOCK);
+	b.pow_lds = glibc_pow_tab_to_lds(s_pow, threadIdx.x, BLOCK);
+	b.atan_lds = KIND == KIND_SGD ? atan_tab_to_lds(s_atan, threadIdx.x) : 0u;
+	if (in_lds) {                                                                 // n_mat <= rows_lds(KIND): the launcher's test
+		const unsigned int count = (unsigned int)n_mat * STRIDE;
+		for (unsigned int j = threadIdx.x; j < count; j += BLOCK) s_rows[j] = rows[j];
+	}
+	__syncthreads();
+	const long long stride = (long long)gridDim.x * BLOCK;
+	const unsigned int t = threadIdx.x;
+	for (long long k0 = (long long)blockIdx.x * BLOCK; k0 < n; k0 += stride) {     // k0: workgroup-uniform
+		const long long k = k0 + t;
+		const bool live = k < n;
+		bool act = false;
+		unsigned int id = 0u;
+		v3 i = mk(0, 0, 1), o = mk(0, 0, 1);
+		if (live) {                                                                // 40 B per hit, touched once: non-temporal
+			const unsigned int raw = (unsigned int)__builtin_nontemporal_load(mat + k);
+			const unsigned int toff = lane_byte_offset(t);                          // SGPR base + the lane's 32-bit offset (note below)
+			i = DENSE ? load3_dense_off_nt(vi, k0, toff) : load3(vi, k); o = DENSE ? load3_dense_off_nt(vo, k0, toff) : load3(vo, k);
+			act = raw < (unsigned int)n_mat;                                        // negative ids are >= 2^31 as unsigned
+			id = act ? raw : 0u;
+		}
+		v3 fr = mk(0, 0, 0);                                                       // an inactive hit: +0
+		if (__ballot(act) != 0ull) {                                               // wave-uniform: a wave of dead hits computes nothing
+			if (act) {
+				if (in_lds) unit<KIND, WANT>(b, s_rows + id * STRIDE, i, o, fr);                            // workgroup-uniform: ds_read_b64 ...
+				else unit<KIND, WANT>(b, (const double *)((const char *)rows + (size_t)(id * (STRIDE * 8u))), i, o, fr);   // ... or uniform base + 32-bit byte offset
+			}
+		}
+		if (live) { if (DENSE) store3_dense_off_nt(vout, k0, lane_byte_offset(t), fr); else store3(vout, k, fr); }
+	}
+}
+
+template <int KIND, int WANT>
+hipError_t launch_set(hipStream_t s, const double *rows, int n_mat, bool rows_global, long long n, const int32_t *mat, const View &i, const View &o,
+                      const View &out)
+{
+	Brdf b;
+	memset(&b, 0, sizeof b);
+	b.kind = KIND;
+	b.fr.kind = KIND == KIND_SGD ? FR_SGD : FR_UNPOLARIZED;
+	const int in_lds = !rows_global && n_mat <= rows_lds(KIND);
+	const size_t lds = in_lds ? sizeof(double) * (size_t)n_mat * (size_t)row_stride(KIND) : 0;      // dynamic: a small set costs no occupancy
+	dim3 g(djbk::grid_capped(n, BLOCK, GRID_CAP)), t(BLOCK);
+	if (djbk::dense_strict(i) && djbk::dense_strict(o) && djbk::dense_strict(out))
+		hipLaunchKernelGGL((k_model_set<KIND, WANT, true>), g, t, lds, s, b, rows, n_mat, in_lds, n, mat, i, o, out);
+	else
+		hipLaunchKernelGGL((k_model_set<KIND, WANT, false>), g, t, lds, s, b, rows, n_mat, in_lds, n, mat, i, o, out);
+	return hipGetLastError();
+}
+
+} // namespace
+
+namespace djbk {
+
+int model_set_row_stride(int kind) { return row_stride(kind); }
+
+hipError_t launch_model_set_eval(hipStream_t s, int kind, const double *rows, int n_mat, bool rows_global, long long n, const int32_t *material,
+                                 const View &i, const View &o, const View &out, bool want_cos)
+{
+	if (n <= 0) return hipSuccess;
+	if (kind == KIND_SGD)
+		return want_cos ? launch_set<KIND_SGD, 2>(s, rows, n_mat, rows_global, n, material, i, o, out)
+		                : launch_set<KIND_SGD, 1>(s, rows, n_mat, rows_global, n, material, i, o, out);
+	if (kind == KIND_ABC)
+		return want_cos ? launch_set<KIND_ABC, 2>(s, rows, n_mat, rows_global, n, material, i, o, out)
+		                : launch_set<KIND_ABC, 1>(s, rows, n_mat, rows_global, n, material, i, o, out);
+	return hipErrorInvalidValue;
+}
+
+} // namespace djbk

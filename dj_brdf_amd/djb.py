@@ -1329,6 +1329,102 @@ class utia_set:
             pass
 
 
+class model_set:
+    """M sgd or abc materials -- parameter rows of ONE kind -- resident in ONE block on their context's device: hits that land on many
+    data-driven materials are evaluated in one call, each hit naming its material by id (djb_model_set, include/djb_hip.h).  An extension:
+    the reference's objects are one material each.  ``eval`` / ``evalp`` are all that dj_sgd / dj_abc ask of their object (they sample
+    the cosine hemisphere), so there is no proxy.
+
+    ``model_set(brdfs)``: the rows of ``djb.sgd`` or ``djb.abc`` objects (all of one kind); ``from_rows`` / ``from_names`` take the rows
+    themselves or the published names.  ``material``: int32 ids, one per hit; an id outside [0, M) marks an inactive hit (a dead path),
+    whose output is +0.  An active hit gets the bits of the single-material call on its material.  Arrays: numpy (host) or torch CUDA
+    (device), in the layouts the other operators take; the ids travel in the memory space of the directions."""
+
+    _KINDS = {"sgd": 6, "abc": 7}            # DJB_KIND_SGD, DJB_KIND_ABC
+
+    def __init__(self, brdfs, ctx: Optional[Context] = None):
+        brdfs = list(brdfs)
+        self.ctx = ctx or (brdfs[0].ctx if brdfs else default_context())
+        self._h = C.c_void_p()
+        ptrs = (C.c_void_p * max(len(brdfs), 1))(*[getattr(b._h, "value", None) for b in brdfs])
+        _lib.check(_lib.load().djb_model_set_create_from_brdfs(self.ctx._h, C.c_int(len(brdfs)), ptrs, C.byref(self._h)))
+
+    @classmethod
+    def from_rows(cls, kind: str, rows, ctx: Optional[Context] = None):
+        """``kind``: "sgd" (33 doubles per row, the layout of ``sgd.from_params``) or "abc" (9 doubles per row)"""
+        if kind not in cls._KINDS:
+            raise exc(1, f"djb_error: a model set is of kind 'sgd' or 'abc' (got {kind!r})")
+        width = 33 if kind == "sgd" else 9
+        r = np.ascontiguousarray(rows, dtype=np.float64)
+        if r.ndim != 2 or r.shape[1] != width:
+            raise exc(1, f"djb_error: {kind} rows must have shape (M, {width}), got {tuple(r.shape)}")
+        self = cls.__new__(cls)
+        self.ctx = ctx or default_context()
+        self._h = C.c_void_p()
+        _lib.check(_lib.load().djb_model_set_create(self.ctx._h, C.c_int(cls._KINDS[kind]), C.c_int(r.shape[0]),
+                                                    C.c_void_p(r.ctypes.data if r.size else None), C.byref(self._h)))
+        return self
+
+    @classmethod
+    def from_names(cls, kind: str, names, ctx: Optional[Context] = None):
+        """the published rows of ``names`` (MERL material names; an sgd row also answers to its alias); an unknown name raises as
+        ``djb.sgd(name)`` / ``djb.abc(name)`` do"""
+        from . import param_tables
+        if kind not in cls._KINDS:
+            raise exc(1, f"djb_error: a model set is of kind 'sgd' or 'abc' (got {kind!r})")
+        look = param_tables.sgd_params if kind == "sgd" else param_tables.abc_params
+        rows = []
+        for name in names:
+            try:
+                rows.append(look(name))
+            except KeyError:
+                raise exc(8, f"djb_error: No {kind.upper()} parameters for {name}") from None
+        return cls.from_rows(kind, np.asarray(rows, dtype=np.float64).reshape(len(rows), 33 if kind == "sgd" else 9), ctx)
+
+    def _info(self):
+        k, n = C.c_int(), C.c_int()
+        _lib.check(_lib.load().djb_model_set_info(self._h, C.byref(k), C.byref(n)))
+        return k.value, n.value
+
+    @property
+    def kind(self) -> str:
+        return {v: k for k, v in self._KINDS.items()}[self._info()[0]]
+
+    @property
+    def n_materials(self) -> int:
+        return self._info()[1]
+
+    def _eval(self, material, i, o, want_cos):
+        vi, vo = _Vec(i), _Vec(o)
+        if vi.n != vo.n or vi.mem != vo.mem:
+            raise exc(1, "djb_error: i and o must have the same length and memory space")
+        keep, mp = merl_set._ids(material, vi)
+        out = vi.like()
+        _lib.check(_lib.load().djb_model_set_eval_batch(self.ctx._h, self._h, C.c_int64(vi.n), C.c_void_p(mp), C.byref(vi.view), C.byref(vo.view),
+                                                       C.c_int(want_cos), C.byref(out.view), C.c_int(vi.mem)))
+        del keep
+        return out.keep
+
+    def eval(self, material, i, o):
+        """f_r of material[k] at (i_k, o_k)"""
+        return self._eval(material, i, o, 0)
+
+    def evalp(self, material, i, o):
+        """f_r * cos(theta_i) of material[k] at (i_k, o_k)"""
+        return self._eval(material, i, o, 1)
+
+    def close(self):
+        if self._h:
+            _lib.load().djb_model_set_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # --------------------------------------------------------------------------- user-defined BRDFs (dj_brdf.h:74-109)
 def fit_query_dirs(resolution: int):
     """The (i, o) pairs at which ``tabular(src, resolution)`` evaluates its source, in the reference's call order
@@ -1704,6 +1800,12 @@ def set_utia_exact_only(ctx: Context, on: bool):
     """utia eval / evalp batches run the one-kernel form with the exact fall-backs inline (DJB_OPT_UTIA_EXACT_ONLY)
     instead of the two-tier kernel; same bits."""
     _lib.check(_lib.load().djb_ctx_set_option(ctx._h, C.c_int(5), C.c_int(int(on))))
+
+
+def set_model_set_rows_global(ctx: Context, on: bool):
+    """model-set kernels read their parameter rows from global memory whatever M is (DJB_OPT_MODEL_SET_ROWS_GLOBAL; tests and A/B
+    timing) instead of from the workgroup's copy in LDS; same bits."""
+    _lib.check(_lib.load().djb_ctx_set_option(ctx._h, C.c_int(9), C.c_int(int(on))))
 
 
 def set_contract_1e5(ctx: Context, on: bool):

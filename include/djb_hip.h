@@ -76,7 +76,10 @@ extern "C" {
  *        abc object: evalp of the target and the proxy's pdf for a given pair, guarded, one call).
  *        Additive under 235, no existing entry changed: UTIA material sets -- djb_utia_set, DJB_UTIA_SET_MAX, djb_utia_set_create,
  *        djb_utia_set_info, djb_utia_set_destroy, djb_utia_set_eval_batch (eval / evalp of hits on M resident UTIA tables by per-hit
- *        material id, one call). */
+ *        material id, one call).
+ *        Additive under 235, no existing entry changed: SGD / ABC model sets -- djb_model_set, DJB_MODEL_SET_MAX, djb_model_set_create,
+ *        djb_model_set_create_from_brdfs, djb_model_set_info, djb_model_set_destroy, djb_model_set_eval_batch (eval / evalp of hits on M
+ *        resident sgd or abc parameter rows by per-hit material id, one call), DJB_OPT_MODEL_SET_ROWS_GLOBAL. */
 #define DJB_HIP_VERSION 235
 #define DJB_HIP_VERSION_MAJOR(v) ((v) / 100)
 
@@ -116,6 +119,7 @@ typedef struct djb_brdf djb_brdf;   /* an immutable BRDF object resident in HBM 
 typedef struct djb_leanmap djb_leanmap;   /* an immutable LEAN map (mip pyramid of slope moments) resident in HBM */
 typedef struct djb_merl_set djb_merl_set; /* M MERL tables in one resident block + one proxy parameter set per material */
 typedef struct djb_utia_set djb_utia_set; /* M UTIA record tables in one resident block */
+typedef struct djb_model_set djb_model_set; /* M sgd or abc parameter rows in one resident block */
 
 typedef struct { float *x, *y, *z; int64_t stride; } djb_vec3_view;
 
@@ -241,7 +245,10 @@ enum { DJB_OPT_MERL_EXACT_ONLY = 1,
  * trip.  96 is the break-even of the most expensive operator (Beckmann sample, ~160 ns per unit on one core); a GGX / tabulated eval
  * costs ~31 ns per pair, so a caller that submits host batches of a few hundred pairs from several render threads -- where batch
  * calls on one context also serialise on its lock -- gains from 512 or so.  The results are the same bits either way. */
-       DJB_OPT_HOST_BATCH_MAX = 8 };
+       DJB_OPT_HOST_BATCH_MAX = 8,
+/* DJB_OPT_MODEL_SET_ROWS_GLOBAL = 1 (tests and A/B timing; off by default): the model-set kernels read their parameter rows from
+ * global memory whatever M is, instead of from the copy a workgroup keeps in LDS when the set is small enough.  Same bits. */
+       DJB_OPT_MODEL_SET_ROWS_GLOBAL = 9 };
 djb_status  djb_ctx_set_option(djb_ctx *ctx, int option, int value);
 /* Observer of the MERL file pipeline (djb_fit_merl_files, both context kinds): `fn(path, user)` is called from the reader thread
  * after a file has passed its size check and has been mapped, before its entries are gathered; NULL removes it.  Diagnostics /
@@ -605,6 +612,39 @@ djb_status djb_utia_set_destroy(djb_utia_set *);
 djb_status djb_utia_set_eval_batch(djb_ctx *, const djb_utia_set *, int64_t n, const int32_t *material,
                                    const djb_vec3_view *i, const djb_vec3_view *o, int want_cos,
                                    const djb_vec3_view *out_fr, int mem);
+
+/* ---- SGD / ABC model sets: the material sets of the two data-driven analytic models.  A model set is M resident parameter rows of ONE
+ * kind, DJB_KIND_SGD or DJB_KIND_ABC -- the reference publishes one row per MERL material for each, and mitsuba/dj_sgd.cpp / dj_abc.cpp
+ * ask their object for eval and evalp alone (they sample the cosine hemisphere).  For a model set the material is not a table base but
+ * one row of doubles: the coefficients that are launch-uniform for the single-material kernels are per-hit data here.
+ *
+ * Creation.  djb_model_set_create takes n_materials rows in host memory, in the layout djb_brdf_create_sgd_from_params (33 doubles per
+ * row) / djb_brdf_create_abc_from_params (9 doubles per row) take, and as unvalidated as there: any doubles are accepted, the arithmetic
+ * decides.  djb_model_set_create_from_brdfs reads the rows of n_materials sgd or abc objects: all of one kind, all of the call's context
+ * (anything else: DJB_ERR_INVALID_ARGUMENT); the same handle may appear more than once, and the members may be destroyed as soon as the
+ * call returns.  Either way the set holds each row exactly as the single-material constructor would have built it -- DJB_SGD_FAST=0 in the
+ * environment at creation included, which makes every row of an sgd set run the exact chains only.  1 <= M <= DJB_MODEL_SET_MAX: with
+ * that cap the byte offset of any row stays below 2^26.  The set belongs to its context as a djb_brdf does and may be destroyed after it.
+ *
+ * material: n int32 values in the memory space `mem` names.  A hit with 0 <= material[k] < M gets, bit for bit, what djb_eval_batch
+ * (djb_evalp_batch when want_cos != 0) returns for unit k's inputs on djb_brdf_create_*_from_params(rows[material[k]]).  A hit whose id is
+ * outside [0, M) is INACTIVE: out_fr of that hit is +0.0f and no row is read for it.
+ *
+ * Options.  DJB_OPT_CONTRACT_1E5 changes nothing: a set has no contract-mode kernels, every active hit has the reference's bits.
+ * DJB_OPT_MODEL_SET_ROWS_GLOBAL (tests, A/B timing) makes the kernel read rows from global memory whatever M is; by default a set of up
+ * to 101 sgd rows or 213 abc rows is copied into LDS by every workgroup.  CPU contexts serve the call with the host instantiation of the
+ * same per-unit code.  On a GPU context a device-memory batch is ONE kernel launch, with no allocation and no host read-back: it can be
+ * captured into a hipGraph.  Index-aligned in-place calls (out_fr names i's or o's arrays) are supported: every lane reads its hit
+ * before it writes it.  A host-memory batch of any size is staged through HBM (a set has no host twin). */
+#define DJB_MODEL_SET_MAX 65536
+djb_status djb_model_set_create(djb_ctx *, int kind /* DJB_KIND_SGD | DJB_KIND_ABC */, int n_materials,
+                                const double *rows /* n_materials x 33 (sgd) or x 9 (abc), host memory */, djb_model_set **out);
+djb_status djb_model_set_create_from_brdfs(djb_ctx *, int n_materials, const djb_brdf *const *members, djb_model_set **out);
+djb_status djb_model_set_info(const djb_model_set *, int *kind, int *n_materials);
+djb_status djb_model_set_destroy(djb_model_set *);
+djb_status djb_model_set_eval_batch(djb_ctx *, const djb_model_set *, int64_t n, const int32_t *material,
+                                    const djb_vec3_view *i, const djb_vec3_view *o, int want_cos,
+                                    const djb_vec3_view *out_fr, int mem);
 
 /* beckmann::lrep algebra on {E1..E5} (host scalars; dj_brdf.h:330-356, 1959-2051).  b may be NULL
  * (= the default lrep(0,0,1,1,0)); x (and y) are the scalar arguments of mul / shear / scale.

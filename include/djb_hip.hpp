@@ -1371,6 +1371,45 @@ private:
 	djb_utia_set *m_h;
 };
 
+/* M sgd or abc materials -- parameter rows of ONE kind -- resident in one block on their context's device (include/djb_hip.h,
+ * djb_model_set): each hit names its material by id and the whole batch is one call.  An extension with no counterpart in the reference.
+ * eval / evalp are all that dj_sgd / dj_abc ask of their object (they sample the cosine hemisphere).  An id outside [0, size()) marks an
+ * inactive hit: its output is +0.  An active hit gets the bits of sgd::eval / evalp (abc::eval / evalp) on its material. */
+class model_set {
+public:
+	/* n rows in the layout of djb_brdf_create_sgd_from_params (33 doubles) / djb_brdf_create_abc_from_params (9 doubles); kind = DJB_KIND_SGD or DJB_KIND_ABC */
+	model_set(int kind, size_t n, const double *rows, hip::context *c = NULL) : m_ctx(c), m_h(NULL)
+	{ hip::check(djb_model_set_create(ctx(), kind, (int)n, rows, &m_h)); }
+	/* the rows of n sgd (abc) objects are copied: the objects may be destroyed afterwards */
+	model_set(size_t n, const sgd *const *materials, hip::context *c = NULL) : m_ctx(c), m_h(NULL) { from_objects(n, materials); }
+	model_set(size_t n, const abc *const *materials, hip::context *c = NULL) : m_ctx(c), m_h(NULL) { from_objects(n, materials); }
+	~model_set() { djb_model_set_destroy(m_h); }
+	model_set(model_set &&o) noexcept : m_ctx(o.m_ctx), m_h(o.m_h) { o.m_h = NULL; }
+	model_set &operator=(model_set &&o) noexcept { if (this != &o) { djb_model_set_destroy(m_h); m_ctx = o.m_ctx; m_h = o.m_h; o.m_h = NULL; } return *this; }
+	model_set(const model_set &) = delete;
+	model_set &operator=(const model_set &) = delete;
+	const djb_model_set *get() const { return m_h; }
+	int size() const { int v; hip::check(djb_model_set_info(m_h, NULL, &v)); return v; }
+	int kind() const { int v; hip::check(djb_model_set_info(m_h, &v, NULL)); return v; }
+	// ---- host arrays
+	void eval(size_t n, const int32_t *material, const vec3 *i, const vec3 *o, vec3 *out) const { eval_views((int64_t)n, material, hip::view(i), hip::view(o), hip::view(out), 0, DJB_MEM_HOST); }
+	void evalp(size_t n, const int32_t *material, const vec3 *i, const vec3 *o, vec3 *out) const { eval_views((int64_t)n, material, hip::view(i), hip::view(o), hip::view(out), 1, DJB_MEM_HOST); }
+	// ---- views (SoA or strided), in host memory or in HBM (mem = DJB_MEM_DEVICE: asynchronous on the context's stream)
+	void eval_views(int64_t n, const int32_t *material, const djb_vec3_view &i, const djb_vec3_view &o, const djb_vec3_view &out,
+	                int want_cos, int mem) const
+	{ hip::check(djb_model_set_eval_batch(ctx(), m_h, n, material, &i, &o, want_cos, &out, mem)); }
+private:
+	template <typename T> void from_objects(size_t n, const T *const *materials)
+	{
+		std::vector<const djb_brdf *> h(n);
+		for (size_t k = 0; k < n; ++k) h[k] = materials[k] ? materials[k]->handle() : NULL;
+		hip::check(djb_model_set_create_from_brdfs(ctx(), (int)n, h.data(), &m_h));
+	}
+	djb_ctx *ctx() const { return (m_ctx ? *m_ctx : hip::context::standard()).get(); }
+	hip::context *m_ctx;
+	djb_model_set *m_h;
+};
+
 } // namespace djb
 
 #endif // DJB_HIP_HPP

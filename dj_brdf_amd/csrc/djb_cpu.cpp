@@ -971,13 +971,65 @@ djb_status evalp_pdf_proxy(djb_ctx *ctx, const djb_brdf *target, const djb_brdf 
 	return DJB_OK;
 }
 
-// ------------------------------------------------------------------ MERL material sets: the two loops above per hit, the table and the proxy's
-// parameters selected by the hit's material id; an id outside [0, n_mat) is an inactive hit (+0 in every output, nothing read)
+// ------------------------------------------------------------------ material sets (MERL, UTIA, SGD / ABC): eval_one per hit on a Brdf that
+// the hit's material id points at its table or row; an id outside [0, n_mat) is an inactive hit (+0 in every output, nothing read)
+// a member belongs to the set's context (`what`: "merl" / "utia" / "model"); whether it is of the set's kind is each set's own test
+static djb_status set_member_check(const djb_ctx *ctx, const djb_brdf *b, int index, const char *what)
+{
+	if (!b) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: %s set member %d is a null brdf", what, index);
+	if (!is_cpu(b) || B(b)->ctx != (const CpuCtx *)ctx)
+		return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: %s set member %d belongs to another context", what, index);
+	return DJB_OK;
+}
+static djb_status set_batch_head(int64_t n, const int32_t *material)
+{
+	if (n < 0) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: negative batch size");
+	if (!material) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null material array");
+	return DJB_OK;
+}
+static djb_status set_batch_args(int64_t n, const int32_t *material, const djb_vec3_view *i, const djb_vec3_view *o, const djb_vec3_view *out)
+{
+	djb_status st = set_batch_head(n, material);
+	if (st != DJB_OK) return st;
+	if (!valid(i) || !valid(o)) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null vec3 view");
+	if (!valid(out)) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null output vec3 view");
+	return DJB_OK;
+}
+// bind(tb, m): point the lane's Brdf at material m
+template <int KIND, int WANT, typename Bind>
+void set_eval_loop(int n_mat, long long k0, long long k1, const int32_t *material, const View &vi, const View &vo, const View &vout, Bind bind)
+{
+	Brdf tb; memset(&tb, 0, sizeof tb); tb.kind = KIND;
+	Params tp; memset(&tp, 0, sizeof tp);
+	for (long long k = k0; k < k1; ++k) {
+		v3 fr = mk(0, 0, 0); float unused_pdf = 0.0f;
+		const unsigned int m = (unsigned int)material[k];
+		if (m < (unsigned int)n_mat) {
+			bind(tb, m);
+			eval_one<KIND, WANT>(tb, tp, load3(vi, k), load3(vo, k), fr, unused_pdf);
+		}
+		store3(vout, k, fr);
+	}
+}
+template <int KIND, typename Bind>
+djb_status set_eval(djb_ctx *ctx, int n_mat, int64_t n, const int32_t *material, const djb_vec3_view *i, const djb_vec3_view *o, int want_cos,
+                    const djb_vec3_view *out_fr, Bind bind)
+{
+	djb_status st = set_batch_args(n, material, i, o, out_fr);
+	if (st != DJB_OK) return st;
+	const View vi = view_of(i), vo = view_of(o), vout = view_of(out_fr);
+	parallel_for(C(ctx), n, 4096, [&](long long k0, long long k1) {
+		if (want_cos) set_eval_loop<KIND, 2>(n_mat, k0, k1, material, vi, vo, vout, bind);
+		else set_eval_loop<KIND, 1>(n_mat, k0, k1, material, vi, vo, vout, bind);
+	});
+	return DJB_OK;
+}
+
+// MERL sets: texels = MerlTexel[n_mat][MERL_N]
 djb_status merl_set_member(const djb_ctx *ctx, const djb_brdf *b, int index, const void **texels)
 {
-	if (!b) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: merl set member %d is a null brdf", index);
-	if (!is_cpu(b) || B(b)->ctx != (const CpuCtx *)ctx)
-		return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: merl set member %d belongs to another context", index);
+	djb_status st = set_member_check(ctx, b, index, "merl");
+	if (st != DJB_OK) return st;
 	if (B(b)->dev.kind != KIND_MERL || B(b)->dev.merl_sparse || !B(b)->dev.merl)
 		return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: merl set member %d is not a dense merl brdf (kind %d)", index, B(b)->dev.kind);
 	*texels = B(b)->dev.merl;
@@ -987,86 +1039,35 @@ djb_status merl_set_resolve_params(const djb_params *in, void *out_params)
 {
 	return params_for(in, KIND_GGX, (Params *)out_params);
 }
-template <int WANT>
-void merl_set_eval_loop(const MerlTexel *tex, int n_mat, long long k0, long long k1, const int32_t *material, const View &vi, const View &vo, const View &vout)
-{
-	Brdf tb; memset(&tb, 0, sizeof tb); tb.kind = KIND_MERL;
-	Params tp; memset(&tp, 0, sizeof tp);
-	for (long long k = k0; k < k1; ++k) {
-		v3 fr = mk(0, 0, 0); float unused_pdf = 0.0f;
-		const unsigned int m = (unsigned int)material[k];
-		if (m < (unsigned int)n_mat) {
-			tb.merl = tex + (size_t)m * (size_t)MERL_N;
-			eval_one<KIND_MERL, WANT>(tb, tp, load3(vi, k), load3(vo, k), fr, unused_pdf);
-		}
-		store3(vout, k, fr);
-	}
-}
 djb_status merl_set_eval(djb_ctx *ctx, const void *texels, int n_mat, int64_t n, const int32_t *material, const djb_vec3_view *i,
                          const djb_vec3_view *o, int want_cos, const djb_vec3_view *out_fr)
 {
-	if (n < 0) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: negative batch size");
-	if (!material) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null material array");
-	if (!valid(i) || !valid(o)) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null vec3 view");
-	if (!valid(out_fr)) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null output vec3 view");
-	const View vi = view_of(i), vo = view_of(o), vout = view_of(out_fr);
 	const MerlTexel *tex = (const MerlTexel *)texels;
-	parallel_for(C(ctx), n, 4096, [&](long long k0, long long k1) {
-		if (want_cos) merl_set_eval_loop<2>(tex, n_mat, k0, k1, material, vi, vo, vout);
-		else merl_set_eval_loop<1>(tex, n_mat, k0, k1, material, vi, vo, vout);
-	});
-	return DJB_OK;
+	return set_eval<KIND_MERL>(ctx, n_mat, n, material, i, o, want_cos, out_fr,
+	                           [tex](Brdf &tb, unsigned int m) { tb.merl = tex + (size_t)m * (size_t)MERL_N; });
 }
-// ------------------------------------------------------------------ UTIA material sets: eval_one<KIND_UTIA> per hit on the record table the
-// hit's id selects (records = float4[n_mat][288 * 288 * 8]); an id outside [0, n_mat) is an inactive hit (+0, nothing read)
+// UTIA sets: records = float4[n_mat][288 * 288 * 8]
 djb_status utia_set_member(const djb_ctx *ctx, const djb_brdf *b, int index, const void **records)
 {
-	if (!b) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: utia set member %d is a null brdf", index);
-	if (!is_cpu(b) || B(b)->ctx != (const CpuCtx *)ctx)
-		return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: utia set member %d belongs to another context", index);
+	djb_status st = set_member_check(ctx, b, index, "utia");
+	if (st != DJB_OK) return st;
 	if (B(b)->dev.kind != KIND_UTIA || !B(b)->dev.utia)
 		return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: utia set member %d is not a utia brdf (kind %d)", index, B(b)->dev.kind);
 	*records = B(b)->dev.utia;
 	return DJB_OK;
 }
-template <int WANT>
-void utia_set_eval_loop(const float4 *tab, int n_mat, long long k0, long long k1, const int32_t *material, const View &vi, const View &vo, const View &vout)
-{
-	Brdf tb; memset(&tb, 0, sizeof tb); tb.kind = KIND_UTIA;
-	Params tp; memset(&tp, 0, sizeof tp);
-	for (long long k = k0; k < k1; ++k) {
-		v3 fr = mk(0, 0, 0); float unused_pdf = 0.0f;
-		const unsigned int m = (unsigned int)material[k];
-		if (m < (unsigned int)n_mat) {
-			tb.utia = tab + (size_t)m * 8 * (size_t)(UTIA_N / 3);
-			eval_one<KIND_UTIA, WANT>(tb, tp, load3(vi, k), load3(vo, k), fr, unused_pdf);
-		}
-		store3(vout, k, fr);
-	}
-}
 djb_status utia_set_eval(djb_ctx *ctx, const void *records, int n_mat, int64_t n, const int32_t *material, const djb_vec3_view *i,
                          const djb_vec3_view *o, int want_cos, const djb_vec3_view *out_fr)
 {
-	if (n < 0) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: negative batch size");
-	if (!material) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null material array");
-	if (!valid(i) || !valid(o)) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null vec3 view");
-	if (!valid(out_fr)) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null output vec3 view");
-	const View vi = view_of(i), vo = view_of(o), vout = view_of(out_fr);
 	const float4 *tab = (const float4 *)records;
-	parallel_for(C(ctx), n, 4096, [&](long long k0, long long k1) {
-		if (want_cos) utia_set_eval_loop<2>(tab, n_mat, k0, k1, material, vi, vo, vout);
-		else utia_set_eval_loop<1>(tab, n_mat, k0, k1, material, vi, vo, vout);
-	});
-	return DJB_OK;
+	return set_eval<KIND_UTIA>(ctx, n_mat, n, material, i, o, want_cos, out_fr,
+	                           [tab](Brdf &tb, unsigned int m) { tb.utia = tab + (size_t)m * 8 * (size_t)(UTIA_N / 3); });
 }
-// ------------------------------------------------------------------ SGD / ABC model sets: eval_one<KIND_SGD / KIND_ABC> per hit on a Brdf whose
-// `model` is the row the hit's id selects and whose Fresnel operands are create_model's for that row (rows = double[n_mat][33 or 9]); an id
-// outside [0, n_mat) is an inactive hit (+0, nothing read)
+// SGD / ABC sets: rows = double[n_mat][33 or 9]; the Brdf's `model` is the hit's row and its Fresnel operands are create_model's for that row
 djb_status model_set_member(const djb_ctx *ctx, const djb_brdf *b, int index, int *kind, const double **row)
 {
-	if (!b) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: model set member %d is a null brdf", index);
-	if (!is_cpu(b) || B(b)->ctx != (const CpuCtx *)ctx)
-		return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: model set member %d belongs to another context", index);
+	djb_status st = set_member_check(ctx, b, index, "model");
+	if (st != DJB_OK) return st;
 	const int k = B(b)->dev.kind;
 	if ((k != KIND_SGD && k != KIND_ABC) || B(b)->model.size() != (size_t)(k == KIND_SGD ? 33 : 9))
 		return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: model set member %d is not an sgd or abc brdf (kind %d)", index, k);
@@ -1074,45 +1075,22 @@ djb_status model_set_member(const djb_ctx *ctx, const djb_brdf *b, int index, in
 	*row = B(b)->model.data();
 	return DJB_OK;
 }
-template <int KIND, int WANT>
-void model_set_eval_loop(const double *rows, int n_mat, long long k0, long long k1, const int32_t *material, const View &vi, const View &vo, const View &vout)
-{
-	constexpr int STRIDE = KIND == KIND_SGD ? 33 : 9;
-	Brdf tb; memset(&tb, 0, sizeof tb); tb.kind = KIND;
-	tb.fr.kind = KIND == KIND_SGD ? FR_SGD : FR_UNPOLARIZED;
-	Params tp; memset(&tp, 0, sizeof tp);
-	for (long long k = k0; k < k1; ++k) {
-		v3 fr = mk(0, 0, 0); float unused_pdf = 0.0f;
-		const unsigned int m = (unsigned int)material[k];
-		if (m < (unsigned int)n_mat) {
-			const double *row = rows + (size_t)m * STRIDE;
-			tb.model = row;
-			if (KIND == KIND_SGD) { for (int c = 0; c < 3; ++c) { tb.fr.a[c] = (float)row[12 + c]; tb.fr.b[c] = (float)row[15 + c]; } }
-			else { for (int c = 0; c < 3; ++c) tb.fr.a[c] = (float)row[8]; }
-			eval_one<KIND, WANT>(tb, tp, load3(vi, k), load3(vo, k), fr, unused_pdf);
-		}
-		store3(vout, k, fr);
-	}
-}
 djb_status model_set_eval(djb_ctx *ctx, int kind, const double *rows, int n_mat, int64_t n, const int32_t *material, const djb_vec3_view *i,
                           const djb_vec3_view *o, int want_cos, const djb_vec3_view *out_fr)
 {
-	if (n < 0) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: negative batch size");
-	if (!material) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null material array");
-	if (!valid(i) || !valid(o)) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null vec3 view");
-	if (!valid(out_fr)) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null output vec3 view");
-	const View vi = view_of(i), vo = view_of(o), vout = view_of(out_fr);
-	parallel_for(C(ctx), n, 4096, [&](long long k0, long long k1) {
-		if (kind == KIND_SGD) {
-			if (want_cos) model_set_eval_loop<KIND_SGD, 2>(rows, n_mat, k0, k1, material, vi, vo, vout);
-			else model_set_eval_loop<KIND_SGD, 1>(rows, n_mat, k0, k1, material, vi, vo, vout);
-		} else {
-			if (want_cos) model_set_eval_loop<KIND_ABC, 2>(rows, n_mat, k0, k1, material, vi, vo, vout);
-			else model_set_eval_loop<KIND_ABC, 1>(rows, n_mat, k0, k1, material, vi, vo, vout);
-		}
+	if (kind == KIND_SGD)
+		return set_eval<KIND_SGD>(ctx, n_mat, n, material, i, o, want_cos, out_fr, [rows](Brdf &tb, unsigned int m) {
+			const double *row = rows + (size_t)m * 33;
+			tb.model = row; tb.fr.kind = FR_SGD;
+			for (int c = 0; c < 3; ++c) { tb.fr.a[c] = (float)row[12 + c]; tb.fr.b[c] = (float)row[15 + c]; }
+		});
+	return set_eval<KIND_ABC>(ctx, n_mat, n, material, i, o, want_cos, out_fr, [rows](Brdf &tb, unsigned int m) {
+		const double *row = rows + (size_t)m * 9;
+		tb.model = row; tb.fr.kind = FR_UNPOLARIZED;
+		for (int c = 0; c < 3; ++c) tb.fr.a[c] = (float)row[8];
 	});
-	return DJB_OK;
 }
+// the two MERL-set proxy loops: proxy_loop / proxy_light_loop above per hit, the table and the proxy's parameters selected by the hit's id
 template <int PK>
 void merl_set_proxy_loop(const MerlTexel *tex, const Params *params, int n_mat, const Brdf &pb, long long k0, long long k1, const int32_t *material,
                          const float *u1a, const float *u2a, const View &vo, const View &vw_out, const View &vi_out, float *out_pdf)
@@ -1143,8 +1121,8 @@ djb_status merl_set_evalp_is_proxy(djb_ctx *ctx, const void *texels, const void 
                                    const int32_t *material, const float *u1, const float *u2, const djb_vec3_view *o,
                                    const djb_vec3_view *out_w, const djb_vec3_view *out_i, float *out_pdf)
 {
-	if (n < 0) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: negative batch size");
-	if (!material) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null material array");
+	djb_status st = set_batch_head(n, material);
+	if (st != DJB_OK) return st;
 	if (!u1 || !u2 || !valid(o) || !valid(out_w) || !valid(out_i) || !out_pdf) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null argument");
 	if (B(proxy)->ctx != C(ctx)) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: merl set and proxy belong to different contexts");
 	const Brdf &pb = B(proxy)->dev;
@@ -1185,8 +1163,8 @@ djb_status merl_set_evalp_pdf(djb_ctx *ctx, const void *texels, const void *para
                               const int32_t *material, const djb_vec3_view *i, const djb_vec3_view *o, const djb_vec3_view *out_fr,
                               float *out_pdf)
 {
-	if (n < 0) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: negative batch size");
-	if (!material) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null material array");
+	djb_status st = set_batch_head(n, material);
+	if (st != DJB_OK) return st;
 	if (!valid(i) || !valid(o)) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null vec3 view");
 	if (!valid(out_fr) || !out_pdf) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null output");
 	if (B(proxy)->ctx != C(ctx)) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: merl set and proxy belong to different contexts");

@@ -20,6 +20,7 @@
 #include <thread>
 #include <unistd.h>
 #include <map>
+#include <algorithm>
 #include <atomic>
 #include <mutex>
 #include <string>
@@ -123,13 +124,17 @@ struct djb_leanmap {
 	mutable std::atomic<int> host_ready{0};
 };
 
+// what the three material-set handles share (djb_set_host.hpp works on this part); the types stay distinct and opaque to C
+struct djb_set_base {
+	int device = 0;                  // of the creating context, < 0: a CPU context's set (kept here: the handle may outlive its context)
+	djb_ctx *ctx = nullptr;          // the creating context: compared by the batch calls
+	int n_mat = 0;
+};
+
 // a MERL material set (djb_merl_set.hip): the converted tables of M dense MERL objects in one block, MerlTexel[M][1458000], and -- once
 // given -- the resolved proxy parameters Params[M]; both where the set's context computes (HBM, or host memory for a CPU context).
-// The tables are immutable; the parameters are replaced in stream order by djb_merl_set_set_proxy_params.
-struct djb_merl_set {
-	int device;                      // of the creating context, < 0: a CPU context's set (kept here: the handle may outlive its context)
-	djb_ctx *ctx;                    // the creating context: compared by the batch calls, used by set_proxy_params (a GPU set's stream)
-	int n_mat = 0;
+// The tables are immutable; the parameters are replaced in stream order by djb_merl_set_set_proxy_params (on the context's stream).
+struct djb_merl_set : djb_set_base {
 	bool has_params = false;
 	djbdev::MerlTexel *tex = nullptr;
 	Params *params = nullptr;
@@ -137,21 +142,15 @@ struct djb_merl_set {
 
 // a UTIA material set (djb_utia_set.hip): the converted record tables of M utia objects in one block, float4[M][288 * 288 * 8], where the
 // set's context computes (HBM, or host memory for a CPU context).  Immutable after its constructor returned.
-struct djb_utia_set {
-	int device;                      // of the creating context, < 0: a CPU context's set (kept here: the handle may outlive its context)
-	djb_ctx *ctx;                    // the creating context: compared by the batch call
-	int n_mat = 0;
+struct djb_utia_set : djb_set_base {
 	float4 *tab = nullptr;
 };
 
 // an SGD / ABC model set (djb_model_set.hip): M parameter rows of one kind in one block where the set's context computes.  GPU context:
 // double[M][stride] in HBM, each row as create_model uploads the single one (sgd: 61 doubles, abc: 9).  CPU context: the rows as given,
 // double[M][33 or 9] in host memory.  Immutable after its constructor returned.
-struct djb_model_set {
-	int device;                      // of the creating context, < 0: a CPU context's set (kept here: the handle may outlive its context)
-	djb_ctx *ctx;                    // the creating context: compared by the batch call
+struct djb_model_set : djb_set_base {
 	int kind = 0;                    // DJB_KIND_SGD or DJB_KIND_ABC
-	int n_mat = 0;
 	double *rows = nullptr;
 };
 
@@ -400,7 +399,7 @@ inline djb_status stage_leanmap_coords(Staged &sg, const float *uv, const float 
 	if (lod && (st = sg.in_f(lod, &src->lod)) != DJB_OK) return st;
 	return DJB_OK;
 }
-// material sets (djb_merl_set.hip, djb_utia_set.hip, djb_model_set.hip): the n material ids of a batch where the kernels read them
+// material sets: the n material ids of a batch where the kernels read them (the rest of what the set files share: djb_set_host.hpp)
 inline djb_status stage_material(Staged &sg, const int32_t *material, const int32_t **out)
 {
 	if (!material) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null material array");
@@ -411,6 +410,42 @@ inline djb_status stage_material(Staged &sg, const int32_t *material, const int3
 	if (sg.n && (st = sg.copy(d, material, sizeof(int32_t) * (size_t)sg.n, hipMemcpyHostToDevice)) != DJB_OK) return st;
 	*out = d;
 	return DJB_OK;
+}
+// ------------------------------------------------------------------ shared by eval_common (djb_host_ops.hip) and the UTIA set's eval batch
+// Do the n elements of any output stream share memory with those of any input stream?  A stream is a pointer and a stride in 4-byte
+// units (floats, or the int32 ids of a set); null streams are skipped, n <= 0 overlaps nothing.  The two-tier kernels write placeholders
+// in tier 1 and re-read their inputs in tier 2, so a device-resident call for which this holds takes the one-kernel forms instead.
+struct Stream { const void *p; long long stride; };
+inline bool outputs_overlap_inputs(long long n, const Stream *ins, int n_in, const Stream *outs, int n_out)
+{
+	if (n <= 0) return false;
+	auto end = [n](const Stream &s) { return (uintptr_t)s.p + 4 * (uintptr_t)((n - 1) * s.stride + 1); };
+	for (int a = 0; a < n_out; ++a)
+		for (int c = 0; c < n_in; ++c)
+			if (outs[a].p && ins[c].p && (uintptr_t)outs[a].p < end(ins[c]) && (uintptr_t)ins[c].p < end(outs[a])) return true;
+	return false;
+}
+// the context's scratch block (the tier-2 worklists) holds at least `need` bytes; growing it waits for the stream, whose work may still use the old one
+inline djb_status ensure_scratch(djb_ctx *ctx, size_t need)
+{
+	if (ctx->scratch_bytes >= need) return DJB_OK;
+	HIP_TRY(hipStreamSynchronize(ctx->stream));
+	if (ctx->scratch) (void)hipFree(ctx->scratch);
+	ctx->scratch = nullptr; ctx->scratch_bytes = 0;
+	HIP_TRY(hipMalloc(&ctx->scratch, need));
+	ctx->scratch_bytes = need;
+	return DJB_OK;
+}
+// The kernels that list pairs for a second tier carry pair indices as uint32, so their batches run in chunks of CHUNK pairs:
+//   for (long long lo = 0; lo < n; lo += CHUNK) { const long long m = std::min(n - lo, CHUNK); ... offset_view(v, lo) ... }
+// offset_view: the view from element `lo` on.  Strided views (the MERL / UTIA two-tier calls) advance by lo * stride.  The contract
+// kernels run on dense views only (stride 1, where lo * stride == lo) and take an all-null view with stride 0 for an output that was
+// not asked for: a null plane stays null whatever the stride, so one form serves both.
+constexpr long long CHUNK = 1LL << 31;
+inline View offset_view(const View &v, long long lo)
+{
+	auto at = [&](float *q) { return q ? q + lo * v.stride : nullptr; };
+	return View{ at(v.x), at(v.y), at(v.z), v.stride };
 }
 // object construction helpers (djb_host.hip)
 djb_status alloc_brdf(djb_ctx *ctx, int kind, djb_brdf **out);

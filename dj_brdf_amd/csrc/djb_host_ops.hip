@@ -263,52 +263,30 @@ djb_status eval_common(djb_ctx *ctx, const djb_brdf *b, int64_t n, const djb_vec
 	// batch), so a device-resident caller whose OUTPUT arrays overlap its INPUT arrays (in-place evalp) must not use them:
 	// such calls take the one-kernel forms, which read a pair before they write it (index-aligned in-place views are
 	// the only supported kind of overlap, as for any elementwise kernel).
-	bool aliased = false;
-	if (mem == DJB_MEM_DEVICE) {
-		auto span = [&](const float *q, long long stride) { return std::make_pair((uintptr_t)q, (uintptr_t)(q + (n > 0 ? (n - 1) * stride + 1 : 0))); };
-		auto hit = [&](const float *a, long long sa, const float *bq, long long sb) {
-			if (!a || !bq || n <= 0) return false;
-			auto x = span(a, sa), y = span(bq, sb);
-			return x.first < y.second && y.first < x.second;
-		};
-		const float *ins[6] = { vi.x, vi.y, vi.z, vo.x, vo.y, vo.z };
-		const long long sin_[6] = { vi.stride, vi.stride, vi.stride, vo.stride, vo.stride, vo.stride };
-		const float *outs_[4] = { (want & 3) ? vout.x : nullptr, (want & 3) ? vout.y : nullptr, (want & 3) ? vout.z : nullptr, dpdf };
-		const long long sout[4] = { vout.stride, vout.stride, vout.stride, 1 };
-		for (int a = 0; a < 4 && !aliased; ++a) for (int c = 0; c < 6; ++c) if (hit(outs_[a], sout[a], ins[c], sin_[c])) { aliased = true; break; }
-	}
+	const Stream ins[6] = { { vi.x, vi.stride }, { vi.y, vi.stride }, { vi.z, vi.stride }, { vo.x, vo.stride }, { vo.y, vo.stride }, { vo.z, vo.stride } };
+	const Stream outs[4] = { { vout.x, vout.stride }, { vout.y, vout.stride }, { vout.z, vout.stride }, { dpdf, 1 } };   // null where not asked for
+	const bool aliased = mem == DJB_MEM_DEVICE && outputs_overlap_inputs(n, ins, 6, outs, 4);
 	if (b->dev.kind == DJB_KIND_MERL && (want & 3) && !ctx->merl_exact_only && !aliased) {
 		// two-tier exact lookup (both tiers in one kernel: tier 2 is drained from per-wave LDS queues); pair indices travel as uint32, so very
 		// large batches are chunked
-		const long long CH = 1LL << 31;
-		for (long long lo = 0; lo < n; lo += CH) {
-			long long m = n - lo < CH ? n - lo : CH;
-			auto off = [&](const View &v) { return View{ v.x + lo * v.stride, v.y + lo * v.stride, v.z + lo * v.stride, v.stride }; };
-			View oi = off(vi), oo = off(vo), ou = (want & 3) ? off(vout) : vout;
-			HIP_TRY(djbk::launch_merl_twotier(ctx->stream, b->dev, m, oi, oo, ou, dpdf ? dpdf + lo : nullptr, want));
+		for (long long lo = 0; lo < n; lo += CHUNK) {
+			const long long m = std::min(n - lo, CHUNK);
+			HIP_TRY(djbk::launch_merl_twotier(ctx->stream, b->dev, m, offset_view(vi, lo), offset_view(vo, lo), offset_view(vout, lo),
+			                                  dpdf ? dpdf + lo : nullptr, want));
 		}
 		return sg.finish();
 	}
 	if (b->dev.kind == DJB_KIND_UTIA && (want & 3) && !ctx->utia_exact_only && !aliased) {
 		// two-tier (djb_kernels_eval.hip): pair indices travel as uint32, so very large batches are chunked; the
 		// worklist (16-byte header + 4 bytes per entry; ~2e-5 of the pairs need it) shares the context's scratch
-		const long long CH = 1LL << 31;
-		for (long long lo = 0; lo < n; lo += CH) {
-			long long m = n - lo < CH ? n - lo : CH;
+		for (long long lo = 0; lo < n; lo += CHUNK) {
+			const long long m = std::min(n - lo, CHUNK);
 			size_t cap = (size_t)(m / 256 + 4096);
 			if (ctx->test_worklist_cap >= 0) cap = (size_t)ctx->test_worklist_cap;   // DJB_OPT_TEST_WORKLIST_CAP (tests): force the overflow path
-			size_t need = 16 + 4 * (cap ? cap : 1);
-			if (ctx->scratch_bytes < need) {
-				HIP_TRY(hipStreamSynchronize(ctx->stream));
-				if (ctx->scratch) (void)hipFree(ctx->scratch);
-				ctx->scratch = nullptr; ctx->scratch_bytes = 0;
-				HIP_TRY(hipMalloc(&ctx->scratch, need));
-				ctx->scratch_bytes = need;
-			}
+			if ((st = ensure_scratch(ctx, 16 + 4 * (cap ? cap : 1))) != DJB_OK) return st;
 			unsigned int *count = (unsigned int *)ctx->scratch, *list = count + 4;
-			auto off = [&](const View &v) { return View{ v.x + lo * v.stride, v.y + lo * v.stride, v.z + lo * v.stride, v.stride }; };
-			HIP_TRY(djbk::launch_utia_twotier(ctx->stream, b->dev, m, off(vi), off(vo), off(vout), dpdf ? dpdf + lo : nullptr, want,
-			                                  list, (unsigned int)cap, count, ctx->contract_1e5 != 0));
+			HIP_TRY(djbk::launch_utia_twotier(ctx->stream, b->dev, m, offset_view(vi, lo), offset_view(vo, lo), offset_view(vout, lo),
+			                                  dpdf ? dpdf + lo : nullptr, want, list, (unsigned int)cap, count, ctx->contract_1e5 != 0));
 		}
 		return sg.finish();
 	}
@@ -338,9 +316,8 @@ djb_status eval_common(djb_ctx *ctx, const djb_brdf *b, int64_t n, const djb_vec
 		                     (!(want & 3) || (vout.stride == 1 && al16(vout.x) && al16(vout.y) && al16(vout.z))) && (!(want & 4) || al16(dpdf));
 		if (dense16) {
 			// as for MERL: pair indices travel as uint32; worklist = 512-byte header (CONTRACT_SHARDS counters) + 32-byte records {k, i, o}
-			const long long CH = 1LL << 31;
-			for (long long lo = 0; lo < n; lo += CH) {
-				long long m = n - lo < CH ? n - lo : CH;
+			for (long long lo = 0; lo < n; lo += CHUNK) {
+				const long long m = std::min(n - lo, CHUNK);
 				const size_t REC = 32;
 				wl_adapt(ctx);
 				// a first call has nothing to adapt to, and an overflow costs a full exact pass ON TOP of tier 1 (sgd: 8 ms instead of 1.4 per 1e8
@@ -352,18 +329,10 @@ djb_status eval_common(djb_ctx *ctx, const djb_brdf *b, int64_t n, const djb_vec
 				if (ctx->test_worklist_cap >= 0) cap = ((size_t)ctx->test_worklist_cap / djbk::CONTRACT_SHARDS + 1) * djbk::CONTRACT_SHARDS;
 				if (cap > 0xfffffff0ull) cap = 0xfffffff0ull / djbk::CONTRACT_SHARDS * djbk::CONTRACT_SHARDS;
 				const size_t HDR = sizeof(unsigned int) * djbk::CONTRACT_SHARDS * djbk::CONTRACT_COUNTER_STRIDE;     // 8 KB of counters
-				size_t need = HDR + REC * cap;
-				if (ctx->scratch_bytes < need) {
-					HIP_TRY(hipStreamSynchronize(ctx->stream));
-					if (ctx->scratch) (void)hipFree(ctx->scratch);
-					ctx->scratch = nullptr; ctx->scratch_bytes = 0;
-					HIP_TRY(hipMalloc(&ctx->scratch, need));
-					ctx->scratch_bytes = need;
-				}
+				if ((st = ensure_scratch(ctx, HDR + REC * cap)) != DJB_OK) return st;
 				unsigned int *count = (unsigned int *)ctx->scratch, *list = count + HDR / sizeof(unsigned int);
-				auto off = [&](const View &v) { return View{ v.x ? v.x + lo : nullptr, v.y ? v.y + lo : nullptr, v.z ? v.z + lo : nullptr, v.stride }; };
-				HIP_TRY(djbk::launch_eval_contract(ctx->stream, b->dev, p, model_host, m, off(vi), off(vo), off(vout), dpdf ? dpdf + lo : nullptr, want,
-				                                   list, (unsigned int)cap, count));
+				HIP_TRY(djbk::launch_eval_contract(ctx->stream, b->dev, p, model_host, m, offset_view(vi, lo), offset_view(vo, lo), offset_view(vout, lo),
+				                                   dpdf ? dpdf + lo : nullptr, want, list, (unsigned int)cap, count));
 				if (wl_note(ctx, count, cap, m, (int)djbk::CONTRACT_SHARDS, (int)djbk::CONTRACT_COUNTER_STRIDE)) ctx->wl_note_key = ct_key;
 			}
 			return sg.finish();

@@ -1,7 +1,8 @@
 // djb_merl_set.hip -- the C ABI of MERL material sets (include/djb_hip.h: djb_merl_set): M resident MERL tables in one block and one
 // resolved proxy parameter set per material, evaluated / importance-sampled per hit by material id.  Kernels: djb_kernels_merl_set.hip;
-// host loops (CPU contexts): djb_cpu.cpp.  A set has no host twin: on a GPU context a host batch of any size is staged to the device.
-#include "djb_host.hpp"
+// host loops (CPU contexts): djb_cpu.cpp; what the three kinds of set share: djb_set_host.hpp.  A set has no host twin: on a GPU context a
+// host batch of any size is staged to the device.
+#include "djb_set_host.hpp"
 
 using namespace djbh;
 using djbdev::MerlTexel;
@@ -9,17 +10,6 @@ using djbdev::MerlTexel;
 namespace {
 
 constexpr size_t TABLE_BYTES = sizeof(MerlTexel) * (size_t)MERL_N;
-
-// the set belongs to the call's context, as a djb_brdf does
-djb_status set_check(const djb_ctx *ctx, const djb_merl_set *s)
-{
-	if (!s) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null merl set");
-	if (!ctx) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null ctx");
-	if (is_cpu(ctx) != (s->device < 0))
-		return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: merl set and ctx belong to different back ends (CPU / GPU)");
-	if (s->ctx != ctx) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: the merl set belongs to another context");
-	return DJB_OK;
-}
 
 // n_mat plain parameter sets -> Params as the single-material calls of the set's back end resolve them
 djb_status resolve_all(bool cpu, int n_mat, const djb_params *in, std::vector<Params> *out)
@@ -48,6 +38,22 @@ djb_status install_params(djb_merl_set *s, const std::vector<Params> &p)
 	return DJB_OK;
 }
 
+// the proxy of a proxy call (`op`, as the messages name it) is a ggx or beckmann object of the set's context, and the set has parameters for it
+djb_status proxy_check(const djb_ctx *ctx, const djb_merl_set *s, const djb_brdf *proxy, const char *op)
+{
+	if (!proxy) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null brdf (proxy)");
+	djb_status st = cpu_pair_check(ctx, proxy);
+	if (st != DJB_OK) return st;
+	const bool cpu = is_cpu(ctx);
+	if (!cpu && (proxy->ctx != ctx || proxy->device != ctx->device))
+		return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: merl set and proxy belong to different contexts");
+	const int pkind = cpu ? djbcpu::kind(proxy) : proxy->dev.kind;
+	if (pkind != DJB_KIND_GGX && pkind != DJB_KIND_BECKMANN)
+		return fail(DJB_ERR_NOT_IMPLEMENTED, "djb_error: %s on a merl set takes a ggx or beckmann proxy (proxy kind %d)", op, pkind);
+	if (!s->has_params) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: the merl set has no proxy parameters (djb_merl_set_set_proxy_params)");
+	return DJB_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -56,17 +62,14 @@ djb_status djb_merl_set_create(djb_ctx *ctx, int n_materials, const djb_brdf *co
 try {
 	if (!ctx || !out || !merls) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null argument");
 	*out = nullptr;
-	if (n_materials < 1 || n_materials > DJB_MERL_SET_MAX)
-		return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: a merl set holds 1 .. %d materials (got %d)", DJB_MERL_SET_MAX, n_materials);
+	djb_status st = set_count_check("merl", n_materials, DJB_MERL_SET_MAX);
+	if (st != DJB_OK) return st;
 	const bool cpu = is_cpu(ctx);
-	djb_status st;
 	std::vector<const void *> src((size_t)n_materials);
 	for (int m = 0; m < n_materials; ++m) {
 		const djb_brdf *b = merls[m];
 		if (cpu) { if ((st = djbcpu::merl_set_member(ctx, b, m, &src[m])) != DJB_OK) return st; continue; }
-		if (!b) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: merl set member %d is a null brdf", m);
-		if (is_cpu(b) || b->ctx != ctx || b->device != ctx->device)
-			return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: merl set member %d belongs to another context", m);
+		if ((st = set_gpu_member(ctx, b, m, "merl")) != DJB_OK) return st;
 		if (b->dev.kind != DJB_KIND_MERL || b->dev.merl_sparse || !b->dev.merl)
 			return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: merl set member %d is not a dense merl brdf (kind %d)", m, b->dev.kind);
 		src[m] = b->dev.merl;
@@ -74,32 +77,18 @@ try {
 	std::vector<Params> resolved;
 	if (proxy_params && (st = resolve_all(cpu, n_materials, proxy_params, &resolved)) != DJB_OK) return st;
 
-	djb_merl_set *s = new djb_merl_set();
-	s->device = cpu ? -1 : ctx->device;
-	s->ctx = ctx;
-	s->n_mat = n_materials;
+	djb_merl_set *s = set_new<djb_merl_set>(ctx, n_materials);
 	const size_t tex_bytes = TABLE_BYTES * (size_t)n_materials, par_bytes = sizeof(Params) * (size_t)n_materials;
 	if (cpu) {
 		s->tex = (MerlTexel *)malloc(tex_bytes);
 		s->params = (Params *)calloc((size_t)n_materials, sizeof(Params));
 		if (!s->tex || !s->params) { djb_merl_set_destroy(s); return fail(DJB_ERR_OUT_OF_MEMORY, "djb_error: out of host memory (merl set of %d tables)", n_materials); }
 		for (int m = 0; m < n_materials; ++m) memcpy(s->tex + (size_t)m * (size_t)MERL_N, src[m], TABLE_BYTES);
-	} else {
-		if ((st = check_call(ctx, nullptr, 0, DJB_MEM_DEVICE)) != DJB_OK) { delete s; return st; }
-		std::lock_guard<std::recursive_mutex> call_lock(ctx->call_mu);
-		hipError_t e = hipMalloc((void **)&s->tex, tex_bytes);
-		if (e == hipSuccess) e = hipMalloc((void **)&s->params, par_bytes);
-		if (e == hipSuccess) e = hipMemsetAsync(s->params, 0, par_bytes, ctx->stream);
-		for (int m = 0; m < n_materials && e == hipSuccess; ++m)            // device to device, on the context's stream
-			e = hipMemcpyAsync(s->tex + (size_t)m * (size_t)MERL_N, src[m], TABLE_BYTES, hipMemcpyDeviceToDevice, ctx->stream);
-		if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);          // the sources may be destroyed as soon as this returns
-		if (e != hipSuccess) {
-			(void)hipGetLastError();
-			(void)hipStreamSynchronize(ctx->stream);
-			djb_merl_set_destroy(s);
-			return fail(DJB_ERR_HIP, "djb_error: HIP allocation / copy of a merl set of %d tables (%zu bytes): %s", n_materials, tex_bytes, hipGetErrorString(e));
-		}
-	}
+	} else if ((st = set_gpu_fill(s, djb_merl_set_destroy, "merl", n_materials, "tables", tex_bytes, [&] {
+		hipError_t e = hipMalloc((void **)&s->params, par_bytes);
+		if (e == hipSuccess) e = hipMemsetAsync(s->params, 0, par_bytes, ctx->stream);       // finished with the gather's synchronise
+		return e == hipSuccess ? set_gather(ctx, (void **)&s->tex, TABLE_BYTES, src) : e;
+	})) != DJB_OK) return st;
 	if (proxy_params && (st = install_params(s, resolved)) != DJB_OK) { djb_merl_set_destroy(s); return st; }
 	*out = s;
 	return DJB_OK;
@@ -127,34 +116,20 @@ DJB_ABI_CATCH
 
 djb_status djb_merl_set_destroy(djb_merl_set *s)
 try {
-	if (!s) return DJB_OK;
-	if (s->device < 0) { free(s->tex); free(s->params); }
-	else {
-		(void)hipSetDevice(s->device);
-		if (s->tex) (void)hipFree(s->tex);
-		if (s->params) (void)hipFree(s->params);
-	}
-	delete s;
-	return DJB_OK;
+	return s ? set_free(s, s->tex, s->params) : DJB_OK;
 }
 DJB_ABI_CATCH
 
 djb_status djb_merl_set_eval_batch(djb_ctx *ctx, const djb_merl_set *s, int64_t n, const int32_t *material, const djb_vec3_view *i,
                                    const djb_vec3_view *o, int want_cos, const djb_vec3_view *out_fr, int mem)
 try {
-	djb_status st = set_check(ctx, s);
+	djb_status st = set_check(ctx, s, "merl");
 	if (st != DJB_OK) return st;
 	if (is_cpu(ctx)) return djbcpu::merl_set_eval(ctx, s->tex, s->n_mat, n, material, i, o, want_cos, out_fr);
-	if ((st = check_call(ctx, nullptr, n, mem)) != DJB_OK) return st;
-	std::lock_guard<std::recursive_mutex> call_lock(ctx->call_mu);
-	Staged sg(ctx, n, mem);
-	const int32_t *dmat; View vi, vo, vout;
-	if ((st = stage_material(sg, material, &dmat)) != DJB_OK) return st;
-	if ((st = sg.in_vec(i, &vi)) != DJB_OK) return st;
-	if ((st = sg.in_vec(o, &vo)) != DJB_OK) return st;
-	if ((st = sg.out_vec(out_fr, &vout)) != DJB_OK) return st;
-	HIP_TRY(djbk::launch_merl_set_eval(ctx->stream, s->tex, s->n_mat, n, dmat, vi, vo, vout, want_cos != 0, ctx->merl_exact_only != 0));
-	return sg.finish();
+	SetBatch c(ctx, nullptr, n, mem, material, i, o, out_fr);
+	if (c.st != DJB_OK) return c.st;
+	HIP_TRY(djbk::launch_merl_set_eval(ctx->stream, s->tex, s->n_mat, n, c.dmat, c.vi, c.vo, c.vout, want_cos != 0, ctx->merl_exact_only != 0));
+	return c.sg.finish();
 }
 DJB_ABI_CATCH
 
@@ -162,18 +137,10 @@ djb_status djb_merl_set_evalp_is_proxy_batch(djb_ctx *ctx, const djb_merl_set *s
                                              const float *u1, const float *u2, const djb_vec3_view *o, const djb_vec3_view *out_weight,
                                              const djb_vec3_view *out_i, float *out_pdf, int mem)
 try {
-	djb_status st = set_check(ctx, s);
+	djb_status st = set_check(ctx, s, "merl");
 	if (st != DJB_OK) return st;
-	if (!proxy) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null brdf (proxy)");
-	if ((st = cpu_pair_check(ctx, proxy)) != DJB_OK) return st;
-	const bool cpu = is_cpu(ctx);
-	if (!cpu && (proxy->ctx != ctx || proxy->device != ctx->device))
-		return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: merl set and proxy belong to different contexts");
-	const int pkind = cpu ? djbcpu::kind(proxy) : proxy->dev.kind;
-	if (pkind != DJB_KIND_GGX && pkind != DJB_KIND_BECKMANN)
-		return fail(DJB_ERR_NOT_IMPLEMENTED, "djb_error: evalp_is_proxy on a merl set takes a ggx or beckmann proxy (proxy kind %d)", pkind);
-	if (!s->has_params) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: the merl set has no proxy parameters (djb_merl_set_set_proxy_params)");
-	if (cpu) return djbcpu::merl_set_evalp_is_proxy(ctx, s->tex, s->params, s->n_mat, proxy, n, material, u1, u2, o, out_weight, out_i, out_pdf);
+	if ((st = proxy_check(ctx, s, proxy, "evalp_is_proxy")) != DJB_OK) return st;
+	if (is_cpu(ctx)) return djbcpu::merl_set_evalp_is_proxy(ctx, s->tex, s->params, s->n_mat, proxy, n, material, u1, u2, o, out_weight, out_i, out_pdf);
 	if ((st = check_call(ctx, proxy, n, mem)) != DJB_OK) return st;
 	std::lock_guard<std::recursive_mutex> call_lock(ctx->call_mu);
 	Staged sg(ctx, n, mem);
@@ -194,31 +161,18 @@ DJB_ABI_CATCH
 djb_status djb_merl_set_evalp_pdf_proxy_batch(djb_ctx *ctx, const djb_merl_set *s, const djb_brdf *proxy, int64_t n, const int32_t *material,
                                               const djb_vec3_view *i, const djb_vec3_view *o, const djb_vec3_view *out_fr, float *out_pdf, int mem)
 try {
-	djb_status st = set_check(ctx, s);
+	djb_status st = set_check(ctx, s, "merl");
 	if (st != DJB_OK) return st;
-	if (!proxy) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null brdf (proxy)");
-	if ((st = cpu_pair_check(ctx, proxy)) != DJB_OK) return st;
-	const bool cpu = is_cpu(ctx);
-	if (!cpu && (proxy->ctx != ctx || proxy->device != ctx->device))
-		return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: merl set and proxy belong to different contexts");
-	const int pkind = cpu ? djbcpu::kind(proxy) : proxy->dev.kind;
-	if (pkind != DJB_KIND_GGX && pkind != DJB_KIND_BECKMANN)
-		return fail(DJB_ERR_NOT_IMPLEMENTED, "djb_error: evalp_pdf_proxy on a merl set takes a ggx or beckmann proxy (proxy kind %d)", pkind);
-	if (!s->has_params) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: the merl set has no proxy parameters (djb_merl_set_set_proxy_params)");
+	if ((st = proxy_check(ctx, s, proxy, "evalp_pdf_proxy")) != DJB_OK) return st;
 	if (!out_pdf) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null out_pdf (evalp alone: djb_merl_set_eval_batch)");
-	if (cpu) return djbcpu::merl_set_evalp_pdf(ctx, s->tex, s->params, s->n_mat, proxy, n, material, i, o, out_fr, out_pdf);
-	if ((st = check_call(ctx, proxy, n, mem)) != DJB_OK) return st;
-	std::lock_guard<std::recursive_mutex> call_lock(ctx->call_mu);
-	Staged sg(ctx, n, mem);
-	const int32_t *dmat; View vi, vo, vout; float *dpdf = nullptr;
-	if ((st = stage_material(sg, material, &dmat)) != DJB_OK) return st;
-	if ((st = sg.in_vec(i, &vi)) != DJB_OK) return st;
-	if ((st = sg.in_vec(o, &vo)) != DJB_OK) return st;
-	if ((st = sg.out_vec(out_fr, &vout)) != DJB_OK) return st;
-	if ((st = sg.out_arr(out_pdf, &dpdf)) != DJB_OK) return st;
-	HIP_TRY(djbk::launch_merl_set_evalp_pdf(ctx->stream, proxy->dev, s->params, s->tex, s->n_mat, n, dmat, vi, vo, vout, dpdf,
+	if (is_cpu(ctx)) return djbcpu::merl_set_evalp_pdf(ctx, s->tex, s->params, s->n_mat, proxy, n, material, i, o, out_fr, out_pdf);
+	SetBatch c(ctx, proxy, n, mem, material, i, o, out_fr);
+	if (c.st != DJB_OK) return c.st;
+	float *dpdf = nullptr;
+	if ((st = c.sg.out_arr(out_pdf, &dpdf)) != DJB_OK) return st;
+	HIP_TRY(djbk::launch_merl_set_evalp_pdf(ctx->stream, proxy->dev, s->params, s->tex, s->n_mat, n, c.dmat, c.vi, c.vo, c.vout, dpdf,
 	                                        ctx->merl_exact_only != 0));
-	return sg.finish();
+	return c.sg.finish();
 }
 DJB_ABI_CATCH
 

@@ -1,0 +1,102 @@
+// djb_set_host.hpp -- what the C ABIs of the three material sets share (djb_merl_set.hip, djb_utia_set.hip, djb_model_set.hip; included by
+// those alone): the checks of a handle, a member and a count, the construction and release of the resident block, and the entry of an eval
+// batch.  `what` is the set's noun in the messages: "merl" / "utia" / "model".  Everything works on djb_set_base (djb_host.hpp).
+#pragma once
+#include "djb_host.hpp"
+
+namespace djbh {
+
+// the set belongs to the call's context, as a djb_brdf does
+inline djb_status set_check(const djb_ctx *ctx, const djb_set_base *s, const char *what)
+{
+	if (!s) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null %s set", what);
+	if (!ctx) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null ctx");
+	if (is_cpu(ctx) != (s->device < 0))
+		return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: %s set and ctx belong to different back ends (CPU / GPU)", what);
+	if (s->ctx != ctx) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: the %s set belongs to another context", what);
+	return DJB_OK;
+}
+inline djb_status set_count_check(const char *what, int n, int max)
+{
+	if (n < 1 || n > max) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: a %s set holds 1 .. %d materials (got %d)", what, max, n);
+	return DJB_OK;
+}
+// member m of a GPU context's set is an object of that context (a CPU context's: djbcpu::*_set_member); its kind is each set's own test
+inline djb_status set_gpu_member(const djb_ctx *ctx, const djb_brdf *b, int m, const char *what)
+{
+	if (!b) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: %s set member %d is a null brdf", what, m);
+	if (is_cpu(b) || b->ctx != ctx || b->device != ctx->device)
+		return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: %s set member %d belongs to another context", what, m);
+	return DJB_OK;
+}
+
+template <class S> S *set_new(djb_ctx *ctx, int n_mat)
+{
+	S *s = new S();
+	s->device = is_cpu(ctx) ? -1 : ctx->device;
+	s->ctx = ctx;
+	s->n_mat = n_mat;
+	return s;
+}
+// the handle and its blocks, which live where the set's context computes
+template <class S, class... P> djb_status set_free(S *s, P *... blocks)
+{
+	if (s->device < 0) (free(blocks), ...);
+	else {
+		(void)hipSetDevice(s->device);
+		((blocks ? (void)hipFree(blocks) : (void)0), ...);
+	}
+	delete s;
+	return DJB_OK;
+}
+// A GPU set's resident block: `fill` allocates and fills it under the context's call lock and returns when the data is in place.  On an
+// error the set is destroyed; the message names `n` `unit`s ("tables" / "rows") and `bytes`.
+template <class S, class Fill>
+djb_status set_gpu_fill(S *s, djb_status (*destroy)(S *), const char *what, int n, const char *unit, size_t bytes, Fill fill)
+{
+	djb_ctx *ctx = s->ctx;
+	djb_status st = check_call(ctx, nullptr, 0, DJB_MEM_DEVICE);
+	if (st != DJB_OK) { delete s; return st; }
+	std::lock_guard<std::recursive_mutex> call_lock(ctx->call_mu);
+	const hipError_t e = fill();
+	if (e == hipSuccess) return DJB_OK;
+	(void)hipGetLastError();
+	(void)hipStreamSynchronize(ctx->stream);
+	destroy(s);
+	return fail(DJB_ERR_HIP, "djb_error: HIP allocation / copy of a %s set of %d %s (%zu bytes): %s", what, n, unit, bytes, hipGetErrorString(e));
+}
+// a fill: one block on the context's device, the equally sized device-resident sources gathered into it one after the other on the
+// context's stream; synchronised, so the sources may be destroyed as soon as this returns
+inline hipError_t set_gather(djb_ctx *ctx, void **block, size_t each, const std::vector<const void *> &src)
+{
+	hipError_t e = hipMalloc(block, each * src.size());
+	for (size_t m = 0; m < src.size() && e == hipSuccess; ++m)
+		e = hipMemcpyAsync((char *)*block + m * each, src[m], each, hipMemcpyDeviceToDevice, ctx->stream);
+	return e == hipSuccess ? hipStreamSynchronize(ctx->stream) : e;
+}
+
+// The entry of a batch call on a GPU context's set, after set_check and the CPU dispatch: check_call, the call lock (held while this
+// object lives), then the ids, i, o and the output where the kernels read and write them.  `st` is the first failure; the caller
+// launches on dmat / vi / vo / vout and returns sg.finish().
+struct SetBatch {
+	djb_status st;
+	std::unique_lock<std::recursive_mutex> call_lock;
+	Staged sg;
+	const int32_t *dmat = nullptr;
+	View vi, vo, vout;
+
+	SetBatch(djb_ctx *ctx, const djb_brdf *b, long long n, int mem, const int32_t *material, const djb_vec3_view *i, const djb_vec3_view *o,
+	         const djb_vec3_view *out)
+		: st(check_call(ctx, b, n, mem)),
+		  call_lock(st == DJB_OK ? std::unique_lock<std::recursive_mutex>(ctx->call_mu) : std::unique_lock<std::recursive_mutex>()),
+		  sg(ctx, n, mem)
+	{
+		if (st != DJB_OK) return;
+		if ((st = stage_material(sg, material, &dmat)) != DJB_OK) return;
+		if ((st = sg.in_vec(i, &vi)) != DJB_OK) return;
+		if ((st = sg.in_vec(o, &vo)) != DJB_OK) return;
+		st = sg.out_vec(out, &vout);
+	}
+};
+
+} // namespace djbh

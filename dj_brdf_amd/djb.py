@@ -1112,7 +1112,58 @@ class merl(brdf):
         return _get_samples(self)
 
 
-class merl_set:
+class _material_set:
+    """what merl_set, utia_set and model_set share: the id array of a batch, eval / evalp, and the handle's lifetime.  ``_C`` names the
+    set's C entry points (``{_C}_eval_batch``, ``{_C}_destroy``)."""
+
+    _C = None
+
+    @staticmethod
+    def _ids(material, like: _Vec):
+        if like.is_torch:
+            if not _is_dev(material):
+                material = torch.as_tensor(np.asarray(material.cpu() if hasattr(material, "cpu") else material).astype(np.int32), device=like.device)
+            material = material.to(torch.int32).contiguous()
+            n, ptr = material.numel(), material.data_ptr()
+        else:
+            material = np.ascontiguousarray(material.cpu().numpy() if hasattr(material, "cpu") else material, dtype=np.int32)
+            n, ptr = material.size, material.ctypes.data
+        if n != like.n or material.ndim != 1:
+            raise exc(1, f"djb_error: material must hold one int32 id per hit ({like.n}), got shape {tuple(material.shape)}")
+        return material, ptr
+
+    def _eval(self, material, i, o, want_cos):
+        vi, vo = _Vec(i), _Vec(o)
+        if vi.n != vo.n or vi.mem != vo.mem:
+            raise exc(1, "djb_error: i and o must have the same length and memory space")
+        keep, mp = self._ids(material, vi)
+        out = vi.like()
+        _lib.check(getattr(_lib.load(), f"{self._C}_eval_batch")(self.ctx._h, self._h, C.c_int64(vi.n), C.c_void_p(mp), C.byref(vi.view),
+                                                                 C.byref(vo.view), C.c_int(want_cos), C.byref(out.view), C.c_int(vi.mem)))
+        del keep
+        return out.keep
+
+    def eval(self, material, i, o):
+        """f_r of material[k] at (i_k, o_k)"""
+        return self._eval(material, i, o, 0)
+
+    def evalp(self, material, i, o):
+        """f_r * cos(theta_i) of material[k] at (i_k, o_k)"""
+        return self._eval(material, i, o, 1)
+
+    def close(self):
+        if self._h:
+            getattr(_lib.load(), f"{self._C}_destroy")(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class merl_set(_material_set):
     """M MERL materials resident in ONE block on their context's device, with one fitted proxy parameter set per material: hits that
     land on many measured materials are evaluated / importance-sampled / light-sampled in one call, each hit naming its material by id
     (djb_merl_set, include/djb_hip.h).  An extension: the reference's objects are one material each.
@@ -1120,6 +1171,8 @@ class merl_set:
     ``material``: int32 ids, one per hit; an id outside [0, M) marks an inactive hit (a dead path), whose outputs are all +0.
     An active hit gets the bits of the single-material call on its material.  Arrays: numpy (host) or torch CUDA (device), in the
     layouts the other operators take; the ids travel in the memory space of the directions."""
+
+    _C = "djb_merl_set"
 
     def __init__(self, brdfs, proxy_params=None, ctx: Optional[Context] = None):
         brdfs = list(brdfs)
@@ -1169,39 +1222,6 @@ class merl_set:
         self.set_proxy_params([microfacet.params.isotropic(float(a)) for a in ag])
         return ab, ag
 
-    @staticmethod
-    def _ids(material, like: _Vec):
-        if like.is_torch:
-            if not _is_dev(material):
-                material = torch.as_tensor(np.asarray(material.cpu() if hasattr(material, "cpu") else material).astype(np.int32), device=like.device)
-            material = material.to(torch.int32).contiguous()
-            n, ptr = material.numel(), material.data_ptr()
-        else:
-            material = np.ascontiguousarray(material.cpu().numpy() if hasattr(material, "cpu") else material, dtype=np.int32)
-            n, ptr = material.size, material.ctypes.data
-        if n != like.n or material.ndim != 1:
-            raise exc(1, f"djb_error: material must hold one int32 id per hit ({like.n}), got shape {tuple(material.shape)}")
-        return material, ptr
-
-    def _eval(self, material, i, o, want_cos):
-        vi, vo = _Vec(i), _Vec(o)
-        if vi.n != vo.n or vi.mem != vo.mem:
-            raise exc(1, "djb_error: i and o must have the same length and memory space")
-        keep, mp = self._ids(material, vi)
-        out = vi.like()
-        _lib.check(_lib.load().djb_merl_set_eval_batch(self.ctx._h, self._h, C.c_int64(vi.n), C.c_void_p(mp), C.byref(vi.view), C.byref(vo.view),
-                                                      C.c_int(want_cos), C.byref(out.view), C.c_int(vi.mem)))
-        del keep
-        return out.keep
-
-    def eval(self, material, i, o):
-        """f_r of material[k] at (i_k, o_k)"""
-        return self._eval(material, i, o, 0)
-
-    def evalp(self, material, i, o):
-        """f_r * cos(theta_i) of material[k] at (i_k, o_k)"""
-        return self._eval(material, i, o, 1)
-
     def evalp_is_proxy(self, proxy, material, u1, u2, o):
         """(weight, i, pdf) per hit as ``brdf.evalp_is_proxy``: direction and pdf from ``proxy`` (a ggx or beckmann object) with the
         hit's material's proxy parameters, f_r cos from the hit's material.  One kernel launch on the GPU."""
@@ -1232,17 +1252,6 @@ class merl_set:
         del keep
         return fr.keep, pdf
 
-    def close(self):
-        if self._h:
-            _lib.load().djb_merl_set_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 class utia(brdf):
     """djb::utia(filename) (dj_brdf.h:136-146, 1039-1059)."""
@@ -1265,7 +1274,7 @@ class utia(brdf):
         return _get_samples(self)
 
 
-class utia_set:
+class utia_set(_material_set):
     """M UTIA materials resident in ONE block on their context's device: hits that land on many measured materials are evaluated in one
     call, each hit naming its material by id (djb_utia_set, include/djb_hip.h).  An extension: the reference's objects are one material
     each.  ``eval`` / ``evalp`` are all that dj_utia asks of its table (it samples the cosine hemisphere), so there is no proxy.
@@ -1273,6 +1282,8 @@ class utia_set:
     ``material``: int32 ids, one per hit; an id outside [0, M) marks an inactive hit (a dead path), whose output is +0.  An active
     hit gets the bits of the single-material call on its material.  Arrays: numpy (host) or torch CUDA (device), in the layouts the
     other operators take; the ids travel in the memory space of the directions."""
+
+    _C = "djb_utia_set"
 
     def __init__(self, brdfs, ctx: Optional[Context] = None):
         brdfs = list(brdfs)
@@ -1298,38 +1309,8 @@ class utia_set:
         _lib.check(_lib.load().djb_utia_set_info(self._h, C.byref(n)))
         return n.value
 
-    def _eval(self, material, i, o, want_cos):
-        vi, vo = _Vec(i), _Vec(o)
-        if vi.n != vo.n or vi.mem != vo.mem:
-            raise exc(1, "djb_error: i and o must have the same length and memory space")
-        keep, mp = merl_set._ids(material, vi)
-        out = vi.like()
-        _lib.check(_lib.load().djb_utia_set_eval_batch(self.ctx._h, self._h, C.c_int64(vi.n), C.c_void_p(mp), C.byref(vi.view), C.byref(vo.view),
-                                                      C.c_int(want_cos), C.byref(out.view), C.c_int(vi.mem)))
-        del keep
-        return out.keep
 
-    def eval(self, material, i, o):
-        """f_r of material[k] at (i_k, o_k)"""
-        return self._eval(material, i, o, 0)
-
-    def evalp(self, material, i, o):
-        """f_r * cos(theta_i) of material[k] at (i_k, o_k)"""
-        return self._eval(material, i, o, 1)
-
-    def close(self):
-        if self._h:
-            _lib.load().djb_utia_set_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class model_set:
+class model_set(_material_set):
     """M sgd or abc materials -- parameter rows of ONE kind -- resident in ONE block on their context's device: hits that land on many
     data-driven materials are evaluated in one call, each hit naming its material by id (djb_model_set, include/djb_hip.h).  An extension:
     the reference's objects are one material each.  ``eval`` / ``evalp`` are all that dj_sgd / dj_abc ask of their object (they sample
@@ -1340,6 +1321,7 @@ class model_set:
     whose output is +0.  An active hit gets the bits of the single-material call on its material.  Arrays: numpy (host) or torch CUDA
     (device), in the layouts the other operators take; the ids travel in the memory space of the directions."""
 
+    _C = "djb_model_set"
     _KINDS = {"sgd": 6, "abc": 7}            # DJB_KIND_SGD, DJB_KIND_ABC
 
     def __init__(self, brdfs, ctx: Optional[Context] = None):
@@ -1393,36 +1375,6 @@ class model_set:
     @property
     def n_materials(self) -> int:
         return self._info()[1]
-
-    def _eval(self, material, i, o, want_cos):
-        vi, vo = _Vec(i), _Vec(o)
-        if vi.n != vo.n or vi.mem != vo.mem:
-            raise exc(1, "djb_error: i and o must have the same length and memory space")
-        keep, mp = merl_set._ids(material, vi)
-        out = vi.like()
-        _lib.check(_lib.load().djb_model_set_eval_batch(self.ctx._h, self._h, C.c_int64(vi.n), C.c_void_p(mp), C.byref(vi.view), C.byref(vo.view),
-                                                       C.c_int(want_cos), C.byref(out.view), C.c_int(vi.mem)))
-        del keep
-        return out.keep
-
-    def eval(self, material, i, o):
-        """f_r of material[k] at (i_k, o_k)"""
-        return self._eval(material, i, o, 0)
-
-    def evalp(self, material, i, o):
-        """f_r * cos(theta_i) of material[k] at (i_k, o_k)"""
-        return self._eval(material, i, o, 1)
-
-    def close(self):
-        if self._h:
-            _lib.load().djb_model_set_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # --------------------------------------------------------------------------- user-defined BRDFs (dj_brdf.h:74-109)

@@ -247,6 +247,33 @@ def test_in_place_call_equals_out_of_place(gpu_ctx, uset, layout):
     cases.assert_eval(f"in place, {layout}, against the oracle", got, cases.grid_expected("evalp"), np.ones(n, bool))
 
 
+def test_output_over_the_ids_equals_out_of_place(gpu_ctx, uset):
+    """The ids are an input stream too: the x plane of the output is the id array itself, index-aligned.  Tier 1 declines the block's hits
+    and tier 2 would re-read their ids after tier 1 wrote placeholders over them, so the call has to take the exact kernel -- with the
+    default worklist, and with a worklist of 0 entries, where tier 2 would redo the whole batch."""
+    import torch
+    ids, i, o = cases.grid_block()
+    n = len(ids)
+    dev = _dev(gpu_ctx)
+    want = _call(uset, ids, i, o, 1, "dense")
+    di, do = (torch.from_numpy(np.array(a.T, order="C")).to(dev) for a in (i, o))
+    vi, vo = _view(di.data_ptr(), n, "dense"), _view(do.data_ptr(), n, "dense")
+    try:
+        for cap in (-1, 0):
+            djb.set_test_worklist_cap(gpu_ctx, cap)
+            host = np.zeros((3, n), np.float32)
+            host.view(np.int32)[0] = ids                   # plane 0: the int32 bits of the ids
+            buf = torch.from_numpy(host).to(dev)
+            _lib.check(_lib.load().djb_utia_set_eval_batch(gpu_ctx._h, uset._h, C.c_int64(n), C.c_void_p(buf.data_ptr()), C.byref(vi), C.byref(vo), C.c_int(1),
+                                                           C.byref(_view(buf.data_ptr(), n, "dense")), C.c_int(_lib.MEM_DEVICE)))
+            torch.cuda.synchronize()
+            got = buf.cpu().numpy().T
+            cases.assert_eval(f"output over the ids, cap {cap}", got, want, np.ones(n, bool))
+            cases.assert_eval(f"output over the ids, cap {cap}, against the oracle", got, cases.grid_expected("evalp"), np.ones(n, bool))
+    finally:
+        djb.set_test_worklist_cap(gpu_ctx, -1)
+
+
 # ------------------------------------------------------------------ 8. contexts
 def test_a_set_of_another_context_is_refused(gpu_ctx, uset):
     lib = _lib.load()

@@ -75,6 +75,8 @@ EXPORTS = [
     "djb_merl_set_evalp_is_proxy_batch", "djb_merl_set_evalp_pdf_proxy_batch",
     "djb_utia_set_create", "djb_utia_set_info", "djb_utia_set_destroy", "djb_utia_set_eval_batch",
     "djb_model_set_create", "djb_model_set_create_from_brdfs", "djb_model_set_info", "djb_model_set_destroy", "djb_model_set_eval_batch",
+    "djb_model_set_fit_proxy", "djb_model_set_proxy_info", "djb_model_set_get_proxy", "djb_model_set_evalp_is_proxy_batch",
+    "djb_model_set_evalp_pdf_proxy_batch",
 ]
 
 _lib = None
@@ -112,6 +114,11 @@ def load() -> C.CDLL:
     lib.djb_model_set_info.argtypes = [P, P, P]
     lib.djb_model_set_destroy.argtypes = [P]
     lib.djb_model_set_eval_batch.argtypes = [P, P, C.c_int64, P, P, P, C.c_int, P, C.c_int]
+    lib.djb_model_set_fit_proxy.argtypes = [P, P, C.c_int, C.c_int]
+    lib.djb_model_set_proxy_info.argtypes = [P, P, P]
+    lib.djb_model_set_get_proxy.argtypes = [P, C.c_int, C.c_int, P, P]
+    lib.djb_model_set_evalp_is_proxy_batch.argtypes = [P, P, C.c_int64, P, P, P, P, P, P, P, C.c_int]
+    lib.djb_model_set_evalp_pdf_proxy_batch.argtypes = [P, P, C.c_int64, P, P, P, P, P, C.c_int]
     if lib.djb_version() // 100 != ABI_VERSION // 100:
         raise ImportError(f"{LIB_PATH} has ABI version {lib.djb_version()}, this binding was written against {ABI_VERSION} "
                           "(include/djb_hip.h: DJB_HIP_VERSION) -- rebuild the library")

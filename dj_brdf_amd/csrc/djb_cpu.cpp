@@ -1075,20 +1075,114 @@ djb_status model_set_member(const djb_ctx *ctx, const djb_brdf *b, int index, in
 	*row = B(b)->model.data();
 	return DJB_OK;
 }
+// row m of double[n_mat][33 or 9] becomes the Brdf's `model`, with create_model's Fresnel operands for it
+template <int KIND> static void bind_model_row(Brdf &tb, const double *rows, unsigned int m)
+{
+	const double *row = rows + (size_t)m * (KIND == KIND_SGD ? 33 : 9);
+	tb.model = row; tb.fr.kind = KIND == KIND_SGD ? FR_SGD : FR_UNPOLARIZED;
+	if (KIND == KIND_SGD) for (int c = 0; c < 3; ++c) { tb.fr.a[c] = (float)row[12 + c]; tb.fr.b[c] = (float)row[15 + c]; }
+	else for (int c = 0; c < 3; ++c) tb.fr.a[c] = (float)row[8];
+}
 djb_status model_set_eval(djb_ctx *ctx, int kind, const double *rows, int n_mat, int64_t n, const int32_t *material, const djb_vec3_view *i,
                           const djb_vec3_view *o, int want_cos, const djb_vec3_view *out_fr)
 {
 	if (kind == KIND_SGD)
-		return set_eval<KIND_SGD>(ctx, n_mat, n, material, i, o, want_cos, out_fr, [rows](Brdf &tb, unsigned int m) {
-			const double *row = rows + (size_t)m * 33;
-			tb.model = row; tb.fr.kind = FR_SGD;
-			for (int c = 0; c < 3; ++c) { tb.fr.a[c] = (float)row[12 + c]; tb.fr.b[c] = (float)row[15 + c]; }
-		});
-	return set_eval<KIND_ABC>(ctx, n_mat, n, material, i, o, want_cos, out_fr, [rows](Brdf &tb, unsigned int m) {
-		const double *row = rows + (size_t)m * 9;
-		tb.model = row; tb.fr.kind = FR_UNPOLARIZED;
-		for (int c = 0; c < 3; ++c) tb.fr.a[c] = (float)row[8];
+		return set_eval<KIND_SGD>(ctx, n_mat, n, material, i, o, want_cos, out_fr, [rows](Brdf &tb, unsigned int m) { bind_model_row<KIND_SGD>(tb, rows, m); });
+	return set_eval<KIND_ABC>(ctx, n_mat, n, material, i, o, want_cos, out_fr, [rows](Brdf &tb, unsigned int m) { bind_model_row<KIND_ABC>(tb, rows, m); });
+}
+// the fitted tabular proxies of a model set (djb_model_set_fit_proxy): block = float[n_mat][3][res] -- p22, sigma, qf of tabular(model_m, res,
+// shadow) one after the other -- then int n_qf[n_mat]; each material fitted as create_tabular fits the single object
+djb_status model_set_fit_proxy(djb_ctx *ctx, int kind, const double *rows, int n_mat, int res, int shadow, float *block)
+{
+	if (res <= 2) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: Invalid Resolution");   // dj_brdf.h:2218
+	Params std_p;
+	djb_status st = params_for(nullptr, -1, &std_p);
+	if (st != DJB_OK) return st;
+	int *n_qf = (int *)(block + 3 * (size_t)n_mat * (size_t)res);
+	parallel_for(C(ctx), n_mat, 1, [&](long long m0, long long m1) {
+		for (long long m = m0; m < m1; ++m) {
+			Brdf src; memset(&src, 0, sizeof src); src.kind = kind; src.shadow = 1;
+			if (kind == KIND_SGD) bind_model_row<KIND_SGD>(src, rows, (unsigned int)m); else bind_model_row<KIND_ABC>(src, rows, (unsigned int)m);
+			FitResult R;
+			fit_tabular(src, std_p, res, shadow != 0, R);
+			float *dst = block + 3 * (size_t)m * (size_t)res;
+			memcpy(dst, R.p22.data(), sizeof(float) * (size_t)res);
+			memcpy(dst + res, R.sigma.data(), sizeof(float) * (size_t)res);
+			memcpy(dst + 2 * (size_t)res, R.qf.data(), sizeof(float) * (size_t)res);
+			n_qf[m] = R.n_qf;
+		}
 	});
+	return DJB_OK;
+}
+// the two per-hit steps against those proxies: proxy_loop / proxy_light_loop above per hit with target = model(row_m), proxy = the tabular
+// lobe of material m and params::standard() for it; an inactive hit is +0 in every output, and so is a light-sample hit below the horizon
+// LIGHT: a = i (given), outputs fr and pdf; else a is not read, u1a / u2a are, outputs weight, i and pdf
+template <int KIND, bool LIGHT>
+void model_set_proxy_loop(const double *rows, int n_mat, const float *block, int res, int shadow, const Params &pp, long long k0, long long k1,
+                          const int32_t *material, const float *u1a, const float *u2a, const View &va, const View &vo, const View &vfr,
+                          const View &vi_out, float *out_pdf)
+{
+	const GlibcTabs gt = glibc_tabs_global();
+	const int *n_qf = (const int *)(block + 3 * (size_t)n_mat * (size_t)res);
+	Brdf tb; memset(&tb, 0, sizeof tb); tb.kind = KIND;
+	Brdf pb; memset(&pb, 0, sizeof pb); pb.kind = KIND_TABULAR; pb.shadow = shadow != 0; pb.n_p22 = pb.n_sigma = res;
+	Params tp; memset(&tp, 0, sizeof tp);
+	for (long long k = k0; k < k1; ++k) {
+		v3 fr = mk(0, 0, 0), i_ = mk(0, 0, 0); float pdf = 0.0f;
+		const unsigned int m = (unsigned int)material[k];
+		if (m < (unsigned int)n_mat) {
+			const v3 o = load3(vo, k);
+			if (LIGHT) i_ = load3(va, k);
+			if (!LIGHT || !(i_.z <= 0.0f || o.z <= 0.0f)) {                             // the light sample's guard reads neither row nor table
+				const float *tab = block + 3 * (size_t)m * (size_t)res;
+				pb.p22 = tab; pb.sigma = tab + res; pb.qf = tab + 2 * (size_t)res; pb.n_qf = n_qf[m];
+				v3 unused_w; float unused_pdf;
+				if (!LIGHT) sample_one<KIND_TABULAR, false>(pb, pp, u1a[k], u2a[k], o, gt, i_, unused_w, unused_pdf);
+				if (LIGHT || !(i_.z <= 0.0f)) {                                         // the plugins' side check; a NaN i.z passes
+					v3 unused_fr = mk(0, 0, 0);
+					bind_model_row<KIND>(tb, rows, m);
+					eval_one<KIND_TABULAR, 4>(pb, pp, i_, o, unused_fr, pdf);
+					eval_one<KIND, 2>(tb, tp, i_, o, fr, unused_pdf);
+					if (!LIGHT) fr = divs(fr, pdf);
+				}
+			}
+		}
+		store3(vfr, k, fr); out_pdf[k] = pdf;
+		if (!LIGHT) store3(vi_out, k, i_);
+	}
+}
+template <bool LIGHT>
+static djb_status model_set_proxy_run(djb_ctx *ctx, int kind, const double *rows, int n_mat, const float *block, int res, int shadow, int64_t n,
+                                      const int32_t *material, const float *u1, const float *u2, const View &va, const View &vo, const View &vfr,
+                                      const View &vi_out, float *out_pdf)
+{
+	Params pp;
+	djb_status st = params_for(nullptr, KIND_TABULAR, &pp);
+	if (st != DJB_OK) return st;
+	parallel_for(C(ctx), n, 2048, [&](long long k0, long long k1) {
+		if (kind == KIND_SGD) model_set_proxy_loop<KIND_SGD, LIGHT>(rows, n_mat, block, res, shadow, pp, k0, k1, material, u1, u2, va, vo, vfr, vi_out, out_pdf);
+		else model_set_proxy_loop<KIND_ABC, LIGHT>(rows, n_mat, block, res, shadow, pp, k0, k1, material, u1, u2, va, vo, vfr, vi_out, out_pdf);
+	});
+	return DJB_OK;
+}
+djb_status model_set_evalp_is_proxy(djb_ctx *ctx, int kind, const double *rows, int n_mat, const float *block, int res, int shadow, int64_t n,
+                                    const int32_t *material, const float *u1, const float *u2, const djb_vec3_view *o, const djb_vec3_view *out_w,
+                                    const djb_vec3_view *out_i, float *out_pdf)
+{
+	djb_status st = set_batch_head(n, material);
+	if (st != DJB_OK) return st;
+	if (!u1 || !u2 || !valid(o) || !valid(out_w) || !valid(out_i) || !out_pdf) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null argument");
+	const View none = { nullptr, nullptr, nullptr, 0 };
+	return model_set_proxy_run<false>(ctx, kind, rows, n_mat, block, res, shadow, n, material, u1, u2, none, view_of(o), view_of(out_w), view_of(out_i), out_pdf);
+}
+djb_status model_set_evalp_pdf(djb_ctx *ctx, int kind, const double *rows, int n_mat, const float *block, int res, int shadow, int64_t n,
+                               const int32_t *material, const djb_vec3_view *i, const djb_vec3_view *o, const djb_vec3_view *out_fr, float *out_pdf)
+{
+	djb_status st = set_batch_args(n, material, i, o, out_fr);
+	if (st != DJB_OK) return st;
+	if (!out_pdf) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null output");
+	const View none = { nullptr, nullptr, nullptr, 0 };
+	return model_set_proxy_run<true>(ctx, kind, rows, n_mat, block, res, shadow, n, material, nullptr, nullptr, view_of(i), view_of(o), view_of(out_fr), none, out_pdf);
 }
 // the two MERL-set proxy loops: proxy_loop / proxy_light_loop above per hit, the table and the proxy's parameters selected by the hit's id
 template <int PK>

@@ -114,6 +114,14 @@ djb_status utia_set_eval(djb_ctx *, const void *records, int n_mat, int64_t n, c
 djb_status model_set_member(const djb_ctx *ctx, const djb_brdf *b, int index, int *kind, const double **row);
 djb_status model_set_eval(djb_ctx *, int kind, const double *rows, int n_mat, int64_t n, const int32_t *material, const djb_vec3_view *i,
                           const djb_vec3_view *o, int want_cos, const djb_vec3_view *out_fr);
+// the set's fitted tabular proxies: block = float[n_mat][3][res] (p22, sigma, qf of tabular(model_m, res, shadow)) then int n_qf[n_mat], host
+// memory; and the two per-hit steps against them (evalp_is_proxy / evalp_pdf_proxy above with target = model_m, proxy = that lobe, no params)
+djb_status model_set_fit_proxy(djb_ctx *, int kind, const double *rows, int n_mat, int res, int shadow, float *block);
+djb_status model_set_evalp_is_proxy(djb_ctx *, int kind, const double *rows, int n_mat, const float *block, int res, int shadow, int64_t n,
+                                    const int32_t *material, const float *u1, const float *u2, const djb_vec3_view *o, const djb_vec3_view *out_w,
+                                    const djb_vec3_view *out_i, float *out_pdf);
+djb_status model_set_evalp_pdf(djb_ctx *, int kind, const double *rows, int n_mat, const float *block, int res, int shadow, int64_t n,
+                               const int32_t *material, const djb_vec3_view *i, const djb_vec3_view *o, const djb_vec3_view *out_fr, float *out_pdf);
 djb_status eval_pp(djb_ctx *, const djb_brdf *, int64_t n, const djb_vec3_view *i, const djb_vec3_view *o, const float *rec,
                    int mode, const float *base5, float scale, int lean_flags, int want, const djb_vec3_view *out_fr, float *out_pdf,
                    float *out_pp);

@@ -148,10 +148,15 @@ struct djb_utia_set : djb_set_base {
 
 // an SGD / ABC model set (djb_model_set.hip): M parameter rows of one kind in one block where the set's context computes.  GPU context:
 // double[M][stride] in HBM, each row as create_model uploads the single one (sgd: 61 doubles, abc: 9).  CPU context: the rows as given,
-// double[M][33 or 9] in host memory.  Immutable after its constructor returned.
+// double[M][33 or 9] in host memory.  The rows are immutable after the constructor returned.  The proxy block -- the tables of
+// tabular(model_m, res, shadow) that sampling and the pdf read -- is float[M][3][res] (p22, sigma, qf of each material) followed by
+// int n_qf[M]; djb_model_set_fit_proxy replaces it in stream order on the context's stream.
 struct djb_model_set : djb_set_base {
 	int kind = 0;                    // DJB_KIND_SGD or DJB_KIND_ABC
 	double *rows = nullptr;
+	int proxy_res = 0, proxy_shadow = 0;     // proxy_res == 0: no proxy yet
+	std::vector<float> proxy_host;   // the block in host memory: what a CPU context computes on, and what djb_model_set_get_proxy reads
+	float *proxy_dev = nullptr;      // GPU context: the block in HBM
 };
 
 namespace djbh {
@@ -452,6 +457,8 @@ djb_status alloc_brdf(djb_ctx *ctx, int kind, djb_brdf **out);
 djb_status upload_floats(djb_brdf *b, const float *host, size_t count, const float **dev_out);
 djb_status set_fresnel(djb_brdf *b, const djb_fresnel_desc *f);
 djb_status create_microfacet(djb_ctx *ctx, int kind, const djb_fresnel_desc *f, int shadow, djb_brdf **out);
+// the k_fit launch of n device views of one kind (djb_host_fit.hip: run_fit), p22 / sigma / qf [n][res] and n_qf [n] back in host memory
+djb_status fit_tables(djb_ctx *ctx, const std::vector<Brdf> &srcs, int src_kind, int res, int shadow, float *p22, float *sigma, float *qf, int *n_qf);
 } // namespace djbh
 namespace djbk {
 // per-slot rgb samples in HBM as a fit source (djbdev::Brdf::merl_sparse; djb_host.hip): never handed to the eval kernels

@@ -425,3 +425,12 @@ try {
 DJB_ABI_CATCH
 
 } // extern "C"
+
+namespace djbh {
+// the fit of the n_mat device views `srcs` (all of kind src_kind) for a caller outside this file (djb_model_set.hip): the tables that stay
+// resident with a model set and the per-material count of valid qf entries, [n_mat][res] each; the caller holds ctx->call_mu
+djb_status fit_tables(djb_ctx *ctx, const std::vector<Brdf> &srcs, int src_kind, int res, int shadow, float *p22, float *sigma, float *qf, int *n_qf)
+{
+	return run_fit(ctx, srcs, src_kind, res, shadow, nullptr, nullptr, p22, sigma, nullptr, qf, nullptr, n_qf);
+}
+} // namespace djbh

@@ -145,6 +145,21 @@ hipError_t launch_utia_set_eval(hipStream_t s, const float4 *tab, int n_mat, lon
 int model_set_row_stride(int kind);
 hipError_t launch_model_set_eval(hipStream_t s, int kind, const double *rows, int n_mat, bool rows_global, long long n, const int32_t *material,
                                  const View &i, const View &o, const View &out, bool want_cos);
+// ... and the two per-hit steps against the set's fitted tabular proxies (djb_kernels_model_set_proxy.hip).  tab: the resident proxy block,
+// float[n_mat][3][res] (p22, sigma, qf of each material) followed by int n_qf[n_mat]; n_mat * res <= MODEL_SET_PROXY_MAX_ENTRIES keeps
+// every byte offset into it below 2^31.  proxy_p: params::standard() as the single-material call resolves NULL proxy params.
+// evalp_is_proxy: i = proxy_m.sample(u1, u2, o), pdf = proxy_m.pdf(i, o), weight = model_m.evalp(i, o) / pdf, weight = 0 and pdf = 0 where
+// i.z <= 0; evalp_pdf: fr = model_m.evalp(i, o), pdf = proxy_m.pdf(i, o), both +0 where i.z <= 0 || o.z <= 0.  An inactive hit: +0 in every
+// output.  One launch each; one trip of the grid covers MODEL_SET_PROXY_TRIP hits
+constexpr long long MODEL_SET_PROXY_MAX_ENTRIES = 1LL << 27;
+constexpr long long MODEL_SET_PROXY_TRIP = 256LL * 16 * 256;
+struct ModelSetProxy { const float *tab; int res, shadow; };
+hipError_t launch_model_set_evalp_is_proxy(hipStream_t s, int kind, const double *rows, int n_mat, bool rows_global, const ModelSetProxy &proxy,
+                                           const Params &proxy_p, long long n, const int32_t *material, const float *u1, const float *u2,
+                                           const View &o, const View &out_w, const View &out_i, float *out_pdf);
+hipError_t launch_model_set_evalp_pdf(hipStream_t s, int kind, const double *rows, int n_mat, bool rows_global, const ModelSetProxy &proxy,
+                                      const Params &proxy_p, long long n, const int32_t *material, const View &i, const View &o,
+                                      const View &out_fr, float *out_pdf);
 hipError_t launch_fast_trig_selftest(hipStream_t s, long long n, int mode, uint32_t first, uint32_t seed, unsigned long long *counters4);
 // DJB_OPT_CONTRACT_1E5 (djb_kernels_contract.hip): GGX eval / evalp / pdf inside the 1e-5 value contract, two-tier like
 // the MERL lookup, with a sharded worklist (list: cap records of 32 bytes in total, count: CONTRACT_SHARDS uint32, CONTRACT_COUNTER_STRIDE words apart: the record

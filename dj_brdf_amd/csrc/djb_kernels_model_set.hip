@@ -41,7 +41,7 @@ namespace {
 constexpr int BLOCK = 256;
 constexpr long long GRID_CAP = 256LL * 16;                 // as k_eval for these kinds (djb_kernels_eval.hip)
 
-constexpr int row_stride(int kind) { return kind == KIND_SGD ? (int)SGD_FAST_ROW : 9; }                 // doubles per resident row
+#include "djb_model_set_unit.inc"                                                                        // row_stride, unit
 constexpr int rows_lds(int kind) { return kind == KIND_SGD ? 101 : 213; }                                 // the LDS budget, in rows (above)
 // Registers (tools/kernel_resources.sh, profiles/model_set/kernel_resources.txt): the coefficients that k_eval holds in SGPRs are VGPR pairs
 // here.  sgd: 124 (dense) / 127 (strided) VGPRs against k_eval<SGD>'s 87 / 73 -- 4 waves per SIMD instead of 5 / 6, no scratch; abc: 64 (dense,
@@ -52,21 +52,6 @@ constexpr int min_waves(int kind) { return kind == KIND_SGD ? 4 : 7; }
 static_assert(2048 + 3072 + 128 + 8 * rows_lds(KIND_SGD) * row_stride(KIND_SGD) <= 163840 / 3, "sgd: three workgroups per CU");
 static_assert(2048 + 3072 + 8 + 8 * rows_lds(KIND_ABC) * row_stride(KIND_ABC) <= 163840 / 8, "abc: eight workgroups per CU");
 static_assert(65536ull * 8ull * (unsigned long long)row_stride(KIND_SGD) < (1ull << 31), "the byte offset of the last row fits 32 bits");
-
-// one active hit: the hit's row becomes the lane's Brdf -- `model` and the Fresnel operands create_model derives from the row
-template <int KIND, int WANT>
-DJB_DEV void unit(Brdf b, const double *m, v3 i, v3 o, v3 &fr)
-{
-	b.model = m;
-	b.fr.kind = KIND == KIND_SGD ? FR_SGD : FR_UNPOLARIZED;      // a compile-time constant here: fresnel_eval's switch folds to the kind's term
-	if (KIND == KIND_SGD) {
-#pragma unroll
-		for (int c = 0; c < 3; ++c) { b.fr.a[c] = (float)m[12 + c]; b.fr.b[c] = (float)m[15 + c]; }
-	} else b.fr.a[0] = b.fr.a[1] = b.fr.a[2] = (float)m[8];
-	const Params none = {};
-	float pdf = 0.0f;
-	eval_one<KIND, WANT>(b, none, i, o, fr, pdf);
-}
 
 template <int KIND, int WANT, bool DENSE>
 __global__ __launch_bounds__(BLOCK, min_waves(KIND)) void k_model_set(Brdf b, const double *rows, int n_mat, int in_lds, long long n, const int32_t *mat,

@@ -1,6 +1,7 @@
 // djb_model_set.hip -- the C ABI of SGD / ABC model sets (include/djb_hip.h: djb_model_set): M resident parameter rows of one kind in one
-// block, evaluated per hit by material id.  Kernels: djb_kernels_model_set.hip; host loop (CPU contexts): djb_cpu.cpp; what the three kinds
-// of set share: djb_set_host.hpp.  A set has no host twin: on a GPU context a host batch of any size is staged to the device.
+// block, evaluated per hit by material id, and -- once fitted -- the tables of each row's tabular proxy in a second block, sampled and
+// light-sampled per hit.  Kernels: djb_kernels_model_set.hip, djb_kernels_model_set_proxy.hip; host loops (CPU contexts): djb_cpu.cpp; what
+// the three kinds of set share: djb_set_host.hpp.  A set has no host twin: on a GPU context a host batch of any size is staged to the device.
 #include "djb_set_host.hpp"
 
 using namespace djbh;
@@ -48,7 +49,69 @@ djb_status create(djb_ctx *ctx, int kind, int n_materials, const double *rows, d
 	return DJB_OK;
 }
 
+// the proxy block of M materials at resolution res: float[M][3][res], then int n_qf[M]
+size_t proxy_floats(int n_mat, int res) { return 3 * (size_t)n_mat * (size_t)res + (size_t)n_mat; }
+
+// A GPU set's fit.  The device views are built straight onto the resident rows -- the block holds each row as create_model builds the
+// single one -- with create_model's Fresnel operands, read from a host copy of the block.  launch_fit runs on chunks of FIT_CHUNK = 128
+// materials: with fit_parts that is one workgroup per CU of a 256-CU device, and it bounds the fitter's work arrays (km: n * parts *
+// (res - 1)^2 doubles, 16 MB per chunk at res 90 with 2 parts; the ratio scratch 12 MB), which run_fit takes from the context's staging
+// pool, whatever M is.  A material's tables do not depend on the chunk it is fitted in: the fitter's workgroups share nothing across
+// materials, and its slices (fit_parts) are value-neutral.
+constexpr int FIT_CHUNK = 128;
+djb_status fit_gpu(djb_ctx *ctx, const djb_model_set *s, int res, int shadow, std::vector<float> *block)
+{
+	const int M = s->n_mat, stride = djbk::model_set_row_stride(s->kind);
+	std::vector<double> rows((size_t)stride * (size_t)M);
+	HIP_TRY(hipStreamSynchronize(ctx->stream));
+	HIP_TRY(hipMemcpy(rows.data(), s->rows, sizeof(double) * rows.size(), hipMemcpyDeviceToHost));
+	std::vector<float> p22, sigma, qf;
+	std::vector<int> n_qf;
+	int *n_qf_out = (int *)(block->data() + 3 * (size_t)M * (size_t)res);
+	for (int m0 = 0; m0 < M; m0 += FIT_CHUNK) {
+		const int cnt = std::min(FIT_CHUNK, M - m0);
+		std::vector<Brdf> srcs((size_t)cnt);
+		for (int c = 0; c < cnt; ++c) {
+			Brdf &b = srcs[c];
+			const double *row = rows.data() + (size_t)(m0 + c) * stride;
+			memset(&b, 0, sizeof b);
+			b.kind = s->kind; b.shadow = 1;
+			b.model = s->rows + (size_t)(m0 + c) * stride;
+			if (s->kind == DJB_KIND_SGD) {
+				b.fr.kind = djbdev::FR_SGD;
+				for (int k = 0; k < 3; ++k) { b.fr.a[k] = (float)row[12 + k]; b.fr.b[k] = (float)row[15 + k]; }
+			} else {
+				b.fr.kind = djbdev::FR_UNPOLARIZED;
+				for (int k = 0; k < 3; ++k) b.fr.a[k] = (float)row[8];
+			}
+		}
+		const size_t each = (size_t)cnt * (size_t)res;
+		p22.resize(each); sigma.resize(each); qf.resize(each); n_qf.resize((size_t)cnt);
+		djb_status st = fit_tables(ctx, srcs, s->kind, res, shadow, p22.data(), sigma.data(), qf.data(), n_qf.data());
+		if (st != DJB_OK) return st;
+		for (int c = 0; c < cnt; ++c) {                                               // gather: [chunk][res] per table -> [M][3][res]
+			float *dst = block->data() + 3 * (size_t)(m0 + c) * (size_t)res;
+			memcpy(dst, p22.data() + (size_t)c * res, sizeof(float) * (size_t)res);
+			memcpy(dst + res, sigma.data() + (size_t)c * res, sizeof(float) * (size_t)res);
+			memcpy(dst + 2 * (size_t)res, qf.data() + (size_t)c * res, sizeof(float) * (size_t)res);
+			n_qf_out[m0 + c] = n_qf[c];
+		}
+	}
+	return DJB_OK;
+}
+
+// the checks the two per-hit proxy calls share, before anything is written
+djb_status proxy_call_check(const djb_ctx *ctx, const djb_model_set *s)
+{
+	djb_status st = set_check(ctx, s, "model");
+	if (st != DJB_OK) return st;
+	if (!s->proxy_res) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: the model set has no proxy (djb_model_set_fit_proxy)");
+	return DJB_OK;
+}
+
 } // namespace
+
+static_assert(DJB_MODEL_SET_PROXY_MAX_ENTRIES == djbk::MODEL_SET_PROXY_MAX_ENTRIES, "the header states the kernels' bound");
 
 extern "C" {
 
@@ -105,7 +168,7 @@ DJB_ABI_CATCH
 
 djb_status djb_model_set_destroy(djb_model_set *s)
 try {
-	return s ? set_free(s, s->rows) : DJB_OK;
+	return s ? set_free(s, s->rows, s->proxy_dev) : DJB_OK;
 }
 DJB_ABI_CATCH
 
@@ -121,6 +184,123 @@ try {
 	// over the batch in 64-bit indices
 	HIP_TRY(djbk::launch_model_set_eval(ctx->stream, s->kind, s->rows, s->n_mat, ctx->model_set_rows_global != 0, n, c.dmat, c.vi, c.vo, c.vout,
 	                                    want_cos != 0));
+	return c.sg.finish();
+}
+DJB_ABI_CATCH
+
+djb_status djb_model_set_fit_proxy(djb_ctx *ctx, djb_model_set *s, int res, int shadow)
+try {
+	djb_status st = set_check(ctx, s, "model");
+	if (st != DJB_OK) return st;
+	if (res <= 2) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: Invalid Resolution");                   // dj_brdf.h:2218
+	if ((long long)s->n_mat * res > DJB_MODEL_SET_PROXY_MAX_ENTRIES)
+		return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: a model set's proxy holds at most %lld table entries per table (%d materials x resolution %d)",
+		            (long long)DJB_MODEL_SET_PROXY_MAX_ENTRIES, s->n_mat, res);
+	std::vector<float> block(proxy_floats(s->n_mat, res));
+	if (is_cpu(ctx)) {
+		if ((st = djbcpu::model_set_fit_proxy(ctx, s->kind, s->rows, s->n_mat, res, shadow, block.data())) != DJB_OK) return st;
+	} else {
+		if ((st = check_call(ctx, nullptr, 0, DJB_MEM_DEVICE)) != DJB_OK) return st;
+		std::lock_guard<std::recursive_mutex> call_lock(ctx->call_mu);
+		if ((st = fit_gpu(ctx, s, res, shadow, &block)) != DJB_OK) return st;
+		// the new block, then -- every earlier call on the stream has finished with the old one -- the exchange
+		float *d = nullptr;
+		const size_t bytes = sizeof(float) * block.size();
+		hipError_t e = hipMalloc((void **)&d, bytes);
+		if (e == hipSuccess) e = hipMemcpyAsync(d, block.data(), bytes, hipMemcpyHostToDevice, ctx->stream);
+		if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+		if (e != hipSuccess) {
+			(void)hipGetLastError();
+			if (d) (void)hipFree(d);
+			return fail(DJB_ERR_HIP, "djb_error: HIP allocation / copy of a model set's proxy block (%zu bytes): %s", bytes, hipGetErrorString(e));
+		}
+		if (s->proxy_dev) (void)hipFree(s->proxy_dev);
+		s->proxy_dev = d;
+	}
+	s->proxy_host.swap(block);
+	s->proxy_res = res; s->proxy_shadow = shadow != 0;
+	return DJB_OK;
+}
+DJB_ABI_CATCH
+
+djb_status djb_model_set_proxy_info(const djb_model_set *s, int *res, int *shadow)
+try {
+	if (!s) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null model set");
+	if (res) *res = s->proxy_res;
+	if (shadow) *shadow = s->proxy_shadow;
+	return DJB_OK;
+}
+DJB_ABI_CATCH
+
+djb_status djb_model_set_get_proxy(const djb_model_set *s, int material, int which, float *out, int *count)
+try {
+	if (!s) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null model set");
+	if (!s->proxy_res) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: the model set has no proxy (djb_model_set_fit_proxy)");
+	if (material < 0 || material >= s->n_mat)
+		return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: material %d is outside the set's 0 .. %d", material, s->n_mat - 1);
+	const size_t res = (size_t)s->proxy_res;
+	const float *tab = s->proxy_host.data() + 3 * (size_t)material * res;
+	int n = s->proxy_res;
+	switch (which) {
+	case DJB_TAB_P22: break;
+	case DJB_TAB_SIGMA: tab += res; break;
+	case DJB_TAB_QF: tab += 2 * res; n = ((const int *)(s->proxy_host.data() + 3 * (size_t)s->n_mat * res))[material]; break;
+	default: return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: a model set's proxy holds p22, sigma and qf (table %d)", which);
+	}
+	if (count) *count = n;
+	if (out) memcpy(out, tab, sizeof(float) * (size_t)n);
+	return DJB_OK;
+}
+DJB_ABI_CATCH
+
+djb_status djb_model_set_evalp_is_proxy_batch(djb_ctx *ctx, const djb_model_set *s, int64_t n, const int32_t *material, const float *u1,
+                                              const float *u2, const djb_vec3_view *o, const djb_vec3_view *out_weight,
+                                              const djb_vec3_view *out_i, float *out_pdf, int mem)
+try {
+	djb_status st = proxy_call_check(ctx, s);
+	if (st != DJB_OK) return st;
+	if (is_cpu(ctx))
+		return djbcpu::model_set_evalp_is_proxy(ctx, s->kind, s->rows, s->n_mat, s->proxy_host.data(), s->proxy_res, s->proxy_shadow, n, material, u1, u2,
+		                                        o, out_weight, out_i, out_pdf);
+	if (!Staged::valid(out_weight) || !Staged::valid(out_i) || !out_pdf) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null output");
+	if ((st = check_call(ctx, nullptr, n, mem)) != DJB_OK) return st;
+	std::lock_guard<std::recursive_mutex> call_lock(ctx->call_mu);
+	Params pp;
+	if ((st = device_params(nullptr, &pp, DJB_KIND_TABULAR)) != DJB_OK) return st;         // as the single-material call resolves NULL proxy params
+	Staged sg(ctx, n, mem);
+	const int32_t *dmat; View vo, vi, vw; const float *d1, *d2; float *dpdf = nullptr;
+	if ((st = stage_material(sg, material, &dmat)) != DJB_OK) return st;
+	if ((st = sg.in_f(u1, &d1)) != DJB_OK) return st;
+	if ((st = sg.in_f(u2, &d2)) != DJB_OK) return st;
+	if ((st = sg.in_vec(o, &vo)) != DJB_OK) return st;
+	if ((st = sg.out_vec(out_i, &vi)) != DJB_OK) return st;
+	if ((st = sg.out_vec(out_weight, &vw)) != DJB_OK) return st;
+	if ((st = sg.out_arr(out_pdf, &dpdf)) != DJB_OK) return st;
+	const djbk::ModelSetProxy px = { s->proxy_dev, s->proxy_res, s->proxy_shadow };
+	HIP_TRY(djbk::launch_model_set_evalp_is_proxy(ctx->stream, s->kind, s->rows, s->n_mat, ctx->model_set_rows_global != 0, px, pp, n, dmat, d1, d2, vo,
+	                                              vw, vi, dpdf));
+	return sg.finish();
+}
+DJB_ABI_CATCH
+
+djb_status djb_model_set_evalp_pdf_proxy_batch(djb_ctx *ctx, const djb_model_set *s, int64_t n, const int32_t *material, const djb_vec3_view *i,
+                                               const djb_vec3_view *o, const djb_vec3_view *out_fr, float *out_pdf, int mem)
+try {
+	djb_status st = proxy_call_check(ctx, s);
+	if (st != DJB_OK) return st;
+	if (!out_pdf) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null out_pdf (evalp alone: djb_model_set_eval_batch)");
+	if (is_cpu(ctx))
+		return djbcpu::model_set_evalp_pdf(ctx, s->kind, s->rows, s->n_mat, s->proxy_host.data(), s->proxy_res, s->proxy_shadow, n, material, i, o,
+		                                   out_fr, out_pdf);
+	Params pp;
+	if ((st = device_params(nullptr, &pp, DJB_KIND_TABULAR)) != DJB_OK) return st;
+	SetBatch c(ctx, nullptr, n, mem, material, i, o, out_fr);
+	if (c.st != DJB_OK) return c.st;
+	float *dpdf = nullptr;
+	if ((st = c.sg.out_arr(out_pdf, &dpdf)) != DJB_OK) return st;
+	const djbk::ModelSetProxy px = { s->proxy_dev, s->proxy_res, s->proxy_shadow };
+	HIP_TRY(djbk::launch_model_set_evalp_pdf(ctx->stream, s->kind, s->rows, s->n_mat, ctx->model_set_rows_global != 0, px, pp, n, c.dmat, c.vi, c.vo,
+	                                         c.vout, dpdf));
 	return c.sg.finish();
 }
 DJB_ABI_CATCH

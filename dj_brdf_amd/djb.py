@@ -1313,8 +1313,9 @@ class utia_set(_material_set):
 class model_set(_material_set):
     """M sgd or abc materials -- parameter rows of ONE kind -- resident in ONE block on their context's device: hits that land on many
     data-driven materials are evaluated in one call, each hit naming its material by id (djb_model_set, include/djb_hip.h).  An extension:
-    the reference's objects are one material each.  ``eval`` / ``evalp`` are all that dj_sgd / dj_abc ask of their object (they sample
-    the cosine hemisphere), so there is no proxy.
+    the reference's objects are one material each.  dj_sgd / dj_abc take ``eval`` / ``evalp`` from their object and ``sample`` / ``pdf``
+    from ``tabular(object, 90)``: ``fit_proxy`` fits that lobe for every row and keeps its tables resident, ``evalp_is_proxy`` and
+    ``evalp_pdf_proxy`` are the sampling step and the light sample per hit against it.
 
     ``model_set(brdfs)``: the rows of ``djb.sgd`` or ``djb.abc`` objects (all of one kind); ``from_rows`` / ``from_names`` take the rows
     themselves or the published names.  ``material``: int32 ids, one per hit; an id outside [0, M) marks an inactive hit (a dead path),
@@ -1375,6 +1376,57 @@ class model_set(_material_set):
     @property
     def n_materials(self) -> int:
         return self._info()[1]
+
+    def fit_proxy(self, res: int = 90, shadow: bool = True):
+        """fit ``tabular(material m, res, shadow)`` for every row (the plugins' proxy) and keep its p22 / sigma / qf tables resident;
+        a second call replaces the first in stream order"""
+        _lib.check(_lib.load().djb_model_set_fit_proxy(self.ctx._h, self._h, C.c_int(res), C.c_int(1 if shadow else 0)))
+
+    def proxy_info(self):
+        """(res, shadow) of the resident proxies; res == 0: none fitted yet"""
+        r, sh = C.c_int(), C.c_int()
+        _lib.check(_lib.load().djb_model_set_proxy_info(self._h, C.byref(r), C.byref(sh)))
+        return r.value, bool(sh.value)
+
+    def proxy_tables(self, m: int):
+        """{"p22", "sigma", "qf"} of material ``m``'s proxy as float32 arrays; ``qf`` holds the valid entries only (often fewer than res)"""
+        out = {}
+        for name, which in (("p22", 0), ("sigma", 1), ("qf", 3)):       # DJB_TAB_P22, DJB_TAB_SIGMA, DJB_TAB_QF
+            cnt = C.c_int()
+            _lib.check(_lib.load().djb_model_set_get_proxy(self._h, C.c_int(m), C.c_int(which), None, C.byref(cnt)))
+            a = np.empty(cnt.value, dtype=np.float32)
+            _lib.check(_lib.load().djb_model_set_get_proxy(self._h, C.c_int(m), C.c_int(which), C.c_void_p(a.ctypes.data), C.byref(cnt)))
+            out[name] = a
+        return out
+
+    def evalp_is_proxy(self, material, u1, u2, o):
+        """(weight, i, pdf) per hit as ``brdf.evalp_is_proxy(tabular(material m), ...)``: direction and pdf from the hit's material's fitted
+        lobe, f_r cos from its row; weight = 0 and pdf = 0 where i.z <= 0.  One kernel launch on the GPU."""
+        vo = _Vec(o)
+        keep, mp = self._ids(material, vo)
+        k1, p1 = _scalar_in(u1, vo)
+        k2, p2 = _scalar_in(u2, vo)
+        w, i = vo.like(), vo.like()
+        pdf, pdf_ptr = vo.scalars()
+        _lib.check(_lib.load().djb_model_set_evalp_is_proxy_batch(self.ctx._h, self._h, C.c_int64(vo.n), C.c_void_p(mp), C.c_void_p(p1), C.c_void_p(p2),
+                                                                 C.byref(vo.view), C.byref(w.view), C.byref(i.view), C.c_void_p(pdf_ptr),
+                                                                 C.c_int(vo.mem)))
+        del keep, k1, k2
+        return w.keep, i.keep, pdf
+
+    def evalp_pdf_proxy(self, material, i, o):
+        """(fr, pdf) per hit for GIVEN pairs, the light sample of dj_sgd / dj_abc: f_r * cos(theta_i) of material[k] and the pdf of its
+        fitted lobe; both are +0 where i.z <= 0 or o.z <= 0.  One kernel launch on the GPU."""
+        vi, vo = _Vec(i), _Vec(o)
+        if vi.n != vo.n or vi.mem != vo.mem:
+            raise exc(1, "djb_error: i and o must have the same length and memory space")
+        keep, mp = self._ids(material, vi)
+        fr = vi.like()
+        pdf, pdf_ptr = vi.scalars()
+        _lib.check(_lib.load().djb_model_set_evalp_pdf_proxy_batch(self.ctx._h, self._h, C.c_int64(vi.n), C.c_void_p(mp), C.byref(vi.view),
+                                                                  C.byref(vo.view), C.byref(fr.view), C.c_void_p(pdf_ptr), C.c_int(vi.mem)))
+        del keep
+        return fr.keep, pdf
 
 
 # --------------------------------------------------------------------------- user-defined BRDFs (dj_brdf.h:74-109)

@@ -79,7 +79,10 @@ extern "C" {
  *        material id, one call).
  *        Additive under 235, no existing entry changed: SGD / ABC model sets -- djb_model_set, DJB_MODEL_SET_MAX, djb_model_set_create,
  *        djb_model_set_create_from_brdfs, djb_model_set_info, djb_model_set_destroy, djb_model_set_eval_batch (eval / evalp of hits on M
- *        resident sgd or abc parameter rows by per-hit material id, one call), DJB_OPT_MODEL_SET_ROWS_GLOBAL. */
+ *        resident sgd or abc parameter rows by per-hit material id, one call), DJB_OPT_MODEL_SET_ROWS_GLOBAL.
+ *        Additive under 235, no existing entry changed: fitted tabular proxies on a model set -- DJB_MODEL_SET_PROXY_MAX_ENTRIES,
+ *        djb_model_set_fit_proxy, djb_model_set_proxy_info, djb_model_set_get_proxy, djb_model_set_evalp_is_proxy_batch,
+ *        djb_model_set_evalp_pdf_proxy_batch (the sampling step and the light sample of dj_sgd / dj_abc per hit, one call each). */
 #define DJB_HIP_VERSION 235
 #define DJB_HIP_VERSION_MAJOR(v) ((v) / 100)
 
@@ -614,9 +617,11 @@ djb_status djb_utia_set_eval_batch(djb_ctx *, const djb_utia_set *, int64_t n, c
                                    const djb_vec3_view *out_fr, int mem);
 
 /* ---- SGD / ABC model sets: the material sets of the two data-driven analytic models.  A model set is M resident parameter rows of ONE
- * kind, DJB_KIND_SGD or DJB_KIND_ABC -- the reference publishes one row per MERL material for each, and mitsuba/dj_sgd.cpp / dj_abc.cpp
- * ask their object for eval and evalp alone (they sample the cosine hemisphere).  For a model set the material is not a table base but
- * one row of doubles: the coefficients that are launch-uniform for the single-material kernels are per-hit data here.
+ * kind, DJB_KIND_SGD or DJB_KIND_ABC -- the reference publishes one row per MERL material for each.  mitsuba/dj_sgd.cpp / dj_abc.cpp take
+ * eval and evalp from their object, and sample() and pdf() from djb::tabular(object, 90), a lobe they fit at load time (dj_sgd.cpp:30, 76,
+ * 88, 100; dj_abc.cpp:32, 77, 89, 101): djb_model_set_eval_batch serves the first, the fitted proxies below the second.  For a model set
+ * the material is not a table base but one row of doubles: the coefficients that are launch-uniform for the single-material kernels are
+ * per-hit data here.
  *
  * Creation.  djb_model_set_create takes n_materials rows in host memory, in the layout djb_brdf_create_sgd_from_params (33 doubles per
  * row) / djb_brdf_create_abc_from_params (9 doubles per row) take, and as unvalidated as there: any doubles are accepted, the arithmetic
@@ -645,6 +650,46 @@ djb_status djb_model_set_destroy(djb_model_set *);
 djb_status djb_model_set_eval_batch(djb_ctx *, const djb_model_set *, int64_t n, const int32_t *material,
                                     const djb_vec3_view *i, const djb_vec3_view *o, int want_cos,
                                     const djb_vec3_view *out_fr, int mem);
+
+/* ---- fitted tabular proxies on a model set: what dj_sgd / dj_abc sample from and take their pdf from, per hit.
+ *
+ * djb_model_set_fit_proxy fits tabular(model_m, res, shadow) for every row of the set with the library's fitter (a GPU context: the fit
+ * kernel on the resident rows, 128 materials per launch; a CPU context: the host fitter per row).  The tables of material m are, bit for
+ * bit, those of djb_brdf_create_tabular(djb_brdf_create_{sgd,abc}_from_params(row_m), res, shadow), whatever M is.  What stays resident
+ * is what sampling and the pdf read: p22, sigma and qf (res floats each per material) and the per-material count of valid qf entries,
+ * which can be far below res (dj_brdf.h:2731).  cdf and the Fresnel spline are not kept: neither call reads them.  res <= 2 is the
+ * reference's "Invalid Resolution"; a res beyond the fit kernel's LDS budget is refused as djb_brdf_create_tabular refuses it; and
+ * M * res <= DJB_MODEL_SET_PROXY_MAX_ENTRIES = 2^27, which keeps the byte offset of any table entry (12 bytes per entry of the three
+ * tables, 4 M bytes of counts behind them) below 2^31 for the kernels' uniform-base + 32-bit-offset addressing.  A second call replaces
+ * the first in stream order on the context's stream (the set's context must still exist); the call returns when the block is in place.
+ * djb_model_set_proxy_info: *res = 0 while the set has no proxy.  djb_model_set_get_proxy copies one table of one material
+ * (which: DJB_TAB_P22, DJB_TAB_SIGMA or DJB_TAB_QF; qf: the valid entries) and stores its length in *count; out == NULL queries the
+ * count, as djb_tabular_get does; a material outside [0, M) is DJB_ERR_INVALID_ARGUMENT.
+ *
+ * The two per-hit calls.  A hit with 0 <= material[k] < M gets, bit for bit, what the single-material call returns for unit k's inputs
+ * with target = djb_brdf_create_*_from_params(row_m), proxy = djb_brdf_create_tabular(target, res, shadow) and both params NULL:
+ *   djb_model_set_evalp_is_proxy_batch    djb_evalp_is_proxy_batch: i is stored in every case, weight = 0 and pdf = 0 where i.z <= 0 (a NaN
+ *                                         i.z is evaluated), o is unguarded, the division by a zero pdf gives the IEEE result
+ *   djb_model_set_evalp_pdf_proxy_batch   djb_evalp_pdf_proxy_batch for a GIVEN pair: out_fr = +0 and out_pdf = +0 where i.z <= 0 ||
+ *                                         o.z <= 0 (a NaN z is evaluated; such a hit reads neither row nor table).  out_fr and out_pdf
+ *                                         may not be NULL
+ * A hit whose id is outside [0, M) is INACTIVE: every output of that hit is +0.0f (weight, i and pdf; or fr and pdf) and nothing is read
+ * for it.  A set without a proxy is DJB_ERR_INVALID_ARGUMENT, and so is a set of another context.  DJB_OPT_CONTRACT_1E5 changes
+ * nothing; DJB_OPT_MODEL_SET_ROWS_GLOBAL and DJB_SGD_FAST=0 at creation are honoured as for djb_model_set_eval_batch (by default up to
+ * 101 sgd or 211 abc rows are copied into LDS).  The proxy tables are read from global memory.  CPU contexts serve both calls with the
+ * host instantiation of the same per-unit code.  On a GPU context a device-memory batch is ONE kernel launch, with no allocation and no
+ * host read-back: it can be captured into a hipGraph.  A host-memory batch of any size is staged through HBM (a set has no host twin). */
+#define DJB_MODEL_SET_PROXY_MAX_ENTRIES (1 << 27)
+djb_status djb_model_set_fit_proxy(djb_ctx *, djb_model_set *, int res, int shadow);
+djb_status djb_model_set_proxy_info(const djb_model_set *, int *res, int *shadow);
+djb_status djb_model_set_get_proxy(const djb_model_set *, int material, int which /* DJB_TAB_P22 | DJB_TAB_SIGMA | DJB_TAB_QF */,
+                                   float *out, int *count);
+djb_status djb_model_set_evalp_is_proxy_batch(djb_ctx *, const djb_model_set *, int64_t n, const int32_t *material,
+                                              const float *u1, const float *u2, const djb_vec3_view *o,
+                                              const djb_vec3_view *out_weight, const djb_vec3_view *out_i, float *out_pdf, int mem);
+djb_status djb_model_set_evalp_pdf_proxy_batch(djb_ctx *, const djb_model_set *, int64_t n, const int32_t *material,
+                                               const djb_vec3_view *i, const djb_vec3_view *o,
+                                               const djb_vec3_view *out_fr, float *out_pdf, int mem);
 
 /* beckmann::lrep algebra on {E1..E5} (host scalars; dj_brdf.h:330-356, 1959-2051).  b may be NULL
  * (= the default lrep(0,0,1,1,0)); x (and y) are the scalar arguments of mul / shear / scale.

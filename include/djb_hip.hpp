@@ -1373,8 +1373,10 @@ private:
 
 /* M sgd or abc materials -- parameter rows of ONE kind -- resident in one block on their context's device (include/djb_hip.h,
  * djb_model_set): each hit names its material by id and the whole batch is one call.  An extension with no counterpart in the reference.
- * eval / evalp are all that dj_sgd / dj_abc ask of their object (they sample the cosine hemisphere).  An id outside [0, size()) marks an
- * inactive hit: its output is +0.  An active hit gets the bits of sgd::eval / evalp (abc::eval / evalp) on its material. */
+ * dj_sgd / dj_abc take eval / evalp from their object and sample() / pdf() from tabular(object, 90): fit_proxy fits that lobe for every
+ * row and keeps its p22 / sigma / qf tables resident; evalp_is_proxy and evalp_pdf_proxy are the plugins' sampling step and light sample
+ * per hit against it.  An id outside [0, size()) marks an inactive hit: every output of it is +0.  An active hit gets the bits of
+ * sgd::eval / evalp (abc::eval / evalp) on its material, and of brdf::evalp_is_proxy / evalp_pdf_proxy with tabular(material, res, shadow). */
 class model_set {
 public:
 	/* n rows in the layout of djb_brdf_create_sgd_from_params (33 doubles) / djb_brdf_create_abc_from_params (9 doubles); kind = DJB_KIND_SGD or DJB_KIND_ABC */
@@ -1391,13 +1393,40 @@ public:
 	const djb_model_set *get() const { return m_h; }
 	int size() const { int v; hip::check(djb_model_set_info(m_h, NULL, &v)); return v; }
 	int kind() const { int v; hip::check(djb_model_set_info(m_h, &v, NULL)); return v; }
+	/* tabular(material m, res, shadow) for every row (what dj_sgd / dj_abc build at load time); a second call replaces the first */
+	void fit_proxy(int res = 90, bool shadow = true) { hip::check(djb_model_set_fit_proxy(ctx(), m_h, res, shadow ? 1 : 0)); }
+	/* the resolution of the resident proxies, 0: none fitted yet */
+	int proxy_resolution() const { int v; hip::check(djb_model_set_proxy_info(m_h, &v, NULL)); return v; }
+	bool proxy_shadow() const { int v; hip::check(djb_model_set_proxy_info(m_h, NULL, &v)); return v != 0; }
+	/* one table of material m's proxy: which = DJB_TAB_P22, DJB_TAB_SIGMA or DJB_TAB_QF (the valid entries) */
+	std::vector<float_t> proxy_table(int m, int which) const
+	{
+		int n = 0;
+		hip::check(djb_model_set_get_proxy(m_h, m, which, NULL, &n));
+		std::vector<float_t> v((size_t)n);
+		if (n) hip::check(djb_model_set_get_proxy(m_h, m, which, &v[0], NULL));
+		return v;
+	}
 	// ---- host arrays
 	void eval(size_t n, const int32_t *material, const vec3 *i, const vec3 *o, vec3 *out) const { eval_views((int64_t)n, material, hip::view(i), hip::view(o), hip::view(out), 0, DJB_MEM_HOST); }
 	void evalp(size_t n, const int32_t *material, const vec3 *i, const vec3 *o, vec3 *out) const { eval_views((int64_t)n, material, hip::view(i), hip::view(o), hip::view(out), 1, DJB_MEM_HOST); }
-	// ---- views (SoA or strided), in host memory or in HBM (mem = DJB_MEM_DEVICE: asynchronous on the context's stream)
+	/* the sampling step of dj_sgd / dj_abc per hit: i from the material's fitted lobe, its pdf, weight = evalp / pdf; 0 and 0 where i.z <= 0 */
+	void evalp_is_proxy(size_t n, const int32_t *material, const float_t *u1, const float_t *u2, const vec3 *o, vec3 *out_weight, vec3 *out_i,
+	                    float_t *out_pdf) const
+	{ evalp_is_proxy_views((int64_t)n, material, u1, u2, hip::view(o), hip::view(out_weight), hip::view(out_i), out_pdf, DJB_MEM_HOST); }
+	/* their light sample for given pairs: out_fr = evalp of material[k], out_pdf = the pdf of its fitted lobe, both 0 where i.z <= 0 || o.z <= 0 */
+	void evalp_pdf_proxy(size_t n, const int32_t *material, const vec3 *i, const vec3 *o, vec3 *out_fr, float_t *out_pdf) const
+	{ evalp_pdf_proxy_views((int64_t)n, material, hip::view(i), hip::view(o), hip::view(out_fr), out_pdf, DJB_MEM_HOST); }
+	// ---- views (SoA or strided), in host memory or in HBM (mem = DJB_MEM_DEVICE: asynchronous on the context's stream, one launch)
 	void eval_views(int64_t n, const int32_t *material, const djb_vec3_view &i, const djb_vec3_view &o, const djb_vec3_view &out,
 	                int want_cos, int mem) const
 	{ hip::check(djb_model_set_eval_batch(ctx(), m_h, n, material, &i, &o, want_cos, &out, mem)); }
+	void evalp_is_proxy_views(int64_t n, const int32_t *material, const float_t *u1, const float_t *u2, const djb_vec3_view &o,
+	                          const djb_vec3_view &out_weight, const djb_vec3_view &out_i, float_t *out_pdf, int mem) const
+	{ hip::check(djb_model_set_evalp_is_proxy_batch(ctx(), m_h, n, material, u1, u2, &o, &out_weight, &out_i, out_pdf, mem)); }
+	void evalp_pdf_proxy_views(int64_t n, const int32_t *material, const djb_vec3_view &i, const djb_vec3_view &o, const djb_vec3_view &out_fr,
+	                           float_t *out_pdf, int mem) const
+	{ hip::check(djb_model_set_evalp_pdf_proxy_batch(ctx(), m_h, n, material, &i, &o, &out_fr, out_pdf, mem)); }
 private:
 	template <typename T> void from_objects(size_t n, const T *const *materials)
 	{

@@ -42,6 +42,10 @@ class FresnelDesc(C.Structure):
                 ("points", C.c_void_p), ("npoints", C.c_int)]
 
 
+class SceneSlot(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("local", C.c_int32)]
+
+
 class exc(RuntimeError):
     """Mirror of ``djb::exc`` (reference dj_brdf.h:54-59): carries the djb_error message."""
 
@@ -77,6 +81,7 @@ EXPORTS = [
     "djb_model_set_create", "djb_model_set_create_from_brdfs", "djb_model_set_info", "djb_model_set_destroy", "djb_model_set_eval_batch",
     "djb_model_set_fit_proxy", "djb_model_set_proxy_info", "djb_model_set_get_proxy", "djb_model_set_evalp_is_proxy_batch",
     "djb_model_set_evalp_pdf_proxy_batch",
+    "djb_scene_create", "djb_scene_info", "djb_scene_destroy", "djb_scene_eval_batch",
 ]
 
 _lib = None
@@ -119,6 +124,10 @@ def load() -> C.CDLL:
     lib.djb_model_set_get_proxy.argtypes = [P, C.c_int, C.c_int, P, P]
     lib.djb_model_set_evalp_is_proxy_batch.argtypes = [P, P, C.c_int64, P, P, P, P, P, P, P, C.c_int]
     lib.djb_model_set_evalp_pdf_proxy_batch.argtypes = [P, P, C.c_int64, P, P, P, P, P, C.c_int]
+    lib.djb_scene_create.argtypes = [P, P, P, P, P, C.c_int, P, P]
+    lib.djb_scene_info.argtypes = [P, P, P]
+    lib.djb_scene_destroy.argtypes = [P]
+    lib.djb_scene_eval_batch.argtypes = [P, P, C.c_int64, P, P, P, C.c_int, P, C.c_int]
     if lib.djb_version() // 100 != ABI_VERSION // 100:
         raise ImportError(f"{LIB_PATH} has ABI version {lib.djb_version()}, this binding was written against {ABI_VERSION} "
                           "(include/djb_hip.h: DJB_HIP_VERSION) -- rebuild the library")

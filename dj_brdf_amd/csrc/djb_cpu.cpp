@@ -1090,6 +1090,43 @@ djb_status model_set_eval(djb_ctx *ctx, int kind, const double *rows, int n_mat,
 		return set_eval<KIND_SGD>(ctx, n_mat, n, material, i, o, want_cos, out_fr, [rows](Brdf &tb, unsigned int m) { bind_model_row<KIND_SGD>(tb, rows, m); });
 	return set_eval<KIND_ABC>(ctx, n_mat, n, material, i, o, want_cos, out_fr, [rows](Brdf &tb, unsigned int m) { bind_model_row<KIND_ABC>(tb, rows, m); });
 }
+// Scenes: slots = n_slots packed words (kind code 0 merl, 1 utia, 2 sgd, 3 abc in the high 16 bits, the local id in the low 16; anything
+// else: no material), validated by djb_scene_create.  Each hit is classified through the table and handed, alone, to set_eval_loop with its
+// member's binding: the per-hit code the three sets run.  A hit outside the table or on a slot without material: +0, nothing read
+template <int WANT>
+static void scene_eval_loop(const unsigned int *slots, int n_slots, const MerlTexel *tex, const float4 *tab, const double *sgd, const double *abc,
+                            long long k0, long long k1, const int32_t *material, const View &vi, const View &vo, const View &vout)
+{
+	auto at = [](const View &v, long long k) { return View{ v.x + k * v.stride, v.y + k * v.stride, v.z + k * v.stride, v.stride }; };
+	for (long long k = k0; k < k1; ++k) {
+		const unsigned int raw = (unsigned int)material[k];
+		const unsigned int slot = raw < (unsigned int)n_slots ? slots[raw] : 0xffffffffu;
+		const int32_t local = (int32_t)(slot & 0xffffu);
+		const View i1 = at(vi, k), o1 = at(vo, k), out1 = at(vout, k);
+		switch (slot >> 16) {
+		case 0: set_eval_loop<KIND_MERL, WANT>(65536, 0, 1, &local, i1, o1, out1, [tex](Brdf &tb, unsigned int m) { tb.merl = tex + (size_t)m * (size_t)MERL_N; }); break;
+		case 1: set_eval_loop<KIND_UTIA, WANT>(65536, 0, 1, &local, i1, o1, out1, [tab](Brdf &tb, unsigned int m) { tb.utia = tab + (size_t)m * 8 * (size_t)(UTIA_N / 3); }); break;
+		case 2: set_eval_loop<KIND_SGD, WANT>(65536, 0, 1, &local, i1, o1, out1, [sgd](Brdf &tb, unsigned int m) { bind_model_row<KIND_SGD>(tb, sgd, m); }); break;
+		case 3: set_eval_loop<KIND_ABC, WANT>(65536, 0, 1, &local, i1, o1, out1, [abc](Brdf &tb, unsigned int m) { bind_model_row<KIND_ABC>(tb, abc, m); }); break;
+		default: store3(vout, k, mk(0, 0, 0));
+		}
+	}
+}
+djb_status scene_eval(djb_ctx *ctx, const unsigned int *slots, int n_slots, const void *merl_texels, const void *utia_records, const double *sgd_rows,
+                      const double *abc_rows, int64_t n, const int32_t *material, const djb_vec3_view *i, const djb_vec3_view *o, int want_cos,
+                      const djb_vec3_view *out_fr)
+{
+	djb_status st = set_batch_args(n, material, i, o, out_fr);
+	if (st != DJB_OK) return st;
+	const MerlTexel *tex = (const MerlTexel *)merl_texels;
+	const float4 *tab = (const float4 *)utia_records;
+	const View vi = view_of(i), vo = view_of(o), vout = view_of(out_fr);
+	parallel_for(C(ctx), n, 4096, [&](long long k0, long long k1) {
+		if (want_cos) scene_eval_loop<2>(slots, n_slots, tex, tab, sgd_rows, abc_rows, k0, k1, material, vi, vo, vout);
+		else scene_eval_loop<1>(slots, n_slots, tex, tab, sgd_rows, abc_rows, k0, k1, material, vi, vo, vout);
+	});
+	return DJB_OK;
+}
 // the fitted tabular proxies of a model set (djb_model_set_fit_proxy): block = float[n_mat][3][res] -- p22, sigma, qf of tabular(model_m, res,
 // shadow) one after the other -- then int n_qf[n_mat]; each material fitted as create_tabular fits the single object
 djb_status model_set_fit_proxy(djb_ctx *ctx, int kind, const double *rows, int n_mat, int res, int shadow, float *block)

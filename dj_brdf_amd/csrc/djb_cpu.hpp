@@ -114,6 +114,11 @@ djb_status utia_set_eval(djb_ctx *, const void *records, int n_mat, int64_t n, c
 djb_status model_set_member(const djb_ctx *ctx, const djb_brdf *b, int index, int *kind, const double **row);
 djb_status model_set_eval(djb_ctx *, int kind, const double *rows, int n_mat, int64_t n, const int32_t *material, const djb_vec3_view *i,
                           const djb_vec3_view *o, int want_cos, const djb_vec3_view *out_fr);
+// Scenes on the host (include/djb_hip.h: djb_scene).  slots: n_slots packed words (djb_internal.hpp) in host memory; the four blocks are
+// those of the member sets above, NULL for a kind the scene has no set for (no slot names it)
+djb_status scene_eval(djb_ctx *, const unsigned int *slots, int n_slots, const void *merl_texels, const void *utia_records, const double *sgd_rows,
+                      const double *abc_rows, int64_t n, const int32_t *material, const djb_vec3_view *i, const djb_vec3_view *o, int want_cos,
+                      const djb_vec3_view *out_fr);
 // the set's fitted tabular proxies: block = float[n_mat][3][res] (p22, sigma, qf of tabular(model_m, res, shadow)) then int n_qf[n_mat], host
 // memory; and the two per-hit steps against them (evalp_is_proxy / evalp_pdf_proxy above with target = model_m, proxy = that lobe, no params)
 djb_status model_set_fit_proxy(djb_ctx *, int kind, const double *rows, int n_mat, int res, int shadow, float *block);

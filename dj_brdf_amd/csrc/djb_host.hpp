@@ -60,6 +60,7 @@ struct djb_ctx {
 	unsigned int ct_hopeless_calls = 0;        // calls answered by the exact kernel because of ct_key_share: every 16th re-probes
 	int model_set_rows_global = 0;   // DJB_OPT_MODEL_SET_ROWS_GLOBAL: model-set kernels read their rows from global memory whatever M is (tests, A/B timing)
 	long long test_worklist_cap = -1;   // DJB_OPT_TEST_WORKLIST_CAP (tests): >= 0 overrides the tier-2 worklist capacity
+	long long test_scene_chunk = 0;     // DJB_OPT_TEST_SCENE_CHUNK (tests): > 0 overrides the hits per chunk of a scene call
 	int contract_1e5 = 0;      // DJB_OPT_CONTRACT_1E5: dense GGX eval batches run the two-tier value-contract kernels
 	std::atomic<long long> host_batch_max{DJB_SCALAR_HOST_MAX};   // DJB_OPT_HOST_BATCH_MAX: host-array calls up to this size are answered by the host twin
 	int scalar_on_device = 0;  // DJB_OPT_SCALAR_ON_DEVICE: scalar-size host calls go through the GPU too (A/B testing)
@@ -157,6 +158,15 @@ struct djb_model_set : djb_set_base {
 	int proxy_res = 0, proxy_shadow = 0;     // proxy_res == 0: no proxy yet
 	std::vector<float> proxy_host;   // the block in host memory: what a CPU context computes on, and what djb_model_set_get_proxy reads
 	float *proxy_dev = nullptr;      // GPU context: the block in HBM
+};
+
+// a scene (djb_scene.hip): the slot table that maps a scene material id to (kind, local id) in up to four member sets, which the scene
+// BORROWS.  n_mat is the number of slots.  slots: one packed word per slot (djb_internal.hpp) where the scene's context computes.
+struct djb_scene : djb_set_base {
+	const djb_merl_set *merl = nullptr;
+	const djb_utia_set *utia = nullptr;
+	const djb_model_set *sgd = nullptr, *abc = nullptr;
+	unsigned int *slots = nullptr;
 };
 
 namespace djbh {

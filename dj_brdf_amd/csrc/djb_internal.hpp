@@ -160,6 +160,19 @@ hipError_t launch_model_set_evalp_is_proxy(hipStream_t s, int kind, const double
 hipError_t launch_model_set_evalp_pdf(hipStream_t s, int kind, const double *rows, int n_mat, bool rows_global, const ModelSetProxy &proxy,
                                       const Params &proxy_p, long long n, const int32_t *material, const View &i, const View &o,
                                       const View &out_fr, float *out_pdf);
+// Scenes (djb_kernels_scene.hip): hits on up to four member sets at once.  slots = n_slots words, kind (0 merl, 1 utia, 2 sgd, 3 abc; any
+// other value: no material) << 16 | local id; a hit whose id is outside [0, n_slots) or whose slot has no material is inactive (+0).  One
+// call partitions a chunk of m <= SCENE_CHUNK_MAX hits by kind on the device (three launches) and runs one kernel per member set that is
+// there (utia: tier 1 + fix after a hipMemsetAsync of wl_count, or the fix kernel alone when utia_exact) on its segment of the index list.
+// A null member is not launched.  Scratch, all device memory: hdr 8 words (count[4], offset[4]), tiles 4 * scene_tiles(m) words, list m
+// words, wl_count 4 words, wl wl_cap words.
+constexpr long long SCENE_CHUNK_MAX = 1LL << 26;
+struct SceneMembers { const djbdev::MerlTexel *merl; int n_merl; const float4 *utia; int n_utia; const double *sgd; int n_sgd; const double *abc; int n_abc; };
+struct SceneScratch { unsigned int *hdr, *tiles, *list, *wl_count, *wl; unsigned int wl_cap; };
+size_t scene_tiles(long long m);
+hipError_t launch_scene_eval(hipStream_t s, const SceneMembers &members, const unsigned int *slots, int n_slots, long long m, const int32_t *material,
+                             const View &i, const View &o, const View &out, bool want_cos, const SceneScratch &scratch, bool merl_exact,
+                             bool utia_exact, bool rows_global);
 hipError_t launch_fast_trig_selftest(hipStream_t s, long long n, int mode, uint32_t first, uint32_t seed, unsigned long long *counters4);
 // DJB_OPT_CONTRACT_1E5 (djb_kernels_contract.hip): GGX eval / evalp / pdf inside the 1e-5 value contract, two-tier like
 // the MERL lookup, with a sharded worklist (list: cap records of 32 bytes in total, count: CONTRACT_SHARDS uint32, CONTRACT_COUNTER_STRIDE words apart: the record

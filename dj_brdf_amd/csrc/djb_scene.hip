@@ -1,0 +1,133 @@
+// djb_scene.hip -- the C ABI of scenes (include/djb_hip.h: djb_scene): a resident slot table that maps a scene material id to (kind, local
+// id) in up to four member sets -- a MERL set, a UTIA set, an sgd and an abc model set -- evaluated per hit in one call.  The scene borrows
+// its members and copies only the slot table.  Kernels: djb_kernels_scene.hip; host loop (CPU contexts): djb_cpu.cpp; the checks and the
+// entry of a batch: djb_set_host.hpp.  A scene has no host twin: on a GPU context a host batch of any size is staged to the device.
+#include "djb_set_host.hpp"
+
+using namespace djbh;
+
+namespace {
+
+constexpr long long SCENE_CHUNK = 1LL << 24;     // hits per chunk: 64 MB of index list; indices and list positions stay far below 2^31
+static_assert(SCENE_CHUNK <= djbk::SCENE_CHUNK_MAX && DJB_SCENE_MAX_SLOTS <= (1 << 30), "chunk and table sizes the kernels' 32-bit indices hold");
+
+// kind of the ABI -> the kernels' code (djb_internal.hpp), or -1
+int kind_code(int kind)
+{
+	switch (kind) {
+	case DJB_KIND_MERL: return 0;
+	case DJB_KIND_UTIA: return 1;
+	case DJB_KIND_SGD: return 2;
+	case DJB_KIND_ABC: return 3;
+	}
+	return -1;
+}
+
+} // namespace
+
+extern "C" {
+
+djb_status djb_scene_create(djb_ctx *ctx, const djb_merl_set *merl, const djb_utia_set *utia, const djb_model_set *sgd, const djb_model_set *abc,
+                            int n_slots, const djb_scene_slot *slots, djb_scene **out)
+try {
+	if (!ctx || !out || !slots) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null argument");
+	*out = nullptr;
+	if (!merl && !utia && !sgd && !abc) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: a scene needs at least one member set");
+	if (n_slots < 1 || n_slots > DJB_SCENE_MAX_SLOTS)
+		return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: a scene holds 1 .. %d slots (got %d)", DJB_SCENE_MAX_SLOTS, n_slots);
+	djb_status st;
+	if (merl && (st = set_check(ctx, merl, "merl")) != DJB_OK) return st;
+	if (utia && (st = set_check(ctx, utia, "utia")) != DJB_OK) return st;
+	if (sgd && (st = set_check(ctx, sgd, "model")) != DJB_OK) return st;
+	if (abc && (st = set_check(ctx, abc, "model")) != DJB_OK) return st;
+	if (sgd && sgd->kind != DJB_KIND_SGD) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: the scene's sgd member is a model set of kind %d", sgd->kind);
+	if (abc && abc->kind != DJB_KIND_ABC) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: the scene's abc member is a model set of kind %d", abc->kind);
+	const int count[4] = { merl ? merl->n_mat : 0, utia ? utia->n_mat : 0, sgd ? sgd->n_mat : 0, abc ? abc->n_mat : 0 };
+	static const char *const name[4] = { "merl", "utia", "sgd", "abc" };
+	std::vector<unsigned int> words((size_t)n_slots);
+	for (int k = 0; k < n_slots; ++k) {
+		if (slots[k].kind == DJB_SCENE_NONE) { words[k] = 0xffffffffu; continue; }
+		const int q = kind_code(slots[k].kind);
+		if (q < 0) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: scene slot %d names kind %d (merl, utia, sgd, abc or DJB_SCENE_NONE)", k, slots[k].kind);
+		if (!count[q]) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: scene slot %d names a %s material, but the scene has no %s set", k, name[q], name[q]);
+		if (slots[k].local < 0 || slots[k].local >= count[q] || slots[k].local > 65535)
+			return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: scene slot %d names %s material %d, outside the set's 0 .. %d", k, name[q], slots[k].local,
+			            std::min(count[q], 65536) - 1);
+		words[k] = ((unsigned int)q << 16) | (unsigned int)slots[k].local;
+	}
+	djb_scene *s = set_new<djb_scene>(ctx, n_slots);
+	s->merl = merl; s->utia = utia; s->sgd = sgd; s->abc = abc;
+	const size_t bytes = sizeof(unsigned int) * words.size();
+	if (is_cpu(ctx)) {
+		s->slots = (unsigned int *)malloc(bytes);
+		if (!s->slots) { djb_scene_destroy(s); return fail(DJB_ERR_OUT_OF_MEMORY, "djb_error: out of host memory (scene of %d slots)", n_slots); }
+		memcpy(s->slots, words.data(), bytes);
+	} else if ((st = set_gpu_fill(s, djb_scene_destroy, "scene", n_slots, "slots", bytes, [&] {
+		hipError_t e = hipMalloc((void **)&s->slots, bytes);
+		return e == hipSuccess ? hipMemcpy(s->slots, words.data(), bytes, hipMemcpyHostToDevice) : e;     // synchronous: `words` goes out of scope
+	})) != DJB_OK) return st;
+	*out = s;
+	return DJB_OK;
+}
+DJB_ABI_CATCH
+
+djb_status djb_scene_info(const djb_scene *s, int *n_slots, int members[4])
+try {
+	if (!s) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null scene");
+	if (n_slots) *n_slots = s->n_mat;
+	if (members) {
+		members[0] = s->merl ? s->merl->n_mat : 0; members[1] = s->utia ? s->utia->n_mat : 0;
+		members[2] = s->sgd ? s->sgd->n_mat : 0; members[3] = s->abc ? s->abc->n_mat : 0;
+	}
+	return DJB_OK;
+}
+DJB_ABI_CATCH
+
+djb_status djb_scene_destroy(djb_scene *s)
+try {
+	return s ? set_free(s, s->slots) : DJB_OK;
+}
+DJB_ABI_CATCH
+
+djb_status djb_scene_eval_batch(djb_ctx *ctx, const djb_scene *s, int64_t n, const int32_t *material, const djb_vec3_view *i, const djb_vec3_view *o,
+                                int want_cos, const djb_vec3_view *out_fr, int mem)
+try {
+	djb_status st = set_check(ctx, s, "scene");
+	if (st != DJB_OK) return st;
+	if (is_cpu(ctx))
+		return djbcpu::scene_eval(ctx, s->slots, s->n_mat, s->merl ? s->merl->tex : nullptr, s->utia ? s->utia->tab : nullptr,
+		                          s->sgd ? s->sgd->rows : nullptr, s->abc ? s->abc->rows : nullptr, n, material, i, o, want_cos, out_fr);
+	SetBatch c(ctx, nullptr, n, mem, material, i, o, out_fr);
+	if (c.st != DJB_OK) return c.st;
+	if (n <= 0) return c.sg.finish();
+	const View &vi = c.vi, &vo = c.vo, &vout = c.vout;
+	// Every lane reads its hit before it writes it and kinds touch disjoint hits, so index-aligned in-place views are supported.  The utia
+	// fix pass reads a hit again after tier 1 stored it: a device-resident caller whose outputs overlap an input stream, the ids included,
+	// gets the exact kernel alone for the utia part (the rule of djb_utia_set_eval_batch)
+	const Stream ins[7] = { { vi.x, vi.stride }, { vi.y, vi.stride }, { vi.z, vi.stride }, { vo.x, vo.stride }, { vo.y, vo.stride }, { vo.z, vo.stride },
+	                        { c.dmat, 1 } };
+	const Stream outs[3] = { { vout.x, vout.stride }, { vout.y, vout.stride }, { vout.z, vout.stride } };
+	const bool utia_exact = ctx->utia_exact_only != 0 || (mem == DJB_MEM_DEVICE && outputs_overlap_inputs(n, ins, 7, outs, 3));
+	const djbk::SceneMembers mb = { s->merl ? s->merl->tex : nullptr, s->merl ? s->merl->n_mat : 0, s->utia ? s->utia->tab : nullptr,
+	                                s->utia ? s->utia->n_mat : 0, s->sgd ? s->sgd->rows : nullptr, s->sgd ? s->sgd->n_mat : 0,
+	                                s->abc ? s->abc->rows : nullptr, s->abc ? s->abc->n_mat : 0 };
+	// the partition's list, the tile counts, count / offset and the utia worklist share the context's scratch, sized once for the largest
+	// chunk of this call: words [0, 8) count[4] offset[4], [8, 12) the worklist's count, from 16: tiles, list, worklist
+	const long long chunk = ctx->test_scene_chunk > 0 ? ctx->test_scene_chunk : SCENE_CHUNK;       // DJB_OPT_TEST_SCENE_CHUNK (tests)
+	const long long mc = std::min<long long>(n, chunk);
+	const size_t tiles = 4 * djbk::scene_tiles(mc);
+	size_t cap = (size_t)(mc / 256 + 4096);
+	if (ctx->test_worklist_cap >= 0) cap = (size_t)ctx->test_worklist_cap;                         // DJB_OPT_TEST_WORKLIST_CAP (tests): force the overflow path
+	if ((st = ensure_scratch(ctx, 4 * (16 + tiles + (size_t)mc + (cap ? cap : 1)))) != DJB_OK) return st;
+	unsigned int *w = (unsigned int *)ctx->scratch;
+	const djbk::SceneScratch sc = { w, w + 16, w + 16 + tiles, w + 8, w + 16 + tiles + (size_t)mc, (unsigned int)cap };
+	for (long long lo = 0; lo < n; lo += chunk) {                                                  // back to back on the context's stream
+		const long long m = std::min(n - lo, chunk);
+		HIP_TRY(djbk::launch_scene_eval(ctx->stream, mb, s->slots, s->n_mat, m, c.dmat + lo, offset_view(vi, lo), offset_view(vo, lo), offset_view(vout, lo),
+		                                want_cos != 0, sc, ctx->merl_exact_only != 0, utia_exact, ctx->model_set_rows_global != 0));
+	}
+	return c.sg.finish();
+}
+DJB_ABI_CATCH
+
+} // extern "C"

@@ -1,6 +1,7 @@
-// djb_set_host.hpp -- what the C ABIs of the three material sets share (djb_merl_set.hip, djb_utia_set.hip, djb_model_set.hip; included by
-// those alone): the checks of a handle, a member and a count, the construction and release of the resident block, and the entry of an eval
-// batch.  `what` is the set's noun in the messages: "merl" / "utia" / "model".  Everything works on djb_set_base (djb_host.hpp).
+// djb_set_host.hpp -- what the C ABIs of the three material sets and of scenes share (djb_merl_set.hip, djb_utia_set.hip, djb_model_set.hip,
+// djb_scene.hip; included by those alone): the checks of a handle, a member and a count, the construction and release of the resident block,
+// and the entry of an eval batch.  `what` is the set's noun in the messages: "merl" / "utia" / "model" / "scene".  Everything works on
+// djb_set_base (djb_host.hpp).
 #pragma once
 #include "djb_host.hpp"
 

@@ -1429,6 +1429,57 @@ class model_set(_material_set):
         return fr.keep, pdf
 
 
+class scene(_material_set):
+    """A slot table over up to four member sets -- a ``merl_set``, a ``utia_set``, an sgd and an abc ``model_set`` of one context --: hits
+    that land on measured, UTIA and data-driven materials at once are evaluated in one call, each hit naming its material by SCENE id
+    (djb_scene, include/djb_hip.h).  On the GPU the batch is partitioned by kind on the device and each member's kernel runs on its
+    dense list of hits.  ``eval`` / ``evalp`` only: sampling and the light sample stay with the sets.
+
+    ``slots``: one ``(kind, local)`` pair per scene id, ``kind`` one of "merl", "utia", "sgd", "abc" (or the DJB_KIND_* value) and ``local``
+    the material's id in that member set; ``None`` (or kind "none") is a slot without material.  Two slots may name one material.
+    ``material``: int32 scene ids, one per hit; an id outside the table or on a slot without material marks an inactive hit, whose output
+    is +0.  An active hit gets the bits of its member set's call -- those of the single-material call.  The scene borrows its member sets
+    (this object holds references to them; closing a member before the scene is the caller's error).  Arrays: numpy (host) or torch CUDA
+    (device), in the layouts the other operators take; the ids travel in the memory space of the directions."""
+
+    _C = "djb_scene"
+    NONE = -1                                  # DJB_SCENE_NONE
+    MAX_SLOTS = 1 << 20                        # DJB_SCENE_MAX_SLOTS
+    _KINDS = {"merl": 3, "utia": 4, "sgd": 6, "abc": 7, "none": -1}
+
+    def __init__(self, merl=None, utia=None, sgd=None, abc=None, slots=(), ctx: Optional[Context] = None):
+        members = (merl, utia, sgd, abc)
+        slots = list(slots)
+        given = [m for m in members if m is not None]
+        self.ctx = ctx or (given[0].ctx if given else default_context())
+        self._h = C.c_void_p()
+        self._members = members                    # borrowed by the C object: kept alive here
+        table = (_lib.SceneSlot * max(len(slots), 1))()
+        for k, s in enumerate(slots):
+            kind, local = (self.NONE, 0) if s is None else s
+            if isinstance(kind, str):
+                if kind not in self._KINDS:
+                    raise exc(1, f"djb_error: scene slot {k} names kind {kind!r} ('merl', 'utia', 'sgd', 'abc' or 'none')")
+                kind = self._KINDS[kind]
+            table[k].kind, table[k].local = int(kind), int(local)
+        _lib.check(_lib.load().djb_scene_create(self.ctx._h, *[getattr(getattr(m, "_h", None), "value", None) for m in members],
+                                                C.c_int(len(slots)), table, C.byref(self._h)))
+
+    def _info(self):
+        n, members = C.c_int(), (C.c_int * 4)()
+        _lib.check(_lib.load().djb_scene_info(self._h, C.byref(n), members))
+        return n.value, tuple(members)
+
+    @property
+    def n_slots(self) -> int:
+        return self._info()[0]
+
+    @property
+    def members(self):
+        """materials per kind (merl, utia, sgd, abc); 0: the scene has no such set"""
+        return self._info()[1]
+
+
 # --------------------------------------------------------------------------- user-defined BRDFs (dj_brdf.h:74-109)
 def fit_query_dirs(resolution: int):
     """The (i, o) pairs at which ``tabular(src, resolution)`` evaluates its source, in the reference's call order
@@ -1862,6 +1913,11 @@ def contract_sample_attack(brdf, u1, u2, o, params=None, iters: int = 256, seed:
 def set_test_worklist_cap(ctx: Context, entries: int):
     """tests: override the tier-2 worklist capacity of the two-tier kernels (-1 = automatic); DJB_OPT_TEST_WORKLIST_CAP"""
     _lib.check(_lib.load().djb_ctx_set_option(ctx._h, C.c_int(7), C.c_int(int(entries))))
+
+
+def set_test_scene_chunk(ctx: Context, hits: int):
+    """tests: the hits per chunk of a scene call (0 = the default), to reach chunk boundaries at small n; DJB_OPT_TEST_SCENE_CHUNK"""
+    _lib.check(_lib.load().djb_ctx_set_option(ctx._h, C.c_int(10), C.c_int(int(hits))))
 
 
 def set_aniso_qf2_aligned(ctx: Context, on: bool):

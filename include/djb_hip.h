@@ -82,7 +82,10 @@ extern "C" {
  *        resident sgd or abc parameter rows by per-hit material id, one call), DJB_OPT_MODEL_SET_ROWS_GLOBAL.
  *        Additive under 235, no existing entry changed: fitted tabular proxies on a model set -- DJB_MODEL_SET_PROXY_MAX_ENTRIES,
  *        djb_model_set_fit_proxy, djb_model_set_proxy_info, djb_model_set_get_proxy, djb_model_set_evalp_is_proxy_batch,
- *        djb_model_set_evalp_pdf_proxy_batch (the sampling step and the light sample of dj_sgd / dj_abc per hit, one call each). */
+ *        djb_model_set_evalp_pdf_proxy_batch (the sampling step and the light sample of dj_sgd / dj_abc per hit, one call each).
+ *        Additive under 235, no existing entry changed: scenes -- djb_scene, djb_scene_slot, DJB_SCENE_NONE, DJB_SCENE_MAX_SLOTS,
+ *        djb_scene_create, djb_scene_info, djb_scene_destroy, djb_scene_eval_batch (eval / evalp of hits that land on a MERL set, a UTIA
+ *        set, an sgd and an abc model set at once, by per-hit scene material id, one call), DJB_OPT_TEST_SCENE_CHUNK. */
 #define DJB_HIP_VERSION 235
 #define DJB_HIP_VERSION_MAJOR(v) ((v) / 100)
 
@@ -123,6 +126,7 @@ typedef struct djb_leanmap djb_leanmap;   /* an immutable LEAN map (mip pyramid 
 typedef struct djb_merl_set djb_merl_set; /* M MERL tables in one resident block + one proxy parameter set per material */
 typedef struct djb_utia_set djb_utia_set; /* M UTIA record tables in one resident block */
 typedef struct djb_model_set djb_model_set; /* M sgd or abc parameter rows in one resident block */
+typedef struct djb_scene djb_scene;         /* a slot table over up to four member sets: scene material id -> (kind, local id) */
 
 typedef struct { float *x, *y, *z; int64_t stride; } djb_vec3_view;
 
@@ -251,7 +255,10 @@ enum { DJB_OPT_MERL_EXACT_ONLY = 1,
        DJB_OPT_HOST_BATCH_MAX = 8,
 /* DJB_OPT_MODEL_SET_ROWS_GLOBAL = 1 (tests and A/B timing; off by default): the model-set kernels read their parameter rows from
  * global memory whatever M is, instead of from the copy a workgroup keeps in LDS when the set is small enough.  Same bits. */
-       DJB_OPT_MODEL_SET_ROWS_GLOBAL = 9 };
+       DJB_OPT_MODEL_SET_ROWS_GLOBAL = 9,
+/* DJB_OPT_TEST_SCENE_CHUNK = <hits> (tests only; 0 = the default of 2^24, at most 2^26): the hits per chunk of djb_scene_eval_batch, to
+ * reach chunk boundaries at small n.  Results never depend on it. */
+       DJB_OPT_TEST_SCENE_CHUNK = 10 };
 djb_status  djb_ctx_set_option(djb_ctx *ctx, int option, int value);
 /* Observer of the MERL file pipeline (djb_fit_merl_files, both context kinds): `fn(path, user)` is called from the reader thread
  * after a file has passed its size check and has been mapped, before its entries are gathered; NULL removes it.  Diagnostics /
@@ -690,6 +697,45 @@ djb_status djb_model_set_evalp_is_proxy_batch(djb_ctx *, const djb_model_set *, 
 djb_status djb_model_set_evalp_pdf_proxy_batch(djb_ctx *, const djb_model_set *, int64_t n, const int32_t *material,
                                                const djb_vec3_view *i, const djb_vec3_view *o,
                                                const djb_vec3_view *out_fr, float *out_pdf, int mem);
+
+/* ---- scenes: one call for a hit batch that lands on measured, UTIA and data-driven materials at once.  A material set holds materials
+ * of ONE kind; a wavefront renderer's bounce does not.  A scene is a resident slot table that maps a SCENE material id to (kind, local id)
+ * in up to four member sets -- a MERL set, a UTIA set, an sgd model set and an abc model set -- so that the caller need not split the
+ * batch by kind, gather sub-batches and scatter the results back.  eval / evalp only: sampling and the light sample stay with the sets.
+ *
+ * Creation.  Any member set may be NULL, at least one must be given; every given set belongs to the call's context, `sgd` is a model set of
+ * kind sgd and `abc` one of kind abc.  slots: n_slots entries in host memory, 1 <= n_slots <= DJB_SCENE_MAX_SLOTS.  Every slot names a
+ * kind whose set was given and 0 <= local < that set's count (and <= 65535: the table packs a slot into 32 bits), or has kind
+ * DJB_SCENE_NONE, a slot without material; anything else is DJB_ERR_INVALID_ARGUMENT with a message that names the slot.  Two slots may
+ * name the same material.  The scene BORROWS its member sets: it copies only the slot table, and every call reads the members' resident
+ * blocks.  Destroying a member set before the scene -- or calling the scene after that -- is the caller's error.  The scene belongs to
+ * its context as a set does.  djb_scene_info: members[k] is the number of materials of kind merl, utia, sgd, abc, 0 where there is no set.
+ *
+ * djb_scene_eval_batch (the argument order of djb_model_set_eval_batch).  material: n int32 scene ids in the memory space `mem` names.  A
+ * hit whose id lies outside [0, n_slots), or whose slot is DJB_SCENE_NONE, is INACTIVE: out_fr of that hit is +0.0f and nothing is read
+ * for it.  An active hit gets, bit for bit, what its member set's call returns for it on its local id: the bits of the single-material
+ * call.  DJB_OPT_MERL_EXACT_ONLY, DJB_OPT_UTIA_EXACT_ONLY, DJB_OPT_MODEL_SET_ROWS_GLOBAL, DJB_OPT_TEST_WORKLIST_CAP and DJB_SGD_FAST=0 (at
+ * the sgd set's creation) are honoured as the member sets honour them; DJB_OPT_CONTRACT_1E5 changes nothing.
+ *
+ * On a GPU context the batch is partitioned by kind ON THE DEVICE (a stable counting sort of the hit indices: three small kernels), then
+ * one kernel per member set the scene has runs on its dense list of hits -- no kernel dispatches on kind per lane.  A device-memory call
+ * runs in chunks of 2^24 hits, back to back on the context's stream; per chunk it makes three launches for the partition, one per MERL,
+ * sgd and abc member and two per UTIA member plus the hipMemsetAsync of its worklist count.  It reads nothing back to the host and
+ * allocates nothing once the context's scratch has its size (per hit of the largest chunk: 4 bytes of list, 16 bytes per 512 hits of
+ * counts, the utia worklist): after one call of that size it can be captured into a hipGraph.  Index-aligned in-place calls (out_fr names
+ * i's or o's arrays) are supported; when an output overlaps an input stream the UTIA part takes the exact-only route, as for
+ * djb_utia_set_eval_batch.  A host-memory batch of any size is staged through HBM (a scene has no host twin).  CPU contexts classify each
+ * hit through the table and run the member's per-hit host code. */
+#define DJB_SCENE_NONE (-1)
+#define DJB_SCENE_MAX_SLOTS (1 << 20)
+typedef struct { int32_t kind; int32_t local; } djb_scene_slot;
+/* kind: DJB_KIND_MERL | DJB_KIND_UTIA | DJB_KIND_SGD | DJB_KIND_ABC, or DJB_SCENE_NONE: a slot without material */
+djb_status djb_scene_create(djb_ctx *, const djb_merl_set *merl, const djb_utia_set *utia, const djb_model_set *sgd,
+                            const djb_model_set *abc, int n_slots, const djb_scene_slot *slots, djb_scene **out);
+djb_status djb_scene_info(const djb_scene *, int *n_slots, int members[4] /* materials per kind, 0 = no such set */);
+djb_status djb_scene_destroy(djb_scene *);
+djb_status djb_scene_eval_batch(djb_ctx *, const djb_scene *, int64_t n, const int32_t *material, const djb_vec3_view *i,
+                                const djb_vec3_view *o, int want_cos, const djb_vec3_view *out_fr, int mem);
 
 /* beckmann::lrep algebra on {E1..E5} (host scalars; dj_brdf.h:330-356, 1959-2051).  b may be NULL
  * (= the default lrep(0,0,1,1,0)); x (and y) are the scalar arguments of mul / shear / scale.

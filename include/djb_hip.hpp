@@ -1439,6 +1439,42 @@ private:
 	djb_model_set *m_h;
 };
 
+/* A slot table over up to four member sets of one context -- a merl_set, a utia_set, an sgd and an abc model_set (include/djb_hip.h,
+ * djb_scene): the hits of one bounce land on measured, UTIA and data-driven materials at once; each hit names its material by SCENE id
+ * and the whole batch is one call.  An extension with no counterpart in the reference.  slots[k] = { kind, local }: kind DJB_KIND_MERL,
+ * DJB_KIND_UTIA, DJB_KIND_SGD or DJB_KIND_ABC and the material's id in that member, or kind DJB_SCENE_NONE, a slot without material.  A
+ * hit whose id is outside [0, size()) or whose slot has no material is inactive: its output is +0.  An active hit gets the bits of its
+ * member set's call.  The scene BORROWS its members: they must outlive it.  Any member may be NULL, not all. */
+class scene {
+public:
+	scene(const merl_set *merl, const utia_set *utia, const model_set *sgd, const model_set *abc, size_t n_slots, const djb_scene_slot *slots,
+	      hip::context *c = NULL) : m_ctx(c), m_h(NULL)
+	{
+		hip::check(djb_scene_create(ctx(), merl ? merl->get() : NULL, utia ? utia->get() : NULL, sgd ? sgd->get() : NULL, abc ? abc->get() : NULL,
+		                            (int)n_slots, slots, &m_h));
+	}
+	~scene() { djb_scene_destroy(m_h); }
+	scene(scene &&o) noexcept : m_ctx(o.m_ctx), m_h(o.m_h) { o.m_h = NULL; }
+	scene &operator=(scene &&o) noexcept { if (this != &o) { djb_scene_destroy(m_h); m_ctx = o.m_ctx; m_h = o.m_h; o.m_h = NULL; } return *this; }
+	scene(const scene &) = delete;
+	scene &operator=(const scene &) = delete;
+	const djb_scene *get() const { return m_h; }
+	int size() const { int v; hip::check(djb_scene_info(m_h, &v, NULL)); return v; }
+	/* materials of kind k = 0 merl, 1 utia, 2 sgd, 3 abc; 0: the scene has no such set */
+	int members(int k) const { int v[4]; hip::check(djb_scene_info(m_h, NULL, v)); return k >= 0 && k < 4 ? v[k] : 0; }
+	// ---- host arrays
+	void eval(size_t n, const int32_t *material, const vec3 *i, const vec3 *o, vec3 *out) const { eval_views((int64_t)n, material, hip::view(i), hip::view(o), hip::view(out), 0, DJB_MEM_HOST); }
+	void evalp(size_t n, const int32_t *material, const vec3 *i, const vec3 *o, vec3 *out) const { eval_views((int64_t)n, material, hip::view(i), hip::view(o), hip::view(out), 1, DJB_MEM_HOST); }
+	// ---- views (SoA or strided), in host memory or in HBM (mem = DJB_MEM_DEVICE: asynchronous on the context's stream, nothing read back)
+	void eval_views(int64_t n, const int32_t *material, const djb_vec3_view &i, const djb_vec3_view &o, const djb_vec3_view &out,
+	                int want_cos, int mem) const
+	{ hip::check(djb_scene_eval_batch(ctx(), m_h, n, material, &i, &o, want_cos, &out, mem)); }
+private:
+	djb_ctx *ctx() const { return (m_ctx ? *m_ctx : hip::context::standard()).get(); }
+	hip::context *m_ctx;
+	djb_scene *m_h;
+};
+
 } // namespace djb
 
 #endif // DJB_HIP_HPP

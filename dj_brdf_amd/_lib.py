@@ -82,6 +82,7 @@ EXPORTS = [
     "djb_model_set_fit_proxy", "djb_model_set_proxy_info", "djb_model_set_get_proxy", "djb_model_set_evalp_is_proxy_batch",
     "djb_model_set_evalp_pdf_proxy_batch",
     "djb_scene_create", "djb_scene_info", "djb_scene_destroy", "djb_scene_eval_batch",
+    "djb_utia_set_set_proxy_params", "djb_utia_set_proxy_info", "djb_scene_evalp_is_proxy_batch", "djb_scene_evalp_pdf_proxy_batch",
 ]
 
 _lib = None
@@ -128,6 +129,10 @@ def load() -> C.CDLL:
     lib.djb_scene_info.argtypes = [P, P, P]
     lib.djb_scene_destroy.argtypes = [P]
     lib.djb_scene_eval_batch.argtypes = [P, P, C.c_int64, P, P, P, C.c_int, P, C.c_int]
+    lib.djb_utia_set_set_proxy_params.argtypes = [P, P]
+    lib.djb_utia_set_proxy_info.argtypes = [P, P]
+    lib.djb_scene_evalp_is_proxy_batch.argtypes = [P, P, P, C.c_int64, P, P, P, P, P, P, P, C.c_int]
+    lib.djb_scene_evalp_pdf_proxy_batch.argtypes = [P, P, P, C.c_int64, P, P, P, P, P, C.c_int]
     if lib.djb_version() // 100 != ABI_VERSION // 100:
         raise ImportError(f"{LIB_PATH} has ABI version {lib.djb_version()}, this binding was written against {ABI_VERSION} "
                           "(include/djb_hip.h: DJB_HIP_VERSION) -- rebuild the library")

@@ -1310,6 +1310,79 @@ djb_status merl_set_evalp_pdf(djb_ctx *ctx, const void *texels, const void *para
 	return DJB_OK;
 }
 
+// Scenes, the two per-hit proxy steps: each hit is classified through the slot table and handed, alone, to its member's host loop -- the MERL
+// set's, the model set's, and for utia the single-material pair (proxy_loop / proxy_light_loop) with the hit's table and Params.  LIGHT: a = i
+// (given), outputs fr and pdf; else u1a / u2a are read, outputs weight, i and pdf.  A hit outside the table or on a slot without material: +0
+template <int PK, bool LIGHT>
+static void scene_proxy_loop(const SceneProxyHost &S, const Brdf &pb, const Params &model_p, long long k0, long long k1, const int32_t *material,
+                             const float *u1a, const float *u2a, const View &va, const View &vo, const View &vfr, const View &vi_out, float *out_pdf)
+{
+	auto at = [](const View &v, long long k) { return v.x ? View{ v.x + k * v.stride, v.y + k * v.stride, v.z + k * v.stride, v.stride } : v; };
+	const MerlTexel *tex = (const MerlTexel *)S.merl_texels;
+	const float4 *tab = (const float4 *)S.utia_records;
+	const Params *merl_p = (const Params *)S.merl_params, *utia_p = (const Params *)S.utia_params;
+	Brdf tb; memset(&tb, 0, sizeof tb); tb.kind = KIND_UTIA;
+	Params tp; memset(&tp, 0, sizeof tp);
+	for (long long k = k0; k < k1; ++k) {
+		const unsigned int raw = (unsigned int)material[k];
+		const unsigned int slot = raw < (unsigned int)S.n_slots ? S.slots[raw] : 0xffffffffu;
+		const int32_t local = (int32_t)(slot & 0xffffu);
+		const View a1 = at(va, k), o1 = at(vo, k), fr1 = at(vfr, k), i1 = at(vi_out, k);
+		const float *u1 = LIGHT ? nullptr : u1a + k, *u2 = LIGHT ? nullptr : u2a + k;
+		switch (slot >> 16) {
+		case 0:
+			if (LIGHT) merl_set_light_loop<PK>(tex, merl_p, 65536, pb, 0, 1, &local, a1, o1, fr1, out_pdf + k);
+			else merl_set_proxy_loop<PK>(tex, merl_p, 65536, pb, 0, 1, &local, u1, u2, o1, fr1, i1, out_pdf + k);
+			break;
+		case 1:
+			tb.utia = tab + (size_t)local * 8 * (size_t)(UTIA_N / 3);
+			if (LIGHT) proxy_light_loop<PK, KIND_UTIA>(tb, tp, pb, utia_p[local], 0, 1, a1, o1, fr1, out_pdf + k);
+			else proxy_loop<PK, KIND_UTIA>(tb, tp, pb, utia_p[local], 0, 1, u1, u2, o1, fr1, i1, out_pdf + k);
+			break;
+		case 2: model_set_proxy_loop<KIND_SGD, LIGHT>(S.sgd_rows, S.n_sgd, S.sgd_block, S.sgd_res, S.sgd_shadow, model_p, 0, 1, &local, u1, u2, a1, o1, fr1, i1, out_pdf + k); break;
+		case 3: model_set_proxy_loop<KIND_ABC, LIGHT>(S.abc_rows, S.n_abc, S.abc_block, S.abc_res, S.abc_shadow, model_p, 0, 1, &local, u1, u2, a1, o1, fr1, i1, out_pdf + k); break;
+		default:
+			store3(vfr, k, mk(0, 0, 0)); out_pdf[k] = 0.0f;
+			if (!LIGHT) store3(vi_out, k, mk(0, 0, 0));
+		}
+	}
+}
+// proxy: checked by the caller (djb_scene.hip) -- a ggx or beckmann object of this context when the scene has a merl or utia member, else unused
+template <bool LIGHT>
+static djb_status scene_proxy_run(djb_ctx *ctx, const SceneProxyHost &S, const djb_brdf *proxy, int64_t n, const int32_t *material, const float *u1,
+                                  const float *u2, const View &va, const View &vo, const View &vfr, const View &vi_out, float *out_pdf)
+{
+	Params model_p;
+	djb_status st = params_for(nullptr, KIND_TABULAR, &model_p);
+	if (st != DJB_OK) return st;
+	if (proxy && B(proxy)->ctx != C(ctx)) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: scene and proxy belong to different contexts");
+	Brdf none; memset(&none, 0, sizeof none); none.kind = KIND_GGX;                  // a scene of model members alone: no hit reads the lobe
+	const Brdf &pb = proxy ? B(proxy)->dev : none;
+	parallel_for(C(ctx), n, 2048, [&](long long k0, long long k1) {
+		if (pb.kind == KIND_GGX) scene_proxy_loop<KIND_GGX, LIGHT>(S, pb, model_p, k0, k1, material, u1, u2, va, vo, vfr, vi_out, out_pdf);
+		else scene_proxy_loop<KIND_BECKMANN, LIGHT>(S, pb, model_p, k0, k1, material, u1, u2, va, vo, vfr, vi_out, out_pdf);
+	});
+	return DJB_OK;
+}
+djb_status scene_evalp_is_proxy(djb_ctx *ctx, const SceneProxyHost &S, const djb_brdf *proxy, int64_t n, const int32_t *material, const float *u1,
+                                const float *u2, const djb_vec3_view *o, const djb_vec3_view *out_w, const djb_vec3_view *out_i, float *out_pdf)
+{
+	djb_status st = set_batch_head(n, material);
+	if (st != DJB_OK) return st;
+	if (!u1 || !u2 || !valid(o) || !valid(out_w) || !valid(out_i) || !out_pdf) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null argument");
+	const View none = { nullptr, nullptr, nullptr, 0 };
+	return scene_proxy_run<false>(ctx, S, proxy, n, material, u1, u2, none, view_of(o), view_of(out_w), view_of(out_i), out_pdf);
+}
+djb_status scene_evalp_pdf(djb_ctx *ctx, const SceneProxyHost &S, const djb_brdf *proxy, int64_t n, const int32_t *material, const djb_vec3_view *i,
+                           const djb_vec3_view *o, const djb_vec3_view *out_fr, float *out_pdf)
+{
+	djb_status st = set_batch_args(n, material, i, o, out_fr);
+	if (st != DJB_OK) return st;
+	if (!out_pdf) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null output");
+	const View none = { nullptr, nullptr, nullptr, 0 };
+	return scene_proxy_run<true>(ctx, S, proxy, n, material, nullptr, nullptr, view_of(i), view_of(o), view_of(out_fr), none, out_pdf);
+}
+
 djb_status eval_pp(djb_ctx *ctx, const djb_brdf *b_, int64_t n, const djb_vec3_view *i, const djb_vec3_view *o, const float *rec,
                    int mode, const float *base5, float scale, int lean_flags, int want, const djb_vec3_view *out_fr, float *out_pdf,
                    float *out_pp)

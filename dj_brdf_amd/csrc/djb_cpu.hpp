@@ -119,6 +119,19 @@ djb_status model_set_eval(djb_ctx *, int kind, const double *rows, int n_mat, in
 djb_status scene_eval(djb_ctx *, const unsigned int *slots, int n_slots, const void *merl_texels, const void *utia_records, const double *sgd_rows,
                       const double *abc_rows, int64_t n, const int32_t *material, const djb_vec3_view *i, const djb_vec3_view *o, int want_cos,
                       const djb_vec3_view *out_fr);
+// ... and the two per-hit proxy steps of a scene: the blocks of the members the scene has (NULL / 0 for the others) -- the MERL and UTIA
+// tables with their resolved Params[M], the model rows with their fitted proxy blocks (model_set_fit_proxy below).  proxy: the ggx or
+// beckmann lobe of the merl and utia parts, checked by the caller; not read when the scene has neither
+struct SceneProxyHost {
+	const unsigned int *slots; int n_slots;
+	const void *merl_texels, *merl_params, *utia_records, *utia_params;
+	const double *sgd_rows; const float *sgd_block; int n_sgd, sgd_res, sgd_shadow;
+	const double *abc_rows; const float *abc_block; int n_abc, abc_res, abc_shadow;
+};
+djb_status scene_evalp_is_proxy(djb_ctx *, const SceneProxyHost &, const djb_brdf *proxy, int64_t n, const int32_t *material, const float *u1,
+                                const float *u2, const djb_vec3_view *o, const djb_vec3_view *out_w, const djb_vec3_view *out_i, float *out_pdf);
+djb_status scene_evalp_pdf(djb_ctx *, const SceneProxyHost &, const djb_brdf *proxy, int64_t n, const int32_t *material, const djb_vec3_view *i,
+                           const djb_vec3_view *o, const djb_vec3_view *out_fr, float *out_pdf);
 // the set's fitted tabular proxies: block = float[n_mat][3][res] (p22, sigma, qf of tabular(model_m, res, shadow)) then int n_qf[n_mat], host
 // memory; and the two per-hit steps against them (evalp_is_proxy / evalp_pdf_proxy above with target = model_m, proxy = that lobe, no params)
 djb_status model_set_fit_proxy(djb_ctx *, int kind, const double *rows, int n_mat, int res, int shadow, float *block);

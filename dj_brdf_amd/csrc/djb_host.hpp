@@ -142,9 +142,13 @@ struct djb_merl_set : djb_set_base {
 };
 
 // a UTIA material set (djb_utia_set.hip): the converted record tables of M utia objects in one block, float4[M][288 * 288 * 8], where the
-// set's context computes (HBM, or host memory for a CPU context).  Immutable after its constructor returned.
+// set's context computes (HBM, or host memory for a CPU context).  The tables are immutable after the constructor returned.  params: once
+// given, the resolved proxy parameters Params[M] next to the tables, replaced in stream order by djb_utia_set_set_proxy_params -- read by
+// the scene's two proxy calls alone (djb_scene.hip); the block is allocated by the first set_proxy_params.
 struct djb_utia_set : djb_set_base {
 	float4 *tab = nullptr;
+	bool has_params = false;
+	Params *params = nullptr;
 };
 
 // an SGD / ABC model set (djb_model_set.hip): M parameter rows of one kind in one block where the set's context computes.  GPU context:

@@ -173,6 +173,24 @@ size_t scene_tiles(long long m);
 hipError_t launch_scene_eval(hipStream_t s, const SceneMembers &members, const unsigned int *slots, int n_slots, long long m, const int32_t *material,
                              const View &i, const View &o, const View &out, bool want_cos, const SceneScratch &scratch, bool merl_exact,
                              bool utia_exact, bool rows_global);
+// the first two launches of a partition alone: tile counts, then their scan into positions, count[4] and offset[4] (scratch.tiles / .hdr)
+hipError_t launch_scene_count_scan(hipStream_t s, const unsigned int *slots, int n_slots, long long m, const int32_t *material, const SceneScratch &scratch);
+// ... and the two per-hit proxy steps on a scene (djb_kernels_scene_proxy.hip): the count and scan above, a scatter that stores the +0 of an
+// inactive hit in every output of the call, then one kernel per member set on its segment of the list -- the body of the member set's proxy
+// kernel (launch_merl_set_evalp_is_proxy / _evalp_pdf, launch_model_set_evalp_is_proxy / _evalp_pdf) and, for utia, of the single-material
+// launch_evalp_is_proxy / launch_evalp_pdf_proxy with the hit's table and Params.  What they read beyond SceneMembers: the resident Params[M]
+// of the merl and utia members and the proxy blocks of the model members (NULL where the scene has no such member).  proxy: the ggx or
+// beckmann lobe of the merl and utia parts, not read without them; model_p: params::standard() for the fitted tabular proxies.
+// scratch.wl / wl_count are not used: no kernel takes a second pass.  One trip of every per-kind grid covers SCENE_PROXY_TRIP hits
+constexpr long long SCENE_PROXY_TRIP = 256LL * 16 * 256;
+struct SceneProxies { const Params *merl, *utia; ModelSetProxy sgd, abc; };
+hipError_t launch_scene_evalp_is_proxy(hipStream_t s, const SceneMembers &members, const SceneProxies &proxies, const Brdf *proxy, const Params &model_p,
+                                       const unsigned int *slots, int n_slots, long long m, const int32_t *material, const float *u1, const float *u2,
+                                       const View &o, const View &out_w, const View &out_i, float *out_pdf, const SceneScratch &scratch,
+                                       bool merl_exact, bool rows_global);
+hipError_t launch_scene_evalp_pdf_proxy(hipStream_t s, const SceneMembers &members, const SceneProxies &proxies, const Brdf *proxy, const Params &model_p,
+                                        const unsigned int *slots, int n_slots, long long m, const int32_t *material, const View &i, const View &o,
+                                        const View &out_fr, float *out_pdf, const SceneScratch &scratch, bool merl_exact, bool rows_global);
 hipError_t launch_fast_trig_selftest(hipStream_t s, long long n, int mode, uint32_t first, uint32_t seed, unsigned long long *counters4);
 // DJB_OPT_CONTRACT_1E5 (djb_kernels_contract.hip): GGX eval / evalp / pdf inside the 1e-5 value contract, two-tier like
 // the MERL lookup, with a sharded worklist (list: cap records of 32 bytes in total, count: CONTRACT_SHARDS uint32, CONTRACT_COUNTER_STRIDE words apart: the record

@@ -31,16 +31,10 @@ using namespace djbdev;
 
 namespace {
 
-constexpr int BLOCK = 256;
-constexpr unsigned int TILE = 512;                          // hits per wave of the partition kernels
-constexpr unsigned int STEPS = TILE / 64u;
-constexpr unsigned int K_MERL = 0, K_UTIA = 1, K_SGD = 2, K_ABC = 3, K_DEAD = 4;
-constexpr unsigned int SLOT_NONE = 0xffffffffu;
+#include "djb_scene_part.inc"                                                                         // BLOCK, TILE, K_*, Hits, slot_of, kind_of, local_of, wave_tile, the MERL record
 constexpr long long GRID_CAP_MERL = 256LL * 16;             // as k_merl_set_fast
 constexpr long long GRID_CAP_UTIA = 256LL * 64;             // as k_utia_set
 constexpr long long GRID_CAP_MODEL = 256LL * 16;            // as k_model_set
-constexpr long long MERL_TEXELS = 90LL * 90 * 180;
-constexpr unsigned int TABLE_F4 = 288u * 288u * 8u;         // float4 per utia material
 constexpr unsigned int NO_RECORD = 0xffffffffu;
 #ifndef DJB_UTIA_MIN_WAVES
 #define DJB_UTIA_MIN_WAVES 4
@@ -50,30 +44,7 @@ constexpr unsigned int NO_RECORD = 0xffffffffu;
 constexpr int rows_lds(int kind) { return kind == KIND_SGD ? 101 : 213; }                                 // as k_model_set
 constexpr int min_waves(int kind) { return kind == KIND_SGD ? 4 : 7; }
 
-// what every kernel reads of the batch: the slot table, the chunk's ids, and -- after the partition -- hdr = {count[4], offset[4]} and the list
-struct Hits {
-	const unsigned int *slots; unsigned int n_slots;
-	const int32_t *mat;
-	const unsigned int *hdr;
-	const unsigned int *list;
-};
-
-// the slot of an id: nothing is read for an id outside [0, n_slots) (negative ids are >= 2^31 as unsigned)
-DJB_DEV unsigned int slot_of(const unsigned int *slots, unsigned int n_slots, unsigned int raw) { return raw < n_slots ? slots[raw] : SLOT_NONE; }
-DJB_DEV unsigned int kind_of(unsigned int slot) { const unsigned int q = slot >> 16; return q < 4u ? q : K_DEAD; }
-// the local id of list entry k for the kernel of kind `q` with n_mat materials; false: not a hit of this kernel (the partition lists none)
-DJB_DEV bool local_of(const Hits &h, unsigned int k, unsigned int q, unsigned int n_mat, unsigned int &local)
-{
-	const unsigned int slot = slot_of(h.slots, h.n_slots, (unsigned int)h.mat[k]);
-	local = slot & 0xffffu;
-	const bool ok = kind_of(slot) == q && local < n_mat;
-	if (!ok) local = 0u;
-	return ok;
-}
-
 // ---- the partition
-DJB_DEV unsigned int wave_tile() { return (unsigned int)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6))); }
-
 __global__ __launch_bounds__(BLOCK) void k_scene_count(const unsigned int *slots, unsigned int n_slots, unsigned int m, const int32_t *mat,
                                                        unsigned int n_tiles, unsigned int *tiles)
 {
@@ -154,16 +125,6 @@ __global__ __launch_bounds__(BLOCK) void k_scene_scatter(const unsigned int *slo
 }
 
 // ---- merl: k_merl_set_fast over the list
-DJB_DEV v3 merl_set_texel(const MerlTexel *tex, unsigned int material, int idx)
-{
-	const MerlTexel t = tex[(unsigned long long)material * (unsigned long long)MERL_TEXELS + (unsigned long long)(unsigned int)idx];
-	return mk(t.x, t.y, t.z);
-}
-DJB_DEV void rec_pack(unsigned int *rec, long long k, unsigned int material, v3 i, v3 o)
-{
-	rec_put_k(rec, k); rec[2] = material; rec_put_v3(rec, 3, i); rec_put_v3(rec, 6, o);
-}
-
 template <int WANT>
 __global__ __launch_bounds__(BLOCK) void k_scene_merl(Hits h, const MerlTexel *tex, unsigned int n_mat, View vi, View vo, View vout, MerlGuard g,
                                                       int merl_exact)
@@ -379,10 +340,7 @@ hipError_t launch_all(hipStream_t s, const djbk::SceneMembers &mb, const unsigne
 	const unsigned int n_tiles = (unsigned int)djbk::scene_tiles(m);
 	const dim3 part((n_tiles + BLOCK / 64 - 1) / (BLOCK / 64)), t(BLOCK);
 	hipError_t e;
-	hipLaunchKernelGGL(k_scene_count, part, t, 0, s, slots, (unsigned int)n_slots, (unsigned int)m, mat, n_tiles, sc.tiles);
-	if ((e = hipGetLastError()) != hipSuccess) return e;
-	hipLaunchKernelGGL(k_scene_scan, dim3(1), dim3(SCAN_BLOCK), 0, s, n_tiles, sc.tiles, sc.hdr);
-	if ((e = hipGetLastError()) != hipSuccess) return e;
+	if ((e = djbk::launch_scene_count_scan(s, slots, n_slots, m, mat, sc)) != hipSuccess) return e;
 	hipLaunchKernelGGL(k_scene_scatter, part, t, 0, s, slots, (unsigned int)n_slots, (unsigned int)m, mat, n_tiles, sc.tiles, sc.list, out);
 	if ((e = hipGetLastError()) != hipSuccess) return e;
 	const Hits h = { slots, (unsigned int)n_slots, mat, sc.hdr, sc.list };
@@ -416,6 +374,17 @@ hipError_t launch_all(hipStream_t s, const djbk::SceneMembers &mb, const unsigne
 namespace djbk {
 
 size_t scene_tiles(long long m) { return (size_t)((m + (long long)TILE - 1) / (long long)TILE); }
+
+hipError_t launch_scene_count_scan(hipStream_t s, const unsigned int *slots, int n_slots, long long m, const int32_t *material, const SceneScratch &sc)
+{
+	const unsigned int n_tiles = (unsigned int)scene_tiles(m);
+	hipLaunchKernelGGL(k_scene_count, dim3((n_tiles + BLOCK / 64 - 1) / (BLOCK / 64)), dim3(BLOCK), 0, s, slots, (unsigned int)n_slots, (unsigned int)m,
+	                   material, n_tiles, sc.tiles);
+	const hipError_t e = hipGetLastError();
+	if (e != hipSuccess) return e;
+	hipLaunchKernelGGL(k_scene_scan, dim3(1), dim3(SCAN_BLOCK), 0, s, n_tiles, sc.tiles, sc.hdr);
+	return hipGetLastError();
+}
 
 hipError_t launch_scene_eval(hipStream_t s, const SceneMembers &members, const unsigned int *slots, int n_slots, long long m, const int32_t *material,
                              const View &i, const View &o, const View &out, bool want_cos, const SceneScratch &scratch, bool merl_exact,

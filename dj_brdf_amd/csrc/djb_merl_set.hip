@@ -11,45 +11,11 @@ namespace {
 
 constexpr size_t TABLE_BYTES = sizeof(MerlTexel) * (size_t)MERL_N;
 
-// n_mat plain parameter sets -> Params as the single-material calls of the set's back end resolve them
-djb_status resolve_all(bool cpu, int n_mat, const djb_params *in, std::vector<Params> *out)
-{
-	if (!in) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null proxy_params");
-	out->resize((size_t)n_mat);
-	for (int m = 0; m < n_mat; ++m) {
-		if (in[m].kind & DJB_PARAMS_RESOLVED_FOLLOWS)
-			return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: proxy_params[%d] carries DJB_PARAMS_RESOLVED_FOLLOWS: a merl set takes plain djb_params", m);
-		memset(&(*out)[m], 0, sizeof(Params));
-		djb_status st = cpu ? djbcpu::merl_set_resolve_params(&in[m], &(*out)[m]) : device_params(&in[m], &(*out)[m], DJB_KIND_GGX);
-		if (st != DJB_OK) return st;
-	}
-	return DJB_OK;
-}
-
-// replaces the resident parameters; a GPU set: one copy on the context's stream, finished when this returns
-djb_status install_params(djb_merl_set *s, const std::vector<Params> &p)
-{
-	if (s->device < 0) { memcpy(s->params, p.data(), sizeof(Params) * p.size()); s->has_params = true; return DJB_OK; }
-	HIP_TRY(hipSetDevice(s->device));
-	std::lock_guard<std::recursive_mutex> call_lock(s->ctx->call_mu);
-	HIP_TRY(hipMemcpyAsync(s->params, p.data(), sizeof(Params) * p.size(), hipMemcpyHostToDevice, s->ctx->stream));
-	HIP_TRY(hipStreamSynchronize(s->ctx->stream));        // `p` is pageable host memory of the caller's frame
-	s->has_params = true;
-	return DJB_OK;
-}
-
 // the proxy of a proxy call (`op`, as the messages name it) is a ggx or beckmann object of the set's context, and the set has parameters for it
 djb_status proxy_check(const djb_ctx *ctx, const djb_merl_set *s, const djb_brdf *proxy, const char *op)
 {
-	if (!proxy) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null brdf (proxy)");
-	djb_status st = cpu_pair_check(ctx, proxy);
+	djb_status st = proxy_object_check(ctx, proxy, "merl set", op);
 	if (st != DJB_OK) return st;
-	const bool cpu = is_cpu(ctx);
-	if (!cpu && (proxy->ctx != ctx || proxy->device != ctx->device))
-		return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: merl set and proxy belong to different contexts");
-	const int pkind = cpu ? djbcpu::kind(proxy) : proxy->dev.kind;
-	if (pkind != DJB_KIND_GGX && pkind != DJB_KIND_BECKMANN)
-		return fail(DJB_ERR_NOT_IMPLEMENTED, "djb_error: %s on a merl set takes a ggx or beckmann proxy (proxy kind %d)", op, pkind);
 	if (!s->has_params) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: the merl set has no proxy parameters (djb_merl_set_set_proxy_params)");
 	return DJB_OK;
 }
@@ -75,7 +41,7 @@ try {
 		src[m] = b->dev.merl;
 	}
 	std::vector<Params> resolved;
-	if (proxy_params && (st = resolve_all(cpu, n_materials, proxy_params, &resolved)) != DJB_OK) return st;
+	if (proxy_params && (st = resolve_all(cpu, n_materials, proxy_params, &resolved, "merl")) != DJB_OK) return st;
 
 	djb_merl_set *s = set_new<djb_merl_set>(ctx, n_materials);
 	const size_t tex_bytes = TABLE_BYTES * (size_t)n_materials, par_bytes = sizeof(Params) * (size_t)n_materials;
@@ -99,7 +65,7 @@ djb_status djb_merl_set_set_proxy_params(djb_merl_set *s, const djb_params *prox
 try {
 	if (!s) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null merl set");
 	std::vector<Params> resolved;
-	djb_status st = resolve_all(s->device < 0, s->n_mat, proxy_params, &resolved);
+	djb_status st = resolve_all(s->device < 0, s->n_mat, proxy_params, &resolved, "merl");
 	if (st != DJB_OK) return st;
 	return install_params(s, resolved);
 }

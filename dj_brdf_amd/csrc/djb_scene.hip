@@ -1,7 +1,8 @@
 // djb_scene.hip -- the C ABI of scenes (include/djb_hip.h: djb_scene): a resident slot table that maps a scene material id to (kind, local
 // id) in up to four member sets -- a MERL set, a UTIA set, an sgd and an abc model set -- evaluated per hit in one call.  The scene borrows
-// its members and copies only the slot table.  Kernels: djb_kernels_scene.hip; host loop (CPU contexts): djb_cpu.cpp; the checks and the
-// entry of a batch: djb_set_host.hpp.  A scene has no host twin: on a GPU context a host batch of any size is staged to the device.
+// its members and copies only the slot table.  Kernels: djb_kernels_scene.hip (eval / evalp), djb_kernels_scene_proxy.hip (the sampling step
+// and the light sample); host loops (CPU contexts): djb_cpu.cpp; the checks and the entry of a batch: djb_set_host.hpp.  A scene has no host
+// twin: on a GPU context a host batch of any size is staged to the device.
 #include "djb_set_host.hpp"
 
 using namespace djbh;
@@ -21,6 +22,60 @@ int kind_code(int kind)
 	case DJB_KIND_ABC: return 3;
 	}
 	return -1;
+}
+
+djbk::SceneMembers members_of(const djb_scene *s)
+{
+	return { s->merl ? s->merl->tex : nullptr, s->merl ? s->merl->n_mat : 0, s->utia ? s->utia->tab : nullptr, s->utia ? s->utia->n_mat : 0,
+	         s->sgd ? s->sgd->rows : nullptr, s->sgd ? s->sgd->n_mat : 0, s->abc ? s->abc->rows : nullptr, s->abc ? s->abc->n_mat : 0 };
+}
+
+// The partition's list, the tile counts, count / offset and the utia worklist share the context's scratch, sized once for the largest
+// chunk of a call of n hits: words [0, 8) count[4] offset[4], [8, 12) the worklist's count, from 16: tiles, list, worklist (wl_cap entries;
+// the proxy calls have none).  *chunk: the hits per chunk
+djb_status scene_scratch(djb_ctx *ctx, long long n, size_t wl_cap, long long *chunk, djbk::SceneScratch *sc)
+{
+	*chunk = ctx->test_scene_chunk > 0 ? ctx->test_scene_chunk : SCENE_CHUNK;                      // DJB_OPT_TEST_SCENE_CHUNK (tests)
+	const long long mc = std::min<long long>(n, *chunk);
+	const size_t tiles = 4 * djbk::scene_tiles(mc);
+	djb_status st = ensure_scratch(ctx, 4 * (16 + tiles + (size_t)mc + (wl_cap ? wl_cap : 1)));
+	if (st != DJB_OK) return st;
+	unsigned int *w = (unsigned int *)ctx->scratch;
+	*sc = { w, w + 16, w + 16 + tiles, w + 8, w + 16 + tiles + (size_t)mc, (unsigned int)wl_cap };
+	return DJB_OK;
+}
+
+// What the two proxy calls ask of the scene's MEMBERS, before anything is launched: a ggx or beckmann `proxy` of the call's context when
+// there is a merl or utia member (the text of the MERL set's proxy_check), and on every member the block its hits will read
+djb_status proxy_members_check(const djb_ctx *ctx, const djb_scene *s, const djb_brdf *proxy, const char *op)
+{
+	djb_status st;
+	if ((s->merl || s->utia) && (st = proxy_object_check(ctx, proxy, "scene", op)) != DJB_OK) return st;
+	if (s->merl && !s->merl->has_params)
+		return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: the scene's merl member has no proxy parameters (djb_merl_set_set_proxy_params)");
+	if (s->utia && !s->utia->has_params)
+		return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: the scene's utia member has no proxy parameters (djb_utia_set_set_proxy_params)");
+	if (s->sgd && !s->sgd->proxy_res) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: the scene's sgd member has no proxy (djb_model_set_fit_proxy)");
+	if (s->abc && !s->abc->proxy_res) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: the scene's abc member has no proxy (djb_model_set_fit_proxy)");
+	return DJB_OK;
+}
+// the members' CURRENT parameter blocks and proxy tables: read at every call, the scene keeps no copy
+djbk::SceneProxies proxies_of(const djb_scene *s)
+{
+	djbk::SceneProxies p = { s->merl ? s->merl->params : nullptr, s->utia ? s->utia->params : nullptr, { nullptr, 0, 0 }, { nullptr, 0, 0 } };
+	if (s->sgd) p.sgd = { s->sgd->proxy_dev, s->sgd->proxy_res, s->sgd->proxy_shadow };
+	if (s->abc) p.abc = { s->abc->proxy_dev, s->abc->proxy_res, s->abc->proxy_shadow };
+	return p;
+}
+djbcpu::SceneProxyHost proxy_host_of(const djb_scene *s)
+{
+	djbcpu::SceneProxyHost h = {};
+	h.slots = s->slots; h.n_slots = s->n_mat;
+	if (s->merl) { h.merl_texels = s->merl->tex; h.merl_params = s->merl->params; }
+	if (s->utia) { h.utia_records = s->utia->tab; h.utia_params = s->utia->params; }
+	if (s->sgd) { h.sgd_rows = s->sgd->rows; h.sgd_block = s->sgd->proxy_host.data(); h.n_sgd = s->sgd->n_mat; h.sgd_res = s->sgd->proxy_res; h.sgd_shadow = s->sgd->proxy_shadow; }
+	if (s->abc) { h.abc_rows = s->abc->rows; h.abc_block = s->abc->proxy_host.data(); h.n_abc = s->abc->n_mat; h.abc_res = s->abc->proxy_res; h.abc_shadow = s->abc->proxy_shadow; }
+	return h;
 }
 
 } // namespace
@@ -108,23 +163,88 @@ try {
 	                        { c.dmat, 1 } };
 	const Stream outs[3] = { { vout.x, vout.stride }, { vout.y, vout.stride }, { vout.z, vout.stride } };
 	const bool utia_exact = ctx->utia_exact_only != 0 || (mem == DJB_MEM_DEVICE && outputs_overlap_inputs(n, ins, 7, outs, 3));
-	const djbk::SceneMembers mb = { s->merl ? s->merl->tex : nullptr, s->merl ? s->merl->n_mat : 0, s->utia ? s->utia->tab : nullptr,
-	                                s->utia ? s->utia->n_mat : 0, s->sgd ? s->sgd->rows : nullptr, s->sgd ? s->sgd->n_mat : 0,
-	                                s->abc ? s->abc->rows : nullptr, s->abc ? s->abc->n_mat : 0 };
-	// the partition's list, the tile counts, count / offset and the utia worklist share the context's scratch, sized once for the largest
-	// chunk of this call: words [0, 8) count[4] offset[4], [8, 12) the worklist's count, from 16: tiles, list, worklist
-	const long long chunk = ctx->test_scene_chunk > 0 ? ctx->test_scene_chunk : SCENE_CHUNK;       // DJB_OPT_TEST_SCENE_CHUNK (tests)
-	const long long mc = std::min<long long>(n, chunk);
-	const size_t tiles = 4 * djbk::scene_tiles(mc);
-	size_t cap = (size_t)(mc / 256 + 4096);
+	const djbk::SceneMembers mb = members_of(s);
+	size_t cap = (size_t)(std::min<long long>(n, ctx->test_scene_chunk > 0 ? ctx->test_scene_chunk : SCENE_CHUNK) / 256 + 4096);
 	if (ctx->test_worklist_cap >= 0) cap = (size_t)ctx->test_worklist_cap;                         // DJB_OPT_TEST_WORKLIST_CAP (tests): force the overflow path
-	if ((st = ensure_scratch(ctx, 4 * (16 + tiles + (size_t)mc + (cap ? cap : 1)))) != DJB_OK) return st;
-	unsigned int *w = (unsigned int *)ctx->scratch;
-	const djbk::SceneScratch sc = { w, w + 16, w + 16 + tiles, w + 8, w + 16 + tiles + (size_t)mc, (unsigned int)cap };
+	long long chunk;
+	djbk::SceneScratch sc;
+	if ((st = scene_scratch(ctx, n, cap, &chunk, &sc)) != DJB_OK) return st;
 	for (long long lo = 0; lo < n; lo += chunk) {                                                  // back to back on the context's stream
 		const long long m = std::min(n - lo, chunk);
 		HIP_TRY(djbk::launch_scene_eval(ctx->stream, mb, s->slots, s->n_mat, m, c.dmat + lo, offset_view(vi, lo), offset_view(vo, lo), offset_view(vout, lo),
 		                                want_cos != 0, sc, ctx->merl_exact_only != 0, utia_exact, ctx->model_set_rows_global != 0));
+	}
+	return c.sg.finish();
+}
+DJB_ABI_CATCH
+
+// Overlap: index-aligned in-place views only.  Every lane reads its hit before it writes it, kinds touch disjoint hits, the MERL drains work
+// on their queued records and no kernel here takes a second pass over a hit, so nothing needs the exact-only detour of the eval call
+djb_status djb_scene_evalp_is_proxy_batch(djb_ctx *ctx, const djb_scene *s, const djb_brdf *proxy, int64_t n, const int32_t *material, const float *u1,
+                                          const float *u2, const djb_vec3_view *o, const djb_vec3_view *out_weight, const djb_vec3_view *out_i,
+                                          float *out_pdf, int mem)
+try {
+	djb_status st = set_check(ctx, s, "scene");
+	if (st != DJB_OK) return st;
+	if ((st = proxy_members_check(ctx, s, proxy, "evalp_is_proxy")) != DJB_OK) return st;
+	const djb_brdf *lobe = s->merl || s->utia ? proxy : nullptr;                                   // not looked at without such a member
+	if (is_cpu(ctx)) return djbcpu::scene_evalp_is_proxy(ctx, proxy_host_of(s), lobe, n, material, u1, u2, o, out_weight, out_i, out_pdf);
+	if (!Staged::valid(out_weight) || !Staged::valid(out_i) || !out_pdf) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null output");
+	if ((st = check_call(ctx, lobe, n, mem)) != DJB_OK) return st;
+	std::lock_guard<std::recursive_mutex> call_lock(ctx->call_mu);
+	Params model_p;
+	if ((st = device_params(nullptr, &model_p, DJB_KIND_TABULAR)) != DJB_OK) return st;            // as the model set's call resolves it
+	Staged sg(ctx, n, mem);
+	const int32_t *dmat; View vo, vi, vw; const float *d1, *d2; float *dpdf = nullptr;
+	if ((st = stage_material(sg, material, &dmat)) != DJB_OK) return st;
+	if ((st = sg.in_f(u1, &d1)) != DJB_OK) return st;
+	if ((st = sg.in_f(u2, &d2)) != DJB_OK) return st;
+	if ((st = sg.in_vec(o, &vo)) != DJB_OK) return st;
+	if ((st = sg.out_vec(out_i, &vi)) != DJB_OK) return st;
+	if ((st = sg.out_vec(out_weight, &vw)) != DJB_OK) return st;
+	if ((st = sg.out_arr(out_pdf, &dpdf)) != DJB_OK) return st;
+	if (n <= 0) return sg.finish();
+	long long chunk;
+	djbk::SceneScratch sc;
+	if ((st = scene_scratch(ctx, n, 0, &chunk, &sc)) != DJB_OK) return st;
+	const djbk::SceneMembers mb = members_of(s);
+	const djbk::SceneProxies px = proxies_of(s);
+	for (long long lo = 0; lo < n; lo += chunk) {                                                  // back to back on the context's stream
+		const long long m = std::min(n - lo, chunk);
+		HIP_TRY(djbk::launch_scene_evalp_is_proxy(ctx->stream, mb, px, lobe ? &lobe->dev : nullptr, model_p, s->slots, s->n_mat, m, dmat + lo, d1 + lo, d2 + lo,
+		                                          offset_view(vo, lo), offset_view(vw, lo), offset_view(vi, lo), dpdf + lo, sc, ctx->merl_exact_only != 0,
+		                                          ctx->model_set_rows_global != 0));
+	}
+	return sg.finish();
+}
+DJB_ABI_CATCH
+
+djb_status djb_scene_evalp_pdf_proxy_batch(djb_ctx *ctx, const djb_scene *s, const djb_brdf *proxy, int64_t n, const int32_t *material,
+                                           const djb_vec3_view *i, const djb_vec3_view *o, const djb_vec3_view *out_fr, float *out_pdf, int mem)
+try {
+	djb_status st = set_check(ctx, s, "scene");
+	if (st != DJB_OK) return st;
+	if ((st = proxy_members_check(ctx, s, proxy, "evalp_pdf_proxy")) != DJB_OK) return st;
+	if (!out_pdf) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null out_pdf (evalp alone: djb_scene_eval_batch)");
+	const djb_brdf *lobe = s->merl || s->utia ? proxy : nullptr;                                   // not looked at without such a member
+	if (is_cpu(ctx)) return djbcpu::scene_evalp_pdf(ctx, proxy_host_of(s), lobe, n, material, i, o, out_fr, out_pdf);
+	Params model_p;
+	if ((st = device_params(nullptr, &model_p, DJB_KIND_TABULAR)) != DJB_OK) return st;
+	SetBatch c(ctx, lobe, n, mem, material, i, o, out_fr);
+	if (c.st != DJB_OK) return c.st;
+	float *dpdf = nullptr;
+	if ((st = c.sg.out_arr(out_pdf, &dpdf)) != DJB_OK) return st;
+	if (n <= 0) return c.sg.finish();
+	long long chunk;
+	djbk::SceneScratch sc;
+	if ((st = scene_scratch(ctx, n, 0, &chunk, &sc)) != DJB_OK) return st;
+	const djbk::SceneMembers mb = members_of(s);
+	const djbk::SceneProxies px = proxies_of(s);
+	for (long long lo = 0; lo < n; lo += chunk) {
+		const long long m = std::min(n - lo, chunk);
+		HIP_TRY(djbk::launch_scene_evalp_pdf_proxy(ctx->stream, mb, px, lobe ? &lobe->dev : nullptr, model_p, s->slots, s->n_mat, m, c.dmat + lo,
+		                                           offset_view(c.vi, lo), offset_view(c.vo, lo), offset_view(c.vout, lo), dpdf + lo, sc,
+		                                           ctx->merl_exact_only != 0, ctx->model_set_rows_global != 0));
 	}
 	return c.sg.finish();
 }

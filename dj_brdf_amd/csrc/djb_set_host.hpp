@@ -1,7 +1,7 @@
 // djb_set_host.hpp -- what the C ABIs of the three material sets and of scenes share (djb_merl_set.hip, djb_utia_set.hip, djb_model_set.hip,
 // djb_scene.hip; included by those alone): the checks of a handle, a member and a count, the construction and release of the resident block,
-// and the entry of an eval batch.  `what` is the set's noun in the messages: "merl" / "utia" / "model" / "scene".  Everything works on
-// djb_set_base (djb_host.hpp).
+// the proxy parameter block of the MERL and UTIA sets and the check of a proxy object, and the entry of an eval batch.  `what` is the set's
+// noun in the messages: "merl" / "utia" / "model" / "scene".  Everything works on djb_set_base (djb_host.hpp).
 #pragma once
 #include "djb_host.hpp"
 
@@ -74,6 +74,47 @@ inline hipError_t set_gather(djb_ctx *ctx, void **block, size_t each, const std:
 	for (size_t m = 0; m < src.size() && e == hipSuccess; ++m)
 		e = hipMemcpyAsync((char *)*block + m * each, src[m], each, hipMemcpyDeviceToDevice, ctx->stream);
 	return e == hipSuccess ? hipStreamSynchronize(ctx->stream) : e;
+}
+
+// ---- the proxy parameter block of a MERL or UTIA set: n_mat plain parameter sets -> Params as the single-material calls of the set's back
+// end resolve them (`what`: "merl" / "utia")
+inline djb_status resolve_all(bool cpu, int n_mat, const djb_params *in, std::vector<Params> *out, const char *what)
+{
+	if (!in) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null proxy_params");
+	out->resize((size_t)n_mat);
+	for (int m = 0; m < n_mat; ++m) {
+		if (in[m].kind & DJB_PARAMS_RESOLVED_FOLLOWS)
+			return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: proxy_params[%d] carries DJB_PARAMS_RESOLVED_FOLLOWS: a %s set takes plain djb_params", m, what);
+		memset(&(*out)[m], 0, sizeof(Params));
+		djb_status st = cpu ? djbcpu::merl_set_resolve_params(&in[m], &(*out)[m]) : device_params(&in[m], &(*out)[m], DJB_KIND_GGX);
+		if (st != DJB_OK) return st;
+	}
+	return DJB_OK;
+}
+// replaces the resident parameters (s->params holds n_mat Params); a GPU set: one copy on the context's stream, finished when this returns
+template <class S> djb_status install_params(S *s, const std::vector<Params> &p)
+{
+	if (s->device < 0) { memcpy(s->params, p.data(), sizeof(Params) * p.size()); s->has_params = true; return DJB_OK; }
+	HIP_TRY(hipSetDevice(s->device));
+	std::lock_guard<std::recursive_mutex> call_lock(s->ctx->call_mu);
+	HIP_TRY(hipMemcpyAsync(s->params, p.data(), sizeof(Params) * p.size(), hipMemcpyHostToDevice, s->ctx->stream));
+	HIP_TRY(hipStreamSynchronize(s->ctx->stream));        // `p` is pageable host memory of the caller's frame
+	s->has_params = true;
+	return DJB_OK;
+}
+// the proxy of a per-hit proxy call (`op`, as the messages name it) on `what` ("merl set" / "scene"): a ggx or beckmann object of the call's context
+inline djb_status proxy_object_check(const djb_ctx *ctx, const djb_brdf *proxy, const char *what, const char *op)
+{
+	if (!proxy) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null brdf (proxy)");
+	djb_status st = cpu_pair_check(ctx, proxy);
+	if (st != DJB_OK) return st;
+	const bool cpu = is_cpu(ctx);
+	if (!cpu && (proxy->ctx != ctx || proxy->device != ctx->device))
+		return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: %s and proxy belong to different contexts", what);
+	const int pkind = cpu ? djbcpu::kind(proxy) : proxy->dev.kind;
+	if (pkind != DJB_KIND_GGX && pkind != DJB_KIND_BECKMANN)
+		return fail(DJB_ERR_NOT_IMPLEMENTED, "djb_error: %s on a %s takes a ggx or beckmann proxy (proxy kind %d)", op, what, pkind);
+	return DJB_OK;
 }
 
 // The entry of a batch call on a GPU context's set, after set_check and the CPU dispatch: check_call, the call lock (held while this

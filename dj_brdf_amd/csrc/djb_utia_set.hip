@@ -1,5 +1,5 @@
 // djb_utia_set.hip -- the C ABI of UTIA material sets (include/djb_hip.h: djb_utia_set): M resident UTIA record tables in one block,
-// evaluated per hit by material id.  Kernels: djb_kernels_utia_set.hip; host loop (CPU contexts): djb_cpu.cpp; what the three kinds of
+// evaluated per hit by material id, and -- once given -- one resolved proxy parameter set per material, which a scene's proxy calls read.  Kernels: djb_kernels_utia_set.hip; host loop (CPU contexts): djb_cpu.cpp; what the three kinds of
 // set share: djb_set_host.hpp.  A set has no host twin: on a GPU context a host batch of any size is staged to the device.
 #include "djb_set_host.hpp"
 
@@ -51,9 +51,39 @@ try {
 }
 DJB_ABI_CATCH
 
+// The block is allocated by the first call (a new set has no proxy parameters); the resolve and the exchange are the MERL set's (djb_set_host.hpp)
+djb_status djb_utia_set_set_proxy_params(djb_utia_set *s, const djb_params *proxy_params)
+try {
+	if (!s) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null utia set");
+	std::vector<Params> resolved;
+	djb_status st = resolve_all(s->device < 0, s->n_mat, proxy_params, &resolved, "utia");
+	if (st != DJB_OK) return st;
+	if (!s->params) {
+		const size_t bytes = sizeof(Params) * (size_t)s->n_mat;
+		if (s->device < 0) {
+			s->params = (Params *)calloc((size_t)s->n_mat, sizeof(Params));
+			if (!s->params) return fail(DJB_ERR_OUT_OF_MEMORY, "djb_error: out of host memory (proxy parameters of a utia set of %d tables)", s->n_mat);
+		} else {
+			HIP_TRY(hipSetDevice(s->device));
+			std::lock_guard<std::recursive_mutex> call_lock(s->ctx->call_mu);
+			HIP_TRY(hipMalloc((void **)&s->params, bytes));
+		}
+	}
+	return install_params(s, resolved);
+}
+DJB_ABI_CATCH
+
+djb_status djb_utia_set_proxy_info(const djb_utia_set *s, int *has_proxy_params)
+try {
+	if (!s) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null utia set");
+	if (has_proxy_params) *has_proxy_params = s->has_params ? 1 : 0;
+	return DJB_OK;
+}
+DJB_ABI_CATCH
+
 djb_status djb_utia_set_destroy(djb_utia_set *s)
 try {
-	return s ? set_free(s, s->tab) : DJB_OK;
+	return s ? set_free(s, s->tab, s->params) : DJB_OK;
 }
 DJB_ABI_CATCH
 

@@ -1277,7 +1277,9 @@ class utia(brdf):
 class utia_set(_material_set):
     """M UTIA materials resident in ONE block on their context's device: hits that land on many measured materials are evaluated in one
     call, each hit naming its material by id (djb_utia_set, include/djb_hip.h).  An extension: the reference's objects are one material
-    each.  ``eval`` / ``evalp`` are all that dj_utia asks of its table (it samples the cosine hemisphere), so there is no proxy.
+    each.  ``eval`` / ``evalp`` are all that dj_utia asks of its table (it samples the cosine hemisphere), so the set has no sampling
+    calls of its own; it can carry one proxy parameter set per material (``set_proxy_params`` / ``fit_proxies``), which a ``scene``
+    samples its utia hits from.
 
     ``material``: int32 ids, one per hit; an id outside [0, M) marks an inactive hit (a dead path), whose output is +0.  An active
     hit gets the bits of the single-material call on its material.  Arrays: numpy (host) or torch CUDA (device), in the layouts the
@@ -1289,6 +1291,7 @@ class utia_set(_material_set):
         brdfs = list(brdfs)
         self.ctx = ctx or (brdfs[0].ctx if brdfs else default_context())
         self._h = C.c_void_p()
+        self._members = brdfs                      # kept for fit_proxies(); the set itself holds copies of their tables
         ptrs = (C.c_void_p * max(len(brdfs), 1))(*[getattr(b._h, "value", None) for b in brdfs])
         _lib.check(_lib.load().djb_utia_set_create(self.ctx._h, C.c_int(len(brdfs)), ptrs, C.byref(self._h)))
 
@@ -1308,6 +1311,31 @@ class utia_set(_material_set):
         n = C.c_int()
         _lib.check(_lib.load().djb_utia_set_info(self._h, C.byref(n)))
         return n.value
+
+    @property
+    def has_proxy_params(self) -> bool:
+        has = C.c_int()
+        _lib.check(_lib.load().djb_utia_set_proxy_info(self._h, C.byref(has)))
+        return bool(has.value)
+
+    def set_proxy_params(self, proxy_params):
+        """one ``microfacet.params`` per material, the lobe a ``scene`` samples this material's hits from; replaces the resident set in
+        stream order"""
+        _lib.check(_lib.load().djb_utia_set_set_proxy_params(self._h, merl_set._params_array(proxy_params, self.n_materials)))
+
+    def fit_proxies(self, res: int = 90, shadow: bool = False):
+        """``fit_ggx_parameters(tabular(utia, res, shadow))`` of every member, one batched fit, installed as
+        ``params.isotropic(alpha_ggx)`` per material, as ``merl_set.fit_proxies``.  Returns (alpha_beckmann[M], alpha_ggx[M]).  Needs the
+        member objects the set was built from (``from_tables`` closes its own)."""
+        if any(not b._h for b in self._members):
+            raise exc(1, "djb_error: fit_proxies needs the member objects the set was built from (one was closed)")
+        uniq = list({id(b): b for b in self._members}.values())
+        ab_u, ag_u = fit_brdf_batch(uniq, res, shadow, ctx=self.ctx)
+        at = {id(b): k for k, b in enumerate(uniq)}
+        sel = [at[id(b)] for b in self._members]
+        ab, ag = ab_u[sel], ag_u[sel]
+        self.set_proxy_params([microfacet.params.isotropic(float(a)) for a in ag])
+        return ab, ag
 
 
 class model_set(_material_set):
@@ -1433,7 +1461,10 @@ class scene(_material_set):
     """A slot table over up to four member sets -- a ``merl_set``, a ``utia_set``, an sgd and an abc ``model_set`` of one context --: hits
     that land on measured, UTIA and data-driven materials at once are evaluated in one call, each hit naming its material by SCENE id
     (djb_scene, include/djb_hip.h).  On the GPU the batch is partitioned by kind on the device and each member's kernel runs on its
-    dense list of hits.  ``eval`` / ``evalp`` only: sampling and the light sample stay with the sets.
+    dense list of hits.  ``eval`` / ``evalp``, and the two per-hit proxy steps ``evalp_is_proxy`` / ``evalp_pdf_proxy``: a merl or utia
+    hit is sampled from ``proxy`` (a ggx or beckmann object) with its material's proxy parameters, an sgd or abc hit from its material's
+    fitted tabular lobe -- so a merl or utia member needs ``set_proxy_params`` / ``fit_proxies`` and a model member ``fit_proxy`` first
+    (before or after the scene is built: every call reads the members' current blocks).
 
     ``slots``: one ``(kind, local)`` pair per scene id, ``kind`` one of "merl", "utia", "sgd", "abc" (or the DJB_KIND_* value) and ``local``
     the material's id in that member set; ``None`` (or kind "none") is a slot without material.  Two slots may name one material.
@@ -1478,6 +1509,37 @@ class scene(_material_set):
     def members(self):
         """materials per kind (merl, utia, sgd, abc); 0: the scene has no such set"""
         return self._info()[1]
+
+    def evalp_is_proxy(self, proxy, material, u1, u2, o):
+        """(weight, i, pdf) per hit, the sampling step of a path vertex: what the hit's member set's ``evalp_is_proxy`` returns for it (utia:
+        ``brdf.evalp_is_proxy`` on the material with the utia set's parameters); an inactive hit is +0 in all three.  ``proxy`` may be
+        None for a scene without merl and utia members."""
+        vo = _Vec(o)
+        keep, mp = self._ids(material, vo)
+        k1, p1 = _scalar_in(u1, vo)
+        k2, p2 = _scalar_in(u2, vo)
+        w, i = vo.like(), vo.like()
+        pdf, pdf_ptr = vo.scalars()
+        _lib.check(_lib.load().djb_scene_evalp_is_proxy_batch(self.ctx._h, self._h, getattr(proxy, "_h", None), C.c_int64(vo.n), C.c_void_p(mp),
+                                                             C.c_void_p(p1), C.c_void_p(p2), C.byref(vo.view), C.byref(w.view), C.byref(i.view),
+                                                             C.c_void_p(pdf_ptr), C.c_int(vo.mem)))
+        del keep, k1, k2
+        return w.keep, i.keep, pdf
+
+    def evalp_pdf_proxy(self, proxy, material, i, o):
+        """(fr, pdf) per hit for GIVEN pairs, the light sample of a path vertex: what the hit's member set's ``evalp_pdf_proxy`` returns
+        for it (utia: ``brdf.evalp_pdf_proxy`` with the utia set's parameters); both +0 where i.z <= 0 or o.z <= 0, and for an inactive
+        hit.  ``proxy`` may be None for a scene without merl and utia members."""
+        vi, vo = _Vec(i), _Vec(o)
+        if vi.n != vo.n or vi.mem != vo.mem:
+            raise exc(1, "djb_error: i and o must have the same length and memory space")
+        keep, mp = self._ids(material, vi)
+        fr = vi.like()
+        pdf, pdf_ptr = vi.scalars()
+        _lib.check(_lib.load().djb_scene_evalp_pdf_proxy_batch(self.ctx._h, self._h, getattr(proxy, "_h", None), C.c_int64(vi.n), C.c_void_p(mp),
+                                                              C.byref(vi.view), C.byref(vo.view), C.byref(fr.view), C.c_void_p(pdf_ptr), C.c_int(vi.mem)))
+        del keep
+        return fr.keep, pdf
 
 
 # --------------------------------------------------------------------------- user-defined BRDFs (dj_brdf.h:74-109)

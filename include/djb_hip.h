@@ -85,7 +85,10 @@ extern "C" {
  *        djb_model_set_evalp_pdf_proxy_batch (the sampling step and the light sample of dj_sgd / dj_abc per hit, one call each).
  *        Additive under 235, no existing entry changed: scenes -- djb_scene, djb_scene_slot, DJB_SCENE_NONE, DJB_SCENE_MAX_SLOTS,
  *        djb_scene_create, djb_scene_info, djb_scene_destroy, djb_scene_eval_batch (eval / evalp of hits that land on a MERL set, a UTIA
- *        set, an sgd and an abc model set at once, by per-hit scene material id, one call), DJB_OPT_TEST_SCENE_CHUNK. */
+ *        set, an sgd and an abc model set at once, by per-hit scene material id, one call), DJB_OPT_TEST_SCENE_CHUNK.
+ *        Additive under 235, no existing entry changed: proxy parameters on a UTIA set -- djb_utia_set_set_proxy_params,
+ *        djb_utia_set_proxy_info -- and the two per-hit steps on a scene -- djb_scene_evalp_is_proxy_batch,
+ *        djb_scene_evalp_pdf_proxy_batch (the sampling step and the light sample across all four member kinds, one call each). */
 #define DJB_HIP_VERSION 235
 #define DJB_HIP_VERSION_MAJOR(v) ((v) / 100)
 
@@ -595,7 +598,14 @@ djb_status djb_merl_set_evalp_pdf_proxy_batch(djb_ctx *, const djb_merl_set *, c
 /* ---- UTIA material sets: djb_merl_set's answer for the other tabulated family.  The cells, angles, weights and tap order of a UTIA
  * look-up depend on (i, o) alone, never on the material: they are computed once per hit and only the base of the hit's two 128-byte
  * records moves with its id.  mitsuba/dj_utia.cpp asks its table for eval and evalp alone (its sampling is the cosine hemisphere, whose
- * pdf i.z / pi needs no table): a set with eval / evalp is the whole plugin per hit.  There is no proxy and no parameter block.
+ * pdf i.z / pi needs no table): a set with eval / evalp is the whole plugin per hit.  There is no proxy and no parameter block in the
+ * set's own calls; a set may CARRY one resolved proxy parameter set per material for the scene's two proxy calls (below), which sample a
+ * utia hit from a ggx / beckmann lobe as djb_evalp_is_proxy_batch does for the single object.
+ *
+ * Proxy parameters.  djb_utia_set_set_proxy_params takes n_materials plain djb_params in host memory under the rules of
+ * djb_merl_set_set_proxy_params: any kind djb_params_resolve accepts, DJB_PARAMS_RESOLVED_FOLLOWS refused, resolved once on the host,
+ * resident as Params[M] (a host array on CPU contexts), replaced in stream order on the context's stream; the call returns when the
+ * block is in place.  A new set has none: djb_utia_set_proxy_info stores 0.
  *
  * Creation.  djb_utia_set_create copies the converted record tables of n_materials utia objects into ONE contiguous block,
  * float4[M][288 * 288 * 8] (10 616 832 bytes per material, allocated once).  Every source object must be a utia object of the call's
@@ -618,6 +628,8 @@ djb_status djb_merl_set_evalp_pdf_proxy_batch(djb_ctx *, const djb_merl_set *, c
 #define DJB_UTIA_SET_MAX 256
 djb_status djb_utia_set_create(djb_ctx *, int n_materials, const djb_brdf *const *utias, djb_utia_set **out);
 djb_status djb_utia_set_info(const djb_utia_set *, int *n_materials);
+djb_status djb_utia_set_set_proxy_params(djb_utia_set *, const djb_params *proxy_params /* n_materials */);
+djb_status djb_utia_set_proxy_info(const djb_utia_set *, int *has_proxy_params);
 djb_status djb_utia_set_destroy(djb_utia_set *);
 djb_status djb_utia_set_eval_batch(djb_ctx *, const djb_utia_set *, int64_t n, const int32_t *material,
                                    const djb_vec3_view *i, const djb_vec3_view *o, int want_cos,
@@ -701,7 +713,7 @@ djb_status djb_model_set_evalp_pdf_proxy_batch(djb_ctx *, const djb_model_set *,
 /* ---- scenes: one call for a hit batch that lands on measured, UTIA and data-driven materials at once.  A material set holds materials
  * of ONE kind; a wavefront renderer's bounce does not.  A scene is a resident slot table that maps a SCENE material id to (kind, local id)
  * in up to four member sets -- a MERL set, a UTIA set, an sgd model set and an abc model set -- so that the caller need not split the
- * batch by kind, gather sub-batches and scatter the results back.  eval / evalp only: sampling and the light sample stay with the sets.
+ * batch by kind, gather sub-batches and scatter the results back.  eval / evalp, and the two per-hit proxy steps (further below).
  *
  * Creation.  Any member set may be NULL, at least one must be given; every given set belongs to the call's context, `sgd` is a model set of
  * kind sgd and `abc` one of kind abc.  slots: n_slots entries in host memory, 1 <= n_slots <= DJB_SCENE_MAX_SLOTS.  Every slot names a
@@ -736,6 +748,41 @@ djb_status djb_scene_info(const djb_scene *, int *n_slots, int members[4] /* mat
 djb_status djb_scene_destroy(djb_scene *);
 djb_status djb_scene_eval_batch(djb_ctx *, const djb_scene *, int64_t n, const int32_t *material, const djb_vec3_view *i,
                                 const djb_vec3_view *o, int want_cos, const djb_vec3_view *out_fr, int mem);
+
+/* ---- the two per-hit proxy steps on a scene: the sampling step and the light sample of a path vertex, whatever kind the hit lands on.
+ * Per hit, bit for bit:
+ *   slot kind merl, local m      djb_merl_set_evalp_is_proxy_batch / djb_merl_set_evalp_pdf_proxy_batch on material m with `proxy`
+ *   slot kind utia, local m      djb_evalp_is_proxy_batch / djb_evalp_pdf_proxy_batch(target = material m, proxy, proxy_params = the utia
+ *                                set's parameters of material m); the light sample takes the i.z <= 0 || o.z <= 0 guard of the other kinds
+ *   slot kind sgd / abc, local m djb_model_set_evalp_is_proxy_batch / djb_model_set_evalp_pdf_proxy_batch on material m, against the set's
+ *                                fitted tabular proxy (`proxy` is not used)
+ *   an id outside [0, n_slots), or a slot without material: +0.0f in every output (weight, i, pdf; or fr, pdf), nothing read for the hit
+ * What the member calls define carries over: sampling stores i in every case, weight = 0 and pdf = 0 where i.z <= 0 (a NaN i.z is
+ * evaluated), o is unguarded, the division by a zero pdf gives the IEEE result; a light-sample hit with i.z <= 0 || o.z <= 0 is +0 in both
+ * outputs and reads nothing (a NaN z is evaluated).
+ *
+ * Preconditions, checked on the host before any launch by the MEMBERS the scene has, not by the hits (no read-back): when the scene has a
+ * merl or a utia member, `proxy` is a ggx or beckmann object of the call's context (NULL: DJB_ERR_INVALID_ARGUMENT, another kind:
+ * DJB_ERR_NOT_IMPLEMENTED) and that member has proxy parameters (else DJB_ERR_INVALID_ARGUMENT; the message names the member); an sgd
+ * or abc member has a fitted proxy (else DJB_ERR_INVALID_ARGUMENT).  A scene with model members alone takes proxy == NULL.  out_pdf ==
+ * NULL is DJB_ERR_INVALID_ARGUMENT.  The scene borrows its members: each call reads their CURRENT parameter blocks and proxy tables, so
+ * a djb_*_set_set_proxy_params or a refit after djb_scene_create is what the next call sees.
+ *
+ * On a GPU context: the partition of djb_scene_eval_batch (same tiles, scratch and chunks of 2^24 hits, DJB_OPT_TEST_SCENE_CHUNK
+ * honoured), whose scatter stores the +0 of an inactive hit in every output, then ONE kernel per member set on its dense list of hits.
+ * The utia part runs the exact look-up in place (no worklist, no second pass).  DJB_OPT_MERL_EXACT_ONLY, DJB_OPT_MODEL_SET_ROWS_GLOBAL
+ * and DJB_SGD_FAST=0 at the sgd set's creation are honoured as the member sets honour them.  A device-memory call reads nothing back and
+ * allocates nothing once the context's scratch has its size: after one call of that size it can be captured into a hipGraph.
+ * Overlap: index-aligned in-place views only (out_i over o, out_fr over i, ...): every lane reads its hit before it writes it, kinds
+ * touch disjoint hits and no kernel takes a second pass over a hit; any other overlap of an output with an input, the ids included, is
+ * undefined.  A host-memory batch of any size is staged through HBM.  CPU contexts classify each hit through the table and run the
+ * member's per-hit host code. */
+djb_status djb_scene_evalp_is_proxy_batch(djb_ctx *, const djb_scene *, const djb_brdf *proxy, int64_t n, const int32_t *material,
+                                          const float *u1, const float *u2, const djb_vec3_view *o,
+                                          const djb_vec3_view *out_weight, const djb_vec3_view *out_i, float *out_pdf, int mem);
+djb_status djb_scene_evalp_pdf_proxy_batch(djb_ctx *, const djb_scene *, const djb_brdf *proxy, int64_t n, const int32_t *material,
+                                           const djb_vec3_view *i, const djb_vec3_view *o,
+                                           const djb_vec3_view *out_fr, float *out_pdf, int mem);
 
 /* beckmann::lrep algebra on {E1..E5} (host scalars; dj_brdf.h:330-356, 1959-2051).  b may be NULL
  * (= the default lrep(0,0,1,1,0)); x (and y) are the scalar arguments of mul / shear / scale.

@@ -1278,6 +1278,16 @@ private:
 	int m_elev, m_azim;
 };
 
+namespace hip {
+// the facade's params carry their resolved form; a material set takes the plain parameter sets and resolves them itself
+inline std::vector<djb_params> plain_params(size_t n, const microfacet::params *p)
+{
+	std::vector<djb_params> v(p ? n : 0);
+	for (size_t k = 0; k < v.size(); ++k) { v[k] = *p[k].desc(); v[k].kind = DJB_PARAMS_KIND(v[k].kind); }
+	return v;
+}
+} // namespace hip
+
 /* M MERL materials resident in one block on their context's device, with one fitted proxy parameter set per material
  * (include/djb_hip.h, djb_merl_set): the hits of a wavefront renderer land on many measured materials; each hit names its material
  * by id and the whole batch is one call.  An extension with no counterpart in the reference, whose objects are one material each.
@@ -1326,13 +1336,7 @@ public:
 	                           const djb_vec3_view &out_fr, float_t *out_pdf, int mem) const
 	{ hip::check(djb_merl_set_evalp_pdf_proxy_batch(ctx(), m_h, proxy.handle(), n, material, &i, &o, &out_fr, out_pdf, mem)); }
 private:
-	// the facade's params carry their resolved form; a set takes the plain parameter sets and resolves them itself
-	static std::vector<djb_params> plain(size_t n, const microfacet::params *p)
-	{
-		std::vector<djb_params> v(p ? n : 0);
-		for (size_t k = 0; k < v.size(); ++k) { v[k] = *p[k].desc(); v[k].kind = DJB_PARAMS_KIND(v[k].kind); }
-		return v;
-	}
+	static std::vector<djb_params> plain(size_t n, const microfacet::params *p) { return hip::plain_params(n, p); }
 	djb_ctx *ctx() const { return (m_ctx ? *m_ctx : hip::context::standard()).get(); }
 	hip::context *m_ctx;
 	djb_merl_set *m_h;
@@ -1340,8 +1344,9 @@ private:
 
 /* M UTIA materials resident in one block on their context's device (include/djb_hip.h, djb_utia_set): each hit names its material by
  * id and the whole batch is one call.  An extension with no counterpart in the reference.  eval / evalp are all that dj_utia asks of
- * its table (mitsuba/dj_utia.cpp samples the cosine hemisphere): no proxy, no parameters.  An id outside [0, size()) marks an inactive
- * hit: its output is +0.  An active hit gets the bits of utia::eval / evalp on its material. */
+ * its table (mitsuba/dj_utia.cpp samples the cosine hemisphere): no sampling calls of its own.  It can carry one proxy parameter set
+ * per material (set_proxy_params), which a scene samples its utia hits from.  An id outside [0, size()) marks an inactive hit: its
+ * output is +0.  An active hit gets the bits of utia::eval / evalp on its material. */
 class utia_set {
 public:
 	/* the record tables of n utia objects are copied: the objects may be destroyed afterwards */
@@ -1358,6 +1363,10 @@ public:
 	utia_set &operator=(const utia_set &) = delete;
 	const djb_utia_set *get() const { return m_h; }
 	int size() const { int v; hip::check(djb_utia_set_info(m_h, &v)); return v; }
+	bool has_proxy_params() const { int v; hip::check(djb_utia_set_proxy_info(m_h, &v)); return v != 0; }
+	/* one set per material: the ggx / beckmann lobe a scene's evalp_is_proxy / evalp_pdf_proxy use for this material's hits */
+	void set_proxy_params(const microfacet::params *proxy_params)
+	{ std::vector<djb_params> p = hip::plain_params((size_t)size(), proxy_params); hip::check(djb_utia_set_set_proxy_params(m_h, p.data())); }
 	// ---- host arrays
 	void eval(size_t n, const int32_t *material, const vec3 *i, const vec3 *o, vec3 *out) const { eval_views((int64_t)n, material, hip::view(i), hip::view(o), hip::view(out), 0, DJB_MEM_HOST); }
 	void evalp(size_t n, const int32_t *material, const vec3 *i, const vec3 *o, vec3 *out) const { eval_views((int64_t)n, material, hip::view(i), hip::view(o), hip::view(out), 1, DJB_MEM_HOST); }
@@ -1444,7 +1453,10 @@ private:
  * and the whole batch is one call.  An extension with no counterpart in the reference.  slots[k] = { kind, local }: kind DJB_KIND_MERL,
  * DJB_KIND_UTIA, DJB_KIND_SGD or DJB_KIND_ABC and the material's id in that member, or kind DJB_SCENE_NONE, a slot without material.  A
  * hit whose id is outside [0, size()) or whose slot has no material is inactive: its output is +0.  An active hit gets the bits of its
- * member set's call.  The scene BORROWS its members: they must outlive it.  Any member may be NULL, not all. */
+ * member set's call.  The scene BORROWS its members: they must outlive it.  Any member may be NULL, not all.
+ * evalp_is_proxy / evalp_pdf_proxy are the sampling step and the light sample of a path vertex per hit: a merl or utia hit takes its
+ * direction and pdf from `proxy` (a ggx or beckmann object) with its material's proxy parameters, an sgd or abc hit from its material's
+ * fitted tabular lobe; the members need set_proxy_params / fit_proxy first.  proxy may be NULL for a scene with model members alone. */
 class scene {
 public:
 	scene(const merl_set *merl, const utia_set *utia, const model_set *sgd, const model_set *abc, size_t n_slots, const djb_scene_slot *slots,
@@ -1465,10 +1477,21 @@ public:
 	// ---- host arrays
 	void eval(size_t n, const int32_t *material, const vec3 *i, const vec3 *o, vec3 *out) const { eval_views((int64_t)n, material, hip::view(i), hip::view(o), hip::view(out), 0, DJB_MEM_HOST); }
 	void evalp(size_t n, const int32_t *material, const vec3 *i, const vec3 *o, vec3 *out) const { eval_views((int64_t)n, material, hip::view(i), hip::view(o), hip::view(out), 1, DJB_MEM_HOST); }
+	void evalp_is_proxy(const microfacet *proxy, size_t n, const int32_t *material, const float_t *u1, const float_t *u2, const vec3 *o,
+	                    vec3 *out_weight, vec3 *out_i, float_t *out_pdf) const
+	{ evalp_is_proxy_views(proxy, (int64_t)n, material, u1, u2, hip::view(o), hip::view(out_weight), hip::view(out_i), out_pdf, DJB_MEM_HOST); }
+	void evalp_pdf_proxy(const microfacet *proxy, size_t n, const int32_t *material, const vec3 *i, const vec3 *o, vec3 *out_fr, float_t *out_pdf) const
+	{ evalp_pdf_proxy_views(proxy, (int64_t)n, material, hip::view(i), hip::view(o), hip::view(out_fr), out_pdf, DJB_MEM_HOST); }
 	// ---- views (SoA or strided), in host memory or in HBM (mem = DJB_MEM_DEVICE: asynchronous on the context's stream, nothing read back)
 	void eval_views(int64_t n, const int32_t *material, const djb_vec3_view &i, const djb_vec3_view &o, const djb_vec3_view &out,
 	                int want_cos, int mem) const
 	{ hip::check(djb_scene_eval_batch(ctx(), m_h, n, material, &i, &o, want_cos, &out, mem)); }
+	void evalp_is_proxy_views(const microfacet *proxy, int64_t n, const int32_t *material, const float_t *u1, const float_t *u2,
+	                          const djb_vec3_view &o, const djb_vec3_view &out_weight, const djb_vec3_view &out_i, float_t *out_pdf, int mem) const
+	{ hip::check(djb_scene_evalp_is_proxy_batch(ctx(), m_h, proxy ? proxy->handle() : NULL, n, material, u1, u2, &o, &out_weight, &out_i, out_pdf, mem)); }
+	void evalp_pdf_proxy_views(const microfacet *proxy, int64_t n, const int32_t *material, const djb_vec3_view &i, const djb_vec3_view &o,
+	                           const djb_vec3_view &out_fr, float_t *out_pdf, int mem) const
+	{ hip::check(djb_scene_evalp_pdf_proxy_batch(ctx(), m_h, proxy ? proxy->handle() : NULL, n, material, &i, &o, &out_fr, out_pdf, mem)); }
 private:
 	djb_ctx *ctx() const { return (m_ctx ? *m_ctx : hip::context::standard()).get(); }
 	hip::context *m_ctx;

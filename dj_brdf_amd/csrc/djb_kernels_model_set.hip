@@ -17,7 +17,7 @@
 // rows spread over 32 bank pairs.  The byte offset material * STRIDE * 8 is below 2^25 at DJB_MODEL_SET_MAX = 65536: 32-bit offsets.
 // The Fresnel operands are converted per lane, (float)row[12 + c] / (float)row[15 + c] (sgd) and (float)row[8] (abc): create_model's conversions.
 //
-// Rows in LDS.  When M <= rows_lds(KIND) the workgroup copies the block into (dynamic) LDS once and the lanes read their coefficients from
+// Rows in LDS.  When M <= rows_lds(KIND, false) the workgroup copies the block into (dynamic) LDS once and the lanes read their coefficients from
 // there; the launch asks for M * STRIDE * 8 bytes, so a small set costs no occupancy.  The budget is what the kind's occupancy leaves of
 // the CU's 160 KiB next to the staged tables (5248 B sgd, 5128 B abc):
 //   sgd  its 124 / 127 VGPRs allow 4 waves per SIMD (k_eval<SGD> runs 5 at 87) = 4 workgroups per CU up to 73 rows of 488 B; the budget
@@ -41,76 +41,40 @@ namespace {
 constexpr int BLOCK = 256;
 constexpr long long GRID_CAP = 256LL * 16;                 // as k_eval for these kinds (djb_kernels_eval.hip)
 
-#include "djb_model_set_unit.inc"                                                                        // row_stride, unit
-constexpr int rows_lds(int kind) { return kind == KIND_SGD ? 101 : 213; }                                 // the LDS budget, in rows (above)
-// Registers (tools/kernel_resources.sh, profiles/model_set/kernel_resources.txt): the coefficients that k_eval holds in SGPRs are VGPR pairs
-// here.  sgd: 124 (dense) / 127 (strided) VGPRs against k_eval<SGD>'s 87 / 73 -- 4 waves per SIMD instead of 5 / 6, no scratch; abc: 64 (dense,
-// 8 waves, k_eval<ABC>: 57) / 70 (strided: 7 waves, k_eval<ABC>: 61 -- at the hint 8 the strided form kept 32 bytes of scratch).  The dense
-// accesses take their lane offset through lane_byte_offset(): with load3_dense_nt the sgd kernel kept 64-bit addresses across the body
-// (48 bytes of scratch at 128 VGPRs).
-constexpr int min_waves(int kind) { return kind == KIND_SGD ? 4 : 7; }
-static_assert(2048 + 3072 + 128 + 8 * rows_lds(KIND_SGD) * row_stride(KIND_SGD) <= 163840 / 3, "sgd: three workgroups per CU");
-static_assert(2048 + 3072 + 8 + 8 * rows_lds(KIND_ABC) * row_stride(KIND_ABC) <= 163840 / 8, "abc: eight workgroups per CU");
-static_assert(65536ull * 8ull * (unsigned long long)row_stride(KIND_SGD) < (1ull << 31), "the byte offset of the last row fits 32 bits");
+#include "djb_hit_source.inc"                              // BatchHits
+// rows_lds(kind, false): the LDS budget, in rows (above).  min_waves(kind, false), registers (tools/kernel_resources.sh,
+// profiles/model_set/kernel_resources.txt): the coefficients that k_eval holds in SGPRs are VGPR pairs here.  sgd: 124 (dense) / 127 (strided)
+// VGPRs against k_eval<SGD>'s 87 / 73 -- 4 waves per SIMD instead of 5 / 6, no scratch; abc: 64 (dense, 8 waves, k_eval<ABC>: 57) / 70
+// (strided: 7 waves, k_eval<ABC>: 61 -- at the hint 8 the strided form kept 32 bytes of scratch).  The dense accesses take their lane
+// offset through lane_byte_offset(): with load3_dense_nt the sgd kernel kept 64-bit addresses across the body (48 bytes of scratch at
+// 128 VGPRs).
+#include "djb_model_hits.inc"                              // row_stride, unit, rows_lds, min_waves, ModelLaunch, stage, model_eval_trip
 
 template <int KIND, int WANT, bool DENSE>
-__global__ __launch_bounds__(BLOCK, min_waves(KIND)) void k_model_set(Brdf b, const double *rows, int n_mat, int in_lds, long long n, const int32_t *mat,
-                                                                      View vi, View vo, View vout)
+__global__ __launch_bounds__(BLOCK, min_waves(KIND, false)) void k_model_set(Brdf b, const double *rows, int n_mat, int in_lds, long long n, const int32_t *mat,
+                                                                             View vi, View vo, View vout)
 {
-	constexpr unsigned int STRIDE = (unsigned int)row_stride(KIND);
 	__shared__ unsigned long long s_exp[256];
 	__shared__ double s_pow[384];
 	__shared__ double s_atan[KIND == KIND_SGD ? 16 : 1];
-	extern __shared__ double s_rows[];                                            // n_mat * STRIDE doubles when in_lds, else none (launch_set)
-	b.exp_lds = glibc_exp_tab_to_lds(s_exp, threadIdx.x, BLOCK);
-	b.pow_lds = glibc_pow_tab_to_lds(s_pow, threadIdx.x, BLOCK);
-	b.atan_lds = KIND == KIND_SGD ? atan_tab_to_lds(s_atan, threadIdx.x) : 0u;
-	if (in_lds) {                                                                 // n_mat <= rows_lds(KIND): the launcher's test
-		const unsigned int count = (unsigned int)n_mat * STRIDE;
-		for (unsigned int j = threadIdx.x; j < count; j += BLOCK) s_rows[j] = rows[j];
-	}
-	__syncthreads();
-	const long long stride = (long long)gridDim.x * BLOCK;
-	const unsigned int t = threadIdx.x;
-	for (long long k0 = (long long)blockIdx.x * BLOCK; k0 < n; k0 += stride) {     // k0: workgroup-uniform
-		const long long k = k0 + t;
-		const bool live = k < n;
-		bool act = false;
-		unsigned int id = 0u;
-		v3 i = mk(0, 0, 1), o = mk(0, 0, 1);
-		if (live) {                                                                // 40 B per hit, touched once: non-temporal
-			const unsigned int raw = (unsigned int)__builtin_nontemporal_load(mat + k);
-			const unsigned int toff = lane_byte_offset(t);                          // SGPR base + the lane's 32-bit offset (note below)
-			i = DENSE ? load3_dense_off_nt(vi, k0, toff) : load3(vi, k); o = DENSE ? load3_dense_off_nt(vo, k0, toff) : load3(vo, k);
-			act = raw < (unsigned int)n_mat;                                        // negative ids are >= 2^31 as unsigned
-			id = act ? raw : 0u;
-		}
-		v3 fr = mk(0, 0, 0);                                                       // an inactive hit: +0
-		if (__ballot(act) != 0ull) {                                               // wave-uniform: a wave of dead hits computes nothing
-			if (act) {
-				if (in_lds) unit<KIND, WANT>(b, s_rows + id * STRIDE, i, o, fr);                            // workgroup-uniform: ds_read_b64 ...
-				else unit<KIND, WANT>(b, (const double *)((const char *)rows + (size_t)(id * (STRIDE * 8u))), i, o, fr);   // ... or uniform base + 32-bit byte offset
-			}
-		}
-		if (live) { if (DENSE) store3_dense_off_nt(vout, k0, lane_byte_offset(t), fr); else store3(vout, k, fr); }
-	}
+	extern __shared__ double s_rows[];                                            // n_mat * STRIDE doubles when in_lds, else none (ModelLaunch)
+	const BatchHits<DENSE, true, true> src(n, mat, n_mat);
+	b = stage<KIND, KIND == KIND_SGD>(b, s_exp, s_pow, s_atan, s_rows, rows, src.n_mat, in_lds);
+	const long long stride = src.stride();
+	for (long long j0 = src.start(); j0 < src.count(); j0 += stride)                      // j0: workgroup-uniform
+		model_eval_trip<KIND, WANT>(src, j0, s_rows, b, rows, in_lds, vi, vo, vout);
 }
 
 template <int KIND, int WANT>
 hipError_t launch_set(hipStream_t s, const double *rows, int n_mat, bool rows_global, long long n, const int32_t *mat, const View &i, const View &o,
                       const View &out)
 {
-	Brdf b;
-	memset(&b, 0, sizeof b);
-	b.kind = KIND;
-	b.fr.kind = KIND == KIND_SGD ? FR_SGD : FR_UNPOLARIZED;
-	const int in_lds = !rows_global && n_mat <= rows_lds(KIND);
-	const size_t lds = in_lds ? sizeof(double) * (size_t)n_mat * (size_t)row_stride(KIND) : 0;      // dynamic: a small set costs no occupancy
+	const ModelLaunch L(KIND, n_mat, rows_global, false);
 	dim3 g(djbk::grid_capped(n, BLOCK, GRID_CAP)), t(BLOCK);
 	if (djbk::dense_strict(i) && djbk::dense_strict(o) && djbk::dense_strict(out))
-		hipLaunchKernelGGL((k_model_set<KIND, WANT, true>), g, t, lds, s, b, rows, n_mat, in_lds, n, mat, i, o, out);
+		hipLaunchKernelGGL((k_model_set<KIND, WANT, true>), g, t, L.lds, s, L.b, rows, n_mat, L.in_lds, n, mat, i, o, out);
 	else
-		hipLaunchKernelGGL((k_model_set<KIND, WANT, false>), g, t, lds, s, b, rows, n_mat, in_lds, n, mat, i, o, out);
+		hipLaunchKernelGGL((k_model_set<KIND, WANT, false>), g, t, L.lds, s, L.b, rows, n_mat, L.in_lds, n, mat, i, o, out);
 	return hipGetLastError();
 }
 

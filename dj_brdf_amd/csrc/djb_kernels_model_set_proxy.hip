@@ -55,106 +55,36 @@ constexpr int BLOCK = 256;
 constexpr long long GRID_CAP = 256LL * 16;                 // as k_model_set: one trip of the grid is GRID_CAP * BLOCK = 1 048 576 hits
 static_assert(GRID_CAP * BLOCK == djbk::MODEL_SET_PROXY_TRIP, "the trip size the tests restate");
 
-#include "djb_model_set_unit.inc"                          // row_stride, unit
-
-// Registers (tools/kernel_resources.sh, profiles/model_set_proxy/kernel_resources.txt): the sampled direction, o and the pdf live across
-// eval_one next to the per-lane row.  sgd: 141 (dense) / 143 (strided) VGPRs, 3 waves per SIMD (k_model_set<SGD>: 124 / 127 at 4); at the hint
-// 4 all four sgd kernels kept 48 / 64 bytes of scratch at 128 VGPRs.  abc: 77 (dense: 6 waves) / 83 (strided: 5 waves) against k_model_set<ABC>'s
-// 64 / 70 at 8 / 7; at the hint 6 the strided forms kept 16 bytes of scratch, at 7 all four kept 32 / 48.  The hints are the largest
-// without scratch; nothing was timed against them.
-constexpr int min_waves(int kind) { return kind == KIND_SGD ? 3 : 5; }
-// the LDS budget for rows, next to 5248 B of staged tables (exp 2048, pow 3072, arctangent 128): sgd 101 rows at 3 workgroups per CU, as
-// k_model_set (the 100 published rows fit); abc 211 rows at 8 workgroups per CU (k_model_set: 213 -- the arctangent table is staged here)
-constexpr int rows_lds(int kind) { return kind == KIND_SGD ? 101 : 211; }
-static_assert(2048 + 3072 + 128 + 8 * rows_lds(KIND_SGD) * row_stride(KIND_SGD) <= 163840 / 3, "sgd: three workgroups per CU");
-static_assert(2048 + 3072 + 128 + 8 * rows_lds(KIND_ABC) * row_stride(KIND_ABC) <= 163840 / 8, "abc: eight workgroups per CU");
-static_assert(12ull * (unsigned long long)djbk::MODEL_SET_PROXY_MAX_ENTRIES + 4ull * 65536ull < (1ull << 31), "the byte offset of the last table entry and of n_qf[M - 1] fits 31 bits");
-
-using djbk::ModelSetProxy;                                 // the launch-uniform part of a set's proxy block: base, res, shadow
-
-// the lane's proxy: b's staged tables, the tables and the count of material `id`
-DJB_DEV Brdf proxy_of(Brdf b, const ModelSetProxy &px, unsigned int n_mat, unsigned int id)
-{
-	const unsigned int res4 = (unsigned int)px.res * 4u;
-	const char *base = (const char *)px.tab;
-	const unsigned int off = id * (3u * res4);                                     // < 2^31 (above)
-	b.shadow = px.shadow;
-	b.p22 = (const float *)(base + off);
-	b.sigma = (const float *)(base + (off + res4));
-	b.qf = (const float *)(base + (off + 2u * res4));
-	b.n_p22 = b.n_sigma = px.res;
-	b.n_qf = *(const int *)(base + (n_mat * (3u * res4) + (id << 2)));
-	return b;
-}
-
-// the staged tables of both sides: exp and pow for the model, the arctangent core's for the model (sgd) and the proxy's table coordinates
-DJB_DEV Brdf stage(Brdf b, unsigned long long (&s_exp)[256], double (&s_pow)[384], double (&s_atan)[16])
-{
-	b.exp_lds = glibc_exp_tab_to_lds(s_exp, threadIdx.x, BLOCK);
-	b.pow_lds = glibc_pow_tab_to_lds(s_pow, threadIdx.x, BLOCK);
-	b.atan_lds = atan_tab_to_lds(s_atan, threadIdx.x);
-	return b;
-}
+#include "djb_hit_source.inc"                              // BatchHits
+// min_waves(kind, true), registers (tools/kernel_resources.sh, profiles/model_set_proxy/kernel_resources.txt): the sampled direction, o and
+// the pdf live across eval_one next to the per-lane row.  sgd: 141 (dense) / 143 (strided) VGPRs, 3 waves per SIMD (k_model_set<SGD>: 124 / 127
+// at 4); at the hint 4 all four sgd kernels kept 48 / 64 bytes of scratch at 128 VGPRs.  abc: 77 (dense: 6 waves) / 83 (strided: 5 waves)
+// against k_model_set<ABC>'s 64 / 70 at 8 / 7; at the hint 6 the strided forms kept 16 bytes of scratch, at 7 all four kept 32 / 48.  The hints
+// are the largest without scratch; nothing was timed against them.
+// rows_lds(kind, true), the LDS budget for rows next to 5248 B of staged tables (exp 2048, pow 3072, arctangent 128): sgd 101 rows at 3
+// workgroups per CU, as k_model_set (the 100 published rows fit); abc 211 rows at 8 workgroups per CU (k_model_set: 213 -- the arctangent
+// table is staged here)
+#include "djb_model_hits.inc"                              // row_stride, unit, rows_lds, min_waves, ModelLaunch, stage, proxy_of, model_is_trip
 
 template <int KIND, bool DENSE>
-__global__ __launch_bounds__(BLOCK, min_waves(KIND)) void k_model_set_evalp_is_proxy(Brdf b, Params pp, ModelSetProxy px, const double *rows, int n_mat, int in_lds,
-                                                                                     long long n, const int32_t *mat, const float *u1a, const float *u2a,
-                                                                                     View vo, View vw_out, View vi_out, float *out_pdf)
+__global__ __launch_bounds__(BLOCK, min_waves(KIND, true)) void k_model_set_evalp_is_proxy(Brdf b, Params pp, ModelSetProxy px, const double *rows, int n_mat, int in_lds,
+                                                                                           long long n, const int32_t *mat, const float *u1a, const float *u2a,
+                                                                                           View vo, View vw_out, View vi_out, float *out_pdf)
 {
-	constexpr unsigned int STRIDE = (unsigned int)row_stride(KIND);
 	__shared__ unsigned long long s_exp[256];
 	__shared__ double s_pow[384];
 	__shared__ double s_atan[16];
 	extern __shared__ double s_rows[];                                            // n_mat * STRIDE doubles when in_lds, else none
-	b = stage(b, s_exp, s_pow, s_atan);
-	if (in_lds) {                                                                 // n_mat <= rows_lds(KIND): the launcher's test
-		const unsigned int count = (unsigned int)n_mat * STRIDE;
-		for (unsigned int j = threadIdx.x; j < count; j += BLOCK) s_rows[j] = rows[j];
-	}
-	__syncthreads();
-	const GlibcTabs gt = glibc_tabs_global();                                     // Beckmann's: mf_sample<KIND_TABULAR> does not read it
-	const long long stride = (long long)gridDim.x * BLOCK;
-	const unsigned int t = threadIdx.x;
-	for (long long k0 = (long long)blockIdx.x * BLOCK; k0 < n; k0 += stride) {     // k0: workgroup-uniform
-		const long long k = k0 + t;
-		const bool live = k < n;
-		bool act = false;
-		unsigned int id = 0u;
-		float u1 = 0.0f, u2 = 0.0f;
-		v3 o = mk(0, 0, 1);
-		if (live) {                                                                // 52 B per hit, touched once: non-temporal
-			const unsigned int raw = (unsigned int)__builtin_nontemporal_load(mat + k);
-			const unsigned int toff = lane_byte_offset(t);
-			u1 = DENSE ? __builtin_nontemporal_load(dense_off(u1a + k0, toff)) : __builtin_nontemporal_load(u1a + k);
-			u2 = DENSE ? __builtin_nontemporal_load(dense_off(u2a + k0, toff)) : __builtin_nontemporal_load(u2a + k);
-			o = DENSE ? load3_dense_off_nt(vo, k0, toff) : load3(vo, k);
-			act = raw < (unsigned int)n_mat;                                        // negative ids are >= 2^31 as unsigned
-			id = act ? raw : 0u;
-		}
-		v3 w = mk(0, 0, 0), i_ = mk(0, 0, 0); float pdf = 0.0f;                    // an inactive hit: +0 everywhere
-		if (__ballot(act) != 0ull) {                                               // wave-uniform: a wave of dead hits computes nothing
-			if (act) {
-				const Brdf pb = proxy_of(b, px, (unsigned int)n_mat, id);
-				i_ = mf_sample<KIND_TABULAR>(pb, pp, u1, u2, o, gt);
-				if (!(i_.z <= 0.0f)) {                                              // the plugins' side check; a NaN i.z is evaluated
-					v3 unused, fr = mk(0, 0, 0);
-					mf_eval_pdf<KIND_TABULAR, 4>(pb, pp, i_, o, unused, pdf);
-					if (in_lds) unit<KIND, 2>(b, s_rows + id * STRIDE, i_, o, fr);                             // workgroup-uniform: ds_read_b64 ...
-					else unit<KIND, 2>(b, (const double *)((const char *)rows + (size_t)(id * (STRIDE * 8u))), i_, o, fr);   // ... or uniform base + 32-bit byte offset
-					w = divs(fr, pdf);                                              // (1.0f / pdf) * fr: the IEEE result for a zero pdf
-				}
-			}
-		}
-		if (live) {
-			const unsigned int soff = lane_byte_offset(t);                          // again: the stores sit in another block than the loads
-			if (DENSE) { store3_dense_off_nt(vi_out, k0, soff, i_); __builtin_nontemporal_store(pdf, dense_off(out_pdf + k0, soff)); store3_dense_off_nt(vw_out, k0, soff, w); }
-			else { store3(vi_out, k, i_); __builtin_nontemporal_store(pdf, out_pdf + k); store3(vw_out, k, w); }
-		}
-	}
+	const BatchHits<DENSE, true, true> src(n, mat, n_mat);
+	b = stage<KIND, true>(b, s_exp, s_pow, s_atan, s_rows, rows, src.n_mat, in_lds);
+	const long long stride = src.stride();
+	for (long long j0 = src.start(); j0 < src.count(); j0 += stride)                      // j0: workgroup-uniform
+		model_is_trip<KIND>(src, j0, s_rows, b, pp, px, rows, in_lds, u1a, u2a, vo, vw_out, vi_out, out_pdf);
 }
 
+// the light sample: written out, as k_scene_model_light is -- on one body the pair did not keep its instructions
 template <int KIND, bool DENSE>
-__global__ __launch_bounds__(BLOCK, min_waves(KIND)) void k_model_set_evalp_pdf(Brdf b, Params pp, ModelSetProxy px, const double *rows, int n_mat, int in_lds,
+__global__ __launch_bounds__(BLOCK, min_waves(KIND, true)) void k_model_set_evalp_pdf(Brdf b, Params pp, ModelSetProxy px, const double *rows, int n_mat, int in_lds,
                                                                                 long long n, const int32_t *mat, View vi, View vo, View vout, float *out_pdf)
 {
 	constexpr unsigned int STRIDE = (unsigned int)row_stride(KIND);
@@ -162,12 +92,7 @@ __global__ __launch_bounds__(BLOCK, min_waves(KIND)) void k_model_set_evalp_pdf(
 	__shared__ double s_pow[384];
 	__shared__ double s_atan[16];
 	extern __shared__ double s_rows[];
-	b = stage(b, s_exp, s_pow, s_atan);
-	if (in_lds) {
-		const unsigned int count = (unsigned int)n_mat * STRIDE;
-		for (unsigned int j = threadIdx.x; j < count; j += BLOCK) s_rows[j] = rows[j];
-	}
-	__syncthreads();
+	b = stage<KIND, true>(b, s_exp, s_pow, s_atan, s_rows, rows, (unsigned int)n_mat, in_lds);
 	const long long stride = (long long)gridDim.x * BLOCK;
 	const unsigned int t = threadIdx.x;
 	for (long long k0 = (long long)blockIdx.x * BLOCK; k0 < n; k0 += stride) {     // k0: workgroup-uniform
@@ -202,28 +127,16 @@ __global__ __launch_bounds__(BLOCK, min_waves(KIND)) void k_model_set_evalp_pdf(
 	}
 }
 
-struct Launch {
-	Brdf b; int in_lds; size_t lds; dim3 g;
-	Launch(int kind, int n_mat, bool rows_global, long long n)
-	{
-		memset(&b, 0, sizeof b);
-		b.kind = kind;
-		b.fr.kind = kind == KIND_SGD ? FR_SGD : FR_UNPOLARIZED;
-		in_lds = !rows_global && n_mat <= rows_lds(kind);
-		lds = in_lds ? sizeof(double) * (size_t)n_mat * (size_t)row_stride(kind) : 0;                // dynamic: a small set costs no occupancy
-		g = dim3(djbk::grid_capped(n, BLOCK, GRID_CAP));
-	}
-};
-
 template <int KIND>
 hipError_t launch_is(hipStream_t s, const ModelSetProxy &p, const Params &pp, const double *rows, int n_mat, bool rows_global, long long n,
                      const int32_t *mat, const float *u1, const float *u2, const View &o, const View &out_w, const View &out_i, float *out_pdf)
 {
-	const Launch L(KIND, n_mat, rows_global, n);
+	const ModelLaunch L(KIND, n_mat, rows_global, true);
+	const dim3 g(djbk::grid_capped(n, BLOCK, GRID_CAP));
 	if (djbk::dense_strict(o) && djbk::dense_strict(out_w) && djbk::dense_strict(out_i))
-		hipLaunchKernelGGL((k_model_set_evalp_is_proxy<KIND, true>), L.g, dim3(BLOCK), L.lds, s, L.b, pp, p, rows, n_mat, L.in_lds, n, mat, u1, u2, o, out_w, out_i, out_pdf);
+		hipLaunchKernelGGL((k_model_set_evalp_is_proxy<KIND, true>), g, dim3(BLOCK), L.lds, s, L.b, pp, p, rows, n_mat, L.in_lds, n, mat, u1, u2, o, out_w, out_i, out_pdf);
 	else
-		hipLaunchKernelGGL((k_model_set_evalp_is_proxy<KIND, false>), L.g, dim3(BLOCK), L.lds, s, L.b, pp, p, rows, n_mat, L.in_lds, n, mat, u1, u2, o, out_w, out_i, out_pdf);
+		hipLaunchKernelGGL((k_model_set_evalp_is_proxy<KIND, false>), g, dim3(BLOCK), L.lds, s, L.b, pp, p, rows, n_mat, L.in_lds, n, mat, u1, u2, o, out_w, out_i, out_pdf);
 	return hipGetLastError();
 }
 
@@ -231,11 +144,12 @@ template <int KIND>
 hipError_t launch_pdf(hipStream_t s, const ModelSetProxy &p, const Params &pp, const double *rows, int n_mat, bool rows_global, long long n,
                       const int32_t *mat, const View &i, const View &o, const View &out, float *out_pdf)
 {
-	const Launch L(KIND, n_mat, rows_global, n);
+	const ModelLaunch L(KIND, n_mat, rows_global, true);
+	const dim3 g(djbk::grid_capped(n, BLOCK, GRID_CAP));
 	if (djbk::dense_strict(i) && djbk::dense_strict(o) && djbk::dense_strict(out))
-		hipLaunchKernelGGL((k_model_set_evalp_pdf<KIND, true>), L.g, dim3(BLOCK), L.lds, s, L.b, pp, p, rows, n_mat, L.in_lds, n, mat, i, o, out, out_pdf);
+		hipLaunchKernelGGL((k_model_set_evalp_pdf<KIND, true>), g, dim3(BLOCK), L.lds, s, L.b, pp, p, rows, n_mat, L.in_lds, n, mat, i, o, out, out_pdf);
 	else
-		hipLaunchKernelGGL((k_model_set_evalp_pdf<KIND, false>), L.g, dim3(BLOCK), L.lds, s, L.b, pp, p, rows, n_mat, L.in_lds, n, mat, i, o, out, out_pdf);
+		hipLaunchKernelGGL((k_model_set_evalp_pdf<KIND, false>), g, dim3(BLOCK), L.lds, s, L.b, pp, p, rows, n_mat, L.in_lds, n, mat, i, o, out, out_pdf);
 	return hipGetLastError();
 }
 

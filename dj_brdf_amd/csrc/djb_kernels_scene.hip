@@ -13,11 +13,13 @@
 // then, per member set the scene has, the member set's kernel with an indirection -- the loop runs over list positions j below count[kind]
 // (read from device memory: a scalar load, workgroup-uniform), k = list[offset + j], directions and result at k, the local id from the
 // slot of material[k]:
-//   k_scene_merl<WANT>          k_merl_set_fast's body (djb_kernels_merl_set.hip): tier 1 in place, the 9-word record queue, the extra trip
+//   k_scene_merl<WANT>          k_merl_set_fast's body (merl_eval_hits, djb_merl_hits.inc): tier 1 in place, the 9-word record queue, the extra trip
 //   k_scene_utia<WANT>          k_utia_set's body (djb_kernels_utia_set.hip): the per-wave LDS tile, six shuffles, six predicated LDS-direct
 //                               loads; undecided hits append k to the worklist
 //   k_scene_utia_fix<WANT>      k_utia_set_fix: the listed hits; the utia SEGMENT if the list overflowed; alone over the segment
-//   k_scene_model<KIND, WANT>   k_model_set's body (djb_kernels_model_set.hip): unit<KIND, WANT>, rows in dynamic LDS or global memory
+//   k_scene_model<KIND, WANT>   k_model_set's body (model_eval_trip, djb_model_hits.inc): unit<KIND, WANT>, rows in dynamic LDS or global memory
+// The MERL and sgd / abc bodies exist once, over a hit source (djb_hit_source.inc; here ListHits, djb_scene_part.inc); the utia kernels are
+// written out.
 // The per-unit functions are the ones those kernels call, so an active hit has the bits of its member set's call, which are the bits of
 // the single-material call.  The grid of a per-kind kernel is sized for the chunk, an upper bound: a workgroup beyond the count leaves at
 // once.  Nothing is read back to the host.  Every lane reads its hit before it writes it and kinds touch disjoint hits: index-aligned
@@ -31,18 +33,14 @@ using namespace djbdev;
 
 namespace {
 
-#include "djb_scene_part.inc"                                                                         // BLOCK, TILE, K_*, Hits, slot_of, kind_of, local_of, wave_tile, the MERL record
+#include "djb_scene_part.inc"                                                                         // BLOCK, TILE, K_*, Hits, slot_of, kind_of, local_of, ListHits, wave_tile, scatter_hits
 constexpr long long GRID_CAP_MERL = 256LL * 16;             // as k_merl_set_fast
 constexpr long long GRID_CAP_UTIA = 256LL * 64;             // as k_utia_set
 constexpr long long GRID_CAP_MODEL = 256LL * 16;            // as k_model_set
-constexpr unsigned int NO_RECORD = 0xffffffffu;
-#ifndef DJB_UTIA_MIN_WAVES
-#define DJB_UTIA_MIN_WAVES 4
-#endif
 
-#include "djb_model_set_unit.inc"                                                                        // row_stride, unit
-constexpr int rows_lds(int kind) { return kind == KIND_SGD ? 101 : 213; }                                 // as k_model_set
-constexpr int min_waves(int kind) { return kind == KIND_SGD ? 4 : 7; }
+#include "djb_merl_hits.inc"                                // merl_set_texel, the queue record, merl_eval_hits
+#include "djb_utia_hits.inc"                                // DJB_UTIA_MIN_WAVES, TABLE_F4, NO_RECORD, utia_target
+#include "djb_model_hits.inc"                               // row_stride, unit, rows_lds, min_waves, ModelLaunch, model_eval_trip
 
 // ---- the partition
 __global__ __launch_bounds__(BLOCK) void k_scene_count(const unsigned int *slots, unsigned int n_slots, unsigned int m, const int32_t *mat,
@@ -103,72 +101,19 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_scene_scan(unsigned int n_tiles,
 __global__ __launch_bounds__(BLOCK) void k_scene_scatter(const unsigned int *slots, unsigned int n_slots, unsigned int m, const int32_t *mat,
                                                          unsigned int n_tiles, const unsigned int *tiles, unsigned int *list, View vout)
 {
-	const unsigned int lane = threadIdx.x & 63u, tile = wave_tile();
-	if (tile >= n_tiles) return;
-	unsigned int off[4];                                                           // wave-uniform: where the tile's next hit of each kind goes
-#pragma unroll
-	for (unsigned int u = 0; u < 4u; ++u) off[u] = tiles[tile * 4u + u];
-	const unsigned long long below = (1ull << lane) - 1ull;
-	for (unsigned int s = 0; s < STEPS; ++s) {
-		const unsigned int k = tile * TILE + s * 64u + lane;
-		const bool live = k < m;
-		unsigned int q = K_DEAD;
-		if (live) q = kind_of(slot_of(slots, n_slots, (unsigned int)mat[k]));
-#pragma unroll
-		for (unsigned int u = 0; u < 4u; ++u) {
-			const unsigned long long mask = __ballot(q == u);
-			if (q == u) list[off[u] + (unsigned int)__popcll(mask & below)] = k;    // below count[u] + offset[u] <= m: the scan counted these hits
-			off[u] += (unsigned int)__popcll(mask);
-		}
-		if (live && q == K_DEAD) store3(vout, (long long)k, mk(0, 0, 0));          // an inactive hit: +0, nothing read
-	}
+	scatter_hits(slots, n_slots, m, mat, n_tiles, tiles, list, [&](unsigned int k) { store3(vout, (long long)k, mk(0, 0, 0)); });
 }
 
-// ---- merl: k_merl_set_fast over the list
+// ---- merl: merl_eval_hits over the list
 template <int WANT>
 __global__ __launch_bounds__(BLOCK) void k_scene_merl(Hits h, const MerlTexel *tex, unsigned int n_mat, View vi, View vo, View vout, MerlGuard g,
                                                       int merl_exact)
 {
 	__shared__ unsigned int s_q[BLOCK / 64][9][RECQ_CAP];
-	const unsigned int cnt = h.hdr[K_MERL], first = h.hdr[4 + K_MERL];             // uniform addresses: scalar loads
-	if (blockIdx.x * (unsigned int)BLOCK >= cnt) return;                           // the grid is sized for the chunk
-	const unsigned int t = threadIdx.x, wave = t >> 6, lane = t & 63u;
-	unsigned int (&q)[9][RECQ_CAP] = s_q[wave];
-	unsigned int qn = 0;                                                           // wave-uniform
-	const unsigned int stride = gridDim.x * (unsigned int)BLOCK;                   // cnt <= 2^26, stride <= 2^20: j0 does not wrap
-	for (unsigned int j0 = blockIdx.x * (unsigned int)BLOCK; ; j0 += stride) {     // workgroup-uniform trip count; one extra trip flushes the queues
-		const bool last = j0 >= cnt;
-		bool amb = false;
-		unsigned int id = 0u, k = 0u;
-		v3 i = mk(0, 0, 1), o = mk(0, 0, 1);
-		const unsigned int rem = last ? 0u : cnt - j0 >= (unsigned int)BLOCK ? (unsigned int)BLOCK : cnt - j0;
-		if (t < rem) {
-			k = h.list[first + j0 + t];
-			const bool act = local_of(h, k, K_MERL, n_mat, id);
-			i = load3(vi, (long long)k); o = load3(vo, (long long)k);
-			v3 fr = mk(0, 0, 0);
-			if (act) {
-				int idx = 0;
-				if (!merl_exact && merl_index_fast(i, o, g, idx)) {
-					const v3 e = merl_set_texel(tex, id, idx);
-					fr = (WANT & 2) ? scale(i.z, e) : e;                                   // brdf::evalp, dj_brdf.h:803-806
-				} else amb = true;                                                      // the exact index finishes this pair
-			}
-			if (!amb) store3(vout, (long long)k, fr);
-		}
-		unsigned int rec[9];                                                       // built here, outside the branches above (djb_worklist.hpp)
-		rec_pack(rec, (long long)k, id, i, o);
-		recq_push(q, qn, lane, amb, rec);
-		recq_drain(q, qn, lane, last, [&](const unsigned int *r) {
-			const v3 iq = rec_v3(r, 3);
-			const v3 e = merl_set_texel(tex, r[2], merl_index(iq, rec_v3(r, 6)));
-			store3(vout, rec_k(r), (WANT & 2) ? scale(iq.z, e) : e);
-		});
-		if (last) break;
-	}
+	merl_eval_hits<WANT>(ListHits(h, K_MERL, n_mat), s_q, tex, vi, vo, vout, g, merl_exact);
 }
 
-// ---- utia: k_utia_set over the list
+// ---- utia: k_utia_set over the list, written out (djb_utia_hits.inc)
 template <int WANT>
 __global__ __launch_bounds__(BLOCK, DJB_UTIA_MIN_WAVES) void k_scene_utia(Hits h, const float4 *tab, unsigned int n_mat, View vi, View vo, View vout,
                                                                          unsigned int *wl, unsigned int cap, unsigned int *wl_count)
@@ -273,63 +218,30 @@ __global__ __launch_bounds__(BLOCK) void k_scene_utia_fix(Hits h, Brdf b, const 
 	}
 }
 
-// ---- sgd / abc: k_model_set over the list
+// ---- sgd / abc: model_eval_trip over the list
 template <int KIND, int WANT>
-__global__ __launch_bounds__(BLOCK, min_waves(KIND)) void k_scene_model(Hits h, Brdf b, const double *rows, unsigned int n_mat, int in_lds, View vi,
-                                                                        View vo, View vout)
+__global__ __launch_bounds__(BLOCK, min_waves(KIND, false)) void k_scene_model(Hits h, Brdf b, const double *rows, unsigned int n_mat, int in_lds, View vi,
+                                                                               View vo, View vout)
 {
-	constexpr unsigned int STRIDE = (unsigned int)row_stride(KIND);
-	constexpr unsigned int Q = KIND == KIND_SGD ? K_SGD : K_ABC;
 	__shared__ unsigned long long s_exp[256];
 	__shared__ double s_pow[384];
 	__shared__ double s_atan[KIND == KIND_SGD ? 16 : 1];
 	extern __shared__ double s_rows[];                                            // n_mat * STRIDE doubles when in_lds, else none
-	const unsigned int cnt = h.hdr[Q], first = h.hdr[4 + Q];
-	if (blockIdx.x * (unsigned int)BLOCK >= cnt) return;                           // workgroup-uniform, before the staging and its barrier
-	b.exp_lds = glibc_exp_tab_to_lds(s_exp, threadIdx.x, BLOCK);
-	b.pow_lds = glibc_pow_tab_to_lds(s_pow, threadIdx.x, BLOCK);
-	b.atan_lds = KIND == KIND_SGD ? atan_tab_to_lds(s_atan, threadIdx.x) : 0u;
-	if (in_lds) {                                                                 // n_mat <= rows_lds(KIND): the launcher's test
-		const unsigned int count = n_mat * STRIDE;
-		for (unsigned int j = threadIdx.x; j < count; j += BLOCK) s_rows[j] = rows[j];
-	}
-	__syncthreads();
-	const unsigned int stride = gridDim.x * (unsigned int)BLOCK;
-	const unsigned int t = threadIdx.x;
-	for (unsigned int j0 = blockIdx.x * (unsigned int)BLOCK; j0 < cnt; j0 += stride) {     // j0: workgroup-uniform
-		const unsigned int j = j0 + t;
-		const bool live = j < cnt;
-		bool act = false;
-		unsigned int id = 0u, k = 0u;
-		v3 i = mk(0, 0, 1), o = mk(0, 0, 1);
-		if (live) {
-			k = h.list[first + j];
-			act = local_of(h, k, Q, n_mat, id);
-			i = load3(vi, (long long)k); o = load3(vo, (long long)k);
-		}
-		v3 fr = mk(0, 0, 0);
-		if (__ballot(act) != 0ull) {                                               // wave-uniform
-			if (act) {
-				if (in_lds) unit<KIND, WANT>(b, s_rows + id * STRIDE, i, o, fr);                            // workgroup-uniform: ds_read_b64 ...
-				else unit<KIND, WANT>(b, (const double *)((const char *)rows + (size_t)(id * (STRIDE * 8u))), i, o, fr);   // ... or uniform base + 32-bit byte offset
-			}
-		}
-		if (live) store3(vout, (long long)k, fr);
-	}
+	const ListHits src(h, KIND == KIND_SGD ? K_SGD : K_ABC, n_mat);
+	if (src.none()) return;                                                        // workgroup-uniform, before the staging and its barrier
+	b = stage<KIND, KIND == KIND_SGD>(b, s_exp, s_pow, s_atan, s_rows, rows, src.n_mat, in_lds);
+	const unsigned int stride = src.stride();
+	for (unsigned int j0 = src.start(); j0 < src.count(); j0 += stride)                      // j0: workgroup-uniform
+		model_eval_trip<KIND, WANT>(src, j0, s_rows, b, rows, in_lds, vi, vo, vout);
 }
 
 template <int KIND, int WANT>
 hipError_t launch_model(hipStream_t s, const Hits &h, const double *rows, int n_mat, bool rows_global, long long m, const View &i, const View &o,
                         const View &out)
 {
-	Brdf b;
-	memset(&b, 0, sizeof b);
-	b.kind = KIND;
-	b.fr.kind = KIND == KIND_SGD ? FR_SGD : FR_UNPOLARIZED;
-	const int in_lds = !rows_global && n_mat <= rows_lds(KIND);
-	const size_t lds = in_lds ? sizeof(double) * (size_t)n_mat * (size_t)row_stride(KIND) : 0;
-	hipLaunchKernelGGL((k_scene_model<KIND, WANT>), dim3(djbk::grid_capped(m, BLOCK, GRID_CAP_MODEL)), dim3(BLOCK), lds, s, h, b, rows,
-	                   (unsigned int)n_mat, in_lds, i, o, out);
+	const ModelLaunch L(KIND, n_mat, rows_global, false);
+	hipLaunchKernelGGL((k_scene_model<KIND, WANT>), dim3(djbk::grid_capped(m, BLOCK, GRID_CAP_MODEL)), dim3(BLOCK), L.lds, s, h, L.b, rows,
+	                   (unsigned int)n_mat, L.in_lds, i, o, out);
 	return hipGetLastError();
 }
 
@@ -350,9 +262,7 @@ hipError_t launch_all(hipStream_t s, const djbk::SceneMembers &mb, const unsigne
 		if ((e = hipGetLastError()) != hipSuccess) return e;
 	}
 	if (mb.utia) {
-		Brdf b;
-		memset(&b, 0, sizeof b);
-		b.kind = KIND_UTIA;
+		const Brdf b = utia_target();
 		const dim3 g(djbk::grid_capped(m, BLOCK, GRID_CAP_UTIA));
 		if (utia_exact)
 			hipLaunchKernelGGL((k_scene_utia_fix<WANT>), g, t, 0, s, h, b, mb.utia, (unsigned int)mb.n_utia, i, o, out, nullptr, 0u, nullptr, 1);

@@ -18,7 +18,9 @@
 // PKIND: ggx or beckmann, the lobe of the merl and utia parts.  The loop of every per-kind kernel runs over list positions j below
 // count[kind] (a scalar load, workgroup-uniform), k = list[offset + j]; every gather and scatter goes through k.  The grid is sized for the
 // chunk, an upper bound, with the member kernel's cap: a workgroup beyond the count leaves before it stages anything.  The per-unit
-// functions are the ones the member kernels call, so an active hit has the bits of its member's call.
+// functions are the ones the member kernels call, so an active hit has the bits of its member's call.  The MERL bodies and the sgd / abc
+// sampling body exist once, over a hit source (djb_merl_hits.inc, djb_model_hits.inc; here ListHits, djb_scene_part.inc); the sgd / abc
+// light sample and the utia kernels are written out.
 //
 // UTIA, the indices of the exact path for ANY sampled direction (utia_prepare<false>, djb_device_tables.inc; the sampler may return NaN
 // components): a NaN azimuth makes the pair `dead` and replaces all four angles by 1; a polar angle that is NaN compares false with
@@ -41,18 +43,13 @@ using namespace djbdev;
 
 namespace {
 
-#include "djb_scene_part.inc"                              // BLOCK, TILE, K_*, Hits, slot_of, kind_of, local_of, wave_tile, the MERL record
+#include "djb_scene_part.inc"                              // BLOCK, TILE, K_*, Hits, slot_of, kind_of, local_of, ListHits, wave_tile, scatter_hits
 constexpr long long GRID_CAP = 256LL * 16;                 // as every member kernel: k_evalp_is_proxy_merl_set, k_evalp_is_proxy (256-thread workgroups), k_model_set_evalp_is_proxy
 static_assert(GRID_CAP * BLOCK == djbk::SCENE_PROXY_TRIP, "the trip size the tests restate");
 
-#include "djb_model_set_unit.inc"                          // row_stride, unit
-// as djb_kernels_model_set_proxy.hip: the largest hints without scratch there, and the LDS budget for rows next to the staged tables
-constexpr int min_waves(int kind) { return kind == KIND_SGD ? 3 : 5; }
-constexpr int rows_lds(int kind) { return kind == KIND_SGD ? 101 : 211; }
-static_assert(2048 + 3072 + 128 + 8 * rows_lds(KIND_SGD) * row_stride(KIND_SGD) <= 163840 / 3, "sgd: three workgroups per CU");
-static_assert(2048 + 3072 + 128 + 8 * rows_lds(KIND_ABC) * row_stride(KIND_ABC) <= 163840 / 8, "abc: eight workgroups per CU");
-
-using djbk::ModelSetProxy;
+#include "djb_merl_hits.inc"                               // merl_set_texel, the queue record, merl_is_hits / merl_light_hits
+#include "djb_utia_hits.inc"                               // TABLE_F4, utia_target
+#include "djb_model_hits.inc"                              // row_stride, unit, rows_lds, min_waves, ModelLaunch, proxy_of, model_is_trip
 
 // ---- the partition's third step: the list, and +0 in every output of an inactive hit.  LIGHT: va = out_fr; else va = out_weight, vb = out_i
 template <bool LIGHT>
@@ -60,152 +57,33 @@ __global__ __launch_bounds__(BLOCK) void k_scene_scatter_proxy(const unsigned in
                                                                unsigned int n_tiles, const unsigned int *tiles, unsigned int *list, View va, View vb,
                                                                float *out_pdf)
 {
-	const unsigned int lane = threadIdx.x & 63u, tile = wave_tile();
-	if (tile >= n_tiles) return;
-	unsigned int off[4];                                                           // wave-uniform: where the tile's next hit of each kind goes
-#pragma unroll
-	for (unsigned int u = 0; u < 4u; ++u) off[u] = tiles[tile * 4u + u];
-	const unsigned long long below = (1ull << lane) - 1ull;
-	for (unsigned int s = 0; s < STEPS; ++s) {
-		const unsigned int k = tile * TILE + s * 64u + lane;
-		const bool live = k < m;
-		unsigned int q = K_DEAD;
-		if (live) q = kind_of(slot_of(slots, n_slots, (unsigned int)mat[k]));
-#pragma unroll
-		for (unsigned int u = 0; u < 4u; ++u) {
-			const unsigned long long mask = __ballot(q == u);
-			if (q == u) list[off[u] + (unsigned int)__popcll(mask & below)] = k;    // below count[u] + offset[u] <= m: the scan counted these hits
-			off[u] += (unsigned int)__popcll(mask);
-		}
-		if (live && q == K_DEAD) {                                                 // an inactive hit: +0 everywhere, nothing read
-			store3(va, (long long)k, mk(0, 0, 0));
-			if (!LIGHT) store3(vb, (long long)k, mk(0, 0, 0));
-			out_pdf[k] = 0.0f;
-		}
-	}
+	scatter_hits(slots, n_slots, m, mat, n_tiles, tiles, list, [&](unsigned int k) {
+		store3(va, (long long)k, mk(0, 0, 0));
+		if (!LIGHT) store3(vb, (long long)k, mk(0, 0, 0));
+		out_pdf[k] = 0.0f;
+	});
 }
 
-// ---- merl, sampling: k_evalp_is_proxy_merl_set over the list
+// ---- merl: merl_is_hits / merl_light_hits over the list
 template <int PKIND>
 __global__ __launch_bounds__(BLOCK) void k_scene_merl_is(Hits h, Brdf pb, const Params *params, const MerlTexel *tex, unsigned int n_mat,
                                                          const float *u1a, const float *u2a, View vo, View vw_out, View vi_out, float *out_pdf,
                                                          MerlGuard g, int merl_exact)
 {
-	static_assert(PKIND == KIND_GGX || PKIND == KIND_BECKMANN, "the proxy of a MERL set is an analytic lobe");
-	constexpr bool GLIBCT = PKIND == KIND_BECKMANN;                                // logf / expf / powf of Beckmann's quantile functions
+	constexpr bool GLIBCT = PKIND == KIND_BECKMANN;
 	__shared__ double s_glibc[GLIBCT ? GLIBC_LDS_WORDS : 1];
 	__shared__ unsigned long long s_exp[GLIBCT ? 256 : 1];
 	__shared__ unsigned int s_q[BLOCK / 64][10][RECQ_CAP];
-	const unsigned int cnt = h.hdr[K_MERL], first = h.hdr[4 + K_MERL];             // uniform addresses: scalar loads
-	if (blockIdx.x * (unsigned int)BLOCK >= cnt) return;                           // the grid is sized for the chunk; before the staging and its barrier
-	GlibcTabs gt = glibc_tabs_global();
-	if (GLIBCT) {
-		gt = glibc_tabs_to_lds(s_glibc, threadIdx.x, BLOCK);
-		const LdsTab e = glibc_exp_tab_to_lds(s_exp, threadIdx.x, BLOCK);
-		pb.exp_lds = e; gt.exp64 = e;
-		__syncthreads();
-	}
-	pb.atan_lds = 0u;
-
-	const unsigned int t = threadIdx.x, wave = t >> 6, lane = t & 63u;
-	unsigned int (&q)[10][RECQ_CAP] = s_q[wave];
-	unsigned int qn = 0;                                                           // wave-uniform
-	const unsigned int stride = gridDim.x * (unsigned int)BLOCK;                   // cnt <= 2^26, stride <= 2^20: j0 does not wrap
-	for (unsigned int j0 = blockIdx.x * (unsigned int)BLOCK; ; j0 += stride) {     // workgroup-uniform trip count; one extra trip flushes the queues
-		const bool last = j0 >= cnt;
-		bool amb = false;
-		unsigned int id = 0u, k = 0u;
-		v3 i_ = mk(0, 0, 0), o = mk(0, 0, 1); float pdf = 0.0f;
-		const unsigned int rem = last ? 0u : cnt - j0 >= (unsigned int)BLOCK ? (unsigned int)BLOCK : cnt - j0;
-		if (t < rem) {
-			k = h.list[first + j0 + t];
-			v3 w = mk(0, 0, 0);
-			if (local_of(h, k, K_MERL, n_mat, id)) {
-				const float u1 = u1a[k], u2 = u2a[k];
-				o = load3(vo, (long long)k);
-				const Params pp = params[id];
-				// ---- proxy: direction, then the pdf-only arm of mf_eval_pdf on (i, o)
-				i_ = mf_sample<PKIND>(pb, pp, u1, u2, o, gt);
-				if (!(i_.z <= 0.0f)) {                                                  // the side check; a NaN i.z is evaluated
-					v3 unused;
-					mf_eval_pdf<PKIND, 4>(pb, pp, i_, o, unused, pdf);
-					int idx = 0;
-					if (!merl_exact && merl_index_fast(i_, o, g, idx))
-						w = divs(scale(i_.z, merl_set_texel(tex, id, idx)), pdf);           // brdf::evalp = eval * i.z, dj_brdf.h:803-806
-					else amb = true;                                                    // the exact index finishes this pair (below)
-				}
-			}
-			store3(vi_out, (long long)k, i_); out_pdf[k] = pdf;
-			if (!amb) store3(vw_out, (long long)k, w);
-		}
-		unsigned int rec[10];                                                      // built here, outside the branches above (djb_worklist.hpp)
-		rec_pack(rec, (long long)k, id, i_, o); rec[9] = __float_as_uint(pdf);
-		recq_push(q, qn, lane, amb, rec);
-		recq_drain(q, qn, lane, last, [&](const unsigned int *r) {
-			const v3 iq = rec_v3(r, 3);
-			const v3 e = merl_set_texel(tex, r[2], merl_index(iq, rec_v3(r, 6)));
-			store3(vw_out, rec_k(r), divs(scale(iq.z, e), __uint_as_float(r[9])));
-		});
-		if (last) break;
-	}
+	merl_is_hits<PKIND>(ListHits(h, K_MERL, n_mat), s_glibc, s_exp, s_q, pb, params, tex, u1a, u2a, vo, vw_out, vi_out, out_pdf, g, merl_exact);
 }
 
-// ---- merl, the light sample: k_merl_set_evalp_pdf over the list.  A guarded hit reads nothing and is never queued
 template <int PKIND>
 __global__ __launch_bounds__(BLOCK) void k_scene_merl_light(Hits h, Brdf pb, const Params *params, const MerlTexel *tex, unsigned int n_mat, View vi,
                                                             View vo, View vout, float *out_pdf, MerlGuard g, int merl_exact)
 {
-	static_assert(PKIND == KIND_GGX || PKIND == KIND_BECKMANN, "the proxy of a MERL set is an analytic lobe");
-	constexpr bool EXPT = PKIND == KIND_BECKMANN;                                  // the pdf arm calls exp alone
-	__shared__ unsigned long long s_exp[EXPT ? 256 : 1];
+	__shared__ unsigned long long s_exp[PKIND == KIND_BECKMANN ? 256 : 1];
 	__shared__ unsigned int s_q[BLOCK / 64][9][RECQ_CAP];
-	const unsigned int cnt = h.hdr[K_MERL], first = h.hdr[4 + K_MERL];
-	if (blockIdx.x * (unsigned int)BLOCK >= cnt) return;
-	if (EXPT) {
-		pb.exp_lds = glibc_exp_tab_to_lds(s_exp, threadIdx.x, BLOCK);
-		__syncthreads();
-	}
-	pb.atan_lds = 0u;
-
-	const unsigned int t = threadIdx.x, wave = t >> 6, lane = t & 63u;
-	unsigned int (&q)[9][RECQ_CAP] = s_q[wave];
-	unsigned int qn = 0;                                                           // wave-uniform
-	const unsigned int stride = gridDim.x * (unsigned int)BLOCK;
-	for (unsigned int j0 = blockIdx.x * (unsigned int)BLOCK; ; j0 += stride) {     // workgroup-uniform trip count; one extra trip flushes the queues
-		const bool last = j0 >= cnt;
-		bool amb = false;
-		unsigned int id = 0u, k = 0u;
-		v3 i = mk(0, 0, 1), o = mk(0, 0, 1);
-		const unsigned int rem = last ? 0u : cnt - j0 >= (unsigned int)BLOCK ? (unsigned int)BLOCK : cnt - j0;
-		if (t < rem) {
-			k = h.list[first + j0 + t];
-			const bool act = local_of(h, k, K_MERL, n_mat, id);
-			i = load3(vi, (long long)k); o = load3(vo, (long long)k);
-			v3 fr = mk(0, 0, 0); float pdf = 0.0f;                                     // below the horizon: +0, nothing read
-			if (act && !(i.z <= 0.0f || o.z <= 0.0f)) {                                // dj_merl.cpp:57-60, 69-72; a NaN z is evaluated
-				const Params pp = params[id];                                           // asked for first: loads return in order, and the
-				int idx = 0;                                                            // pdf must not wait for the texel behind them
-				const bool decided = !merl_exact && merl_index_fast(i, o, g, idx);
-				v3 e = mk(0, 0, 0);
-				if (decided) e = merl_set_texel(tex, id, idx);                          // in flight across the pdf
-				v3 unused;
-				mf_eval_pdf<PKIND, 4>(pb, pp, i, o, unused, pdf);                       // microfacet::pdf, dj_brdf.h:1713-1730
-				if (decided) fr = scale(i.z, e);                                        // brdf::evalp, dj_brdf.h:803-806
-				else amb = true;                                                        // the exact index finishes this pair
-			}
-			out_pdf[k] = pdf;
-			if (!amb) store3(vout, (long long)k, fr);
-		}
-		unsigned int rec[9];                                                       // built here, outside the branches above (djb_worklist.hpp)
-		rec_pack(rec, (long long)k, id, i, o);
-		recq_push(q, qn, lane, amb, rec);
-		recq_drain(q, qn, lane, last, [&](const unsigned int *r) {
-			const v3 iq = rec_v3(r, 3);
-			const v3 e = merl_set_texel(tex, r[2], merl_index(iq, rec_v3(r, 6)));
-			store3(vout, rec_k(r), scale(iq.z, e));
-		});
-		if (last) break;
-	}
+	merl_light_hits<PKIND>(ListHits(h, K_MERL, n_mat), s_exp, s_q, pb, params, tex, vi, vo, vout, out_pdf, g, merl_exact);
 }
 
 // ---- utia: the single-material proxy kernels per hit.  tb: kind utia, nothing else set; its `utia` becomes the hit's table per lane
@@ -282,79 +160,27 @@ __global__ __launch_bounds__(BLOCK) void k_scene_utia_light(Hits h, Brdf pb, Brd
 	}
 }
 
-// ---- sgd / abc: k_model_set_evalp_is_proxy / k_model_set_evalp_pdf over the list
-// the lane's proxy: b's staged tables, the tables and the count of material `id` (proxy_of, djb_kernels_model_set_proxy.hip)
-DJB_DEV Brdf proxy_of(Brdf b, const ModelSetProxy &px, unsigned int n_mat, unsigned int id)
-{
-	const unsigned int res4 = (unsigned int)px.res * 4u;
-	const char *base = (const char *)px.tab;
-	const unsigned int off = id * (3u * res4);                                     // < 2^31: M * res <= MODEL_SET_PROXY_MAX_ENTRIES
-	b.shadow = px.shadow;
-	b.p22 = (const float *)(base + off);
-	b.sigma = (const float *)(base + (off + res4));
-	b.qf = (const float *)(base + (off + 2u * res4));
-	b.n_p22 = b.n_sigma = px.res;
-	b.n_qf = *(const int *)(base + (n_mat * (3u * res4) + (id << 2)));
-	return b;
-}
-
+// ---- sgd / abc: model_is_trip over the list; the light sample written out
 template <int KIND>
-__global__ __launch_bounds__(BLOCK, min_waves(KIND)) void k_scene_model_is(Hits h, Brdf b, Params pp, ModelSetProxy px, const double *rows, unsigned int n_mat,
-                                                                           int in_lds, const float *u1a, const float *u2a, View vo, View vw_out,
-                                                                           View vi_out, float *out_pdf)
+__global__ __launch_bounds__(BLOCK, min_waves(KIND, true)) void k_scene_model_is(Hits h, Brdf b, Params pp, ModelSetProxy px, const double *rows, unsigned int n_mat,
+                                                                                 int in_lds, const float *u1a, const float *u2a, View vo, View vw_out,
+                                                                                 View vi_out, float *out_pdf)
 {
-	constexpr unsigned int STRIDE = (unsigned int)row_stride(KIND);
-	constexpr unsigned int Q = KIND == KIND_SGD ? K_SGD : K_ABC;
 	__shared__ unsigned long long s_exp[256];
 	__shared__ double s_pow[384];
 	__shared__ double s_atan[16];
 	extern __shared__ double s_rows[];                                            // n_mat * STRIDE doubles when in_lds, else none
-	const unsigned int cnt = h.hdr[Q], first = h.hdr[4 + Q];
-	if (blockIdx.x * (unsigned int)BLOCK >= cnt) return;                           // workgroup-uniform, before the staging and its barrier
-	b.exp_lds = glibc_exp_tab_to_lds(s_exp, threadIdx.x, BLOCK);
-	b.pow_lds = glibc_pow_tab_to_lds(s_pow, threadIdx.x, BLOCK);
-	b.atan_lds = atan_tab_to_lds(s_atan, threadIdx.x);                             // the proxy's table coordinates: staged for abc as well
-	if (in_lds) {                                                                 // n_mat <= rows_lds(KIND): the launcher's test
-		const unsigned int count = n_mat * STRIDE;
-		for (unsigned int j = threadIdx.x; j < count; j += BLOCK) s_rows[j] = rows[j];
-	}
-	__syncthreads();
-	const GlibcTabs gt = glibc_tabs_global();                                     // Beckmann's: mf_sample<KIND_TABULAR> does not read it
-	const unsigned int stride = gridDim.x * (unsigned int)BLOCK;
-	const unsigned int t = threadIdx.x;
-	for (unsigned int j0 = blockIdx.x * (unsigned int)BLOCK; j0 < cnt; j0 += stride) {     // j0: workgroup-uniform
-		const unsigned int j = j0 + t;
-		const bool live = j < cnt;
-		bool act = false;
-		unsigned int id = 0u, k = 0u;
-		float u1 = 0.0f, u2 = 0.0f;
-		v3 o = mk(0, 0, 1);
-		if (live) {
-			k = h.list[first + j];
-			act = local_of(h, k, Q, n_mat, id);
-			u1 = u1a[k]; u2 = u2a[k];
-			o = load3(vo, (long long)k);
-		}
-		v3 w = mk(0, 0, 0), i_ = mk(0, 0, 0); float pdf = 0.0f;
-		if (__ballot(act) != 0ull) {                                               // wave-uniform
-			if (act) {
-				const Brdf pb = proxy_of(b, px, n_mat, id);
-				i_ = mf_sample<KIND_TABULAR>(pb, pp, u1, u2, o, gt);
-				if (!(i_.z <= 0.0f)) {                                              // the plugins' side check; a NaN i.z is evaluated
-					v3 unused, fr = mk(0, 0, 0);
-					mf_eval_pdf<KIND_TABULAR, 4>(pb, pp, i_, o, unused, pdf);
-					if (in_lds) unit<KIND, 2>(b, s_rows + id * STRIDE, i_, o, fr);                             // workgroup-uniform: ds_read_b64 ...
-					else unit<KIND, 2>(b, (const double *)((const char *)rows + (size_t)(id * (STRIDE * 8u))), i_, o, fr);   // ... or uniform base + 32-bit byte offset
-					w = divs(fr, pdf);                                              // (1.0f / pdf) * fr: the IEEE result for a zero pdf
-				}
-			}
-		}
-		if (live) { store3(vi_out, (long long)k, i_); out_pdf[k] = pdf; store3(vw_out, (long long)k, w); }
-	}
+	const ListHits src(h, KIND == KIND_SGD ? K_SGD : K_ABC, n_mat);
+	if (src.none()) return;                                                        // workgroup-uniform, before the staging and its barrier
+	b = stage<KIND, true>(b, s_exp, s_pow, s_atan, s_rows, rows, src.n_mat, in_lds);
+	const unsigned int stride = src.stride();
+	for (unsigned int j0 = src.start(); j0 < src.count(); j0 += stride)                      // j0: workgroup-uniform
+		model_is_trip<KIND>(src, j0, s_rows, b, pp, px, rows, in_lds, u1a, u2a, vo, vw_out, vi_out, out_pdf);
 }
 
+// k_model_set_evalp_pdf over the list, written out: on one body the pair did not keep its instructions
 template <int KIND>
-__global__ __launch_bounds__(BLOCK, min_waves(KIND)) void k_scene_model_light(Hits h, Brdf b, Params pp, ModelSetProxy px, const double *rows,
+__global__ __launch_bounds__(BLOCK, min_waves(KIND, true)) void k_scene_model_light(Hits h, Brdf b, Params pp, ModelSetProxy px, const double *rows,
                                                                               unsigned int n_mat, int in_lds, View vi, View vo, View vout, float *out_pdf)
 {
 	constexpr unsigned int STRIDE = (unsigned int)row_stride(KIND);
@@ -365,14 +191,7 @@ __global__ __launch_bounds__(BLOCK, min_waves(KIND)) void k_scene_model_light(Hi
 	extern __shared__ double s_rows[];
 	const unsigned int cnt = h.hdr[Q], first = h.hdr[4 + Q];
 	if (blockIdx.x * (unsigned int)BLOCK >= cnt) return;
-	b.exp_lds = glibc_exp_tab_to_lds(s_exp, threadIdx.x, BLOCK);
-	b.pow_lds = glibc_pow_tab_to_lds(s_pow, threadIdx.x, BLOCK);
-	b.atan_lds = atan_tab_to_lds(s_atan, threadIdx.x);
-	if (in_lds) {
-		const unsigned int count = n_mat * STRIDE;
-		for (unsigned int j = threadIdx.x; j < count; j += BLOCK) s_rows[j] = rows[j];
-	}
-	__syncthreads();
+	b = stage<KIND, true>(b, s_exp, s_pow, s_atan, s_rows, rows, n_mat, in_lds);
 	const unsigned int stride = gridDim.x * (unsigned int)BLOCK;
 	const unsigned int t = threadIdx.x;
 	for (unsigned int j0 = blockIdx.x * (unsigned int)BLOCK; j0 < cnt; j0 += stride) {     // j0: workgroup-uniform
@@ -404,25 +223,6 @@ __global__ __launch_bounds__(BLOCK, min_waves(KIND)) void k_scene_model_light(Hi
 }
 
 // ---- launches
-struct ModelLaunch {
-	Brdf b; int in_lds; size_t lds;
-	ModelLaunch(int kind, int n_mat, bool rows_global)
-	{
-		memset(&b, 0, sizeof b);
-		b.kind = kind;
-		b.fr.kind = kind == KIND_SGD ? FR_SGD : FR_UNPOLARIZED;
-		in_lds = !rows_global && n_mat <= rows_lds(kind);
-		lds = in_lds ? sizeof(double) * (size_t)n_mat * (size_t)row_stride(kind) : 0;                // dynamic: a small set costs no occupancy
-	}
-};
-Brdf utia_target()
-{
-	Brdf b;
-	memset(&b, 0, sizeof b);
-	b.kind = KIND_UTIA;
-	return b;
-}
-
 // the partition of a chunk; LIGHT: va = out_fr
 template <bool LIGHT>
 hipError_t partition(hipStream_t s, const unsigned int *slots, int n_slots, long long m, const int32_t *mat, const View &va, const View &vb, float *out_pdf,
@@ -474,7 +274,7 @@ template <int KIND>
 hipError_t launch_model_is(hipStream_t s, const Hits &h, const double *rows, int n_mat, const ModelSetProxy &px, const Params &pp, bool rows_global,
                            const dim3 &g, const float *u1, const float *u2, const View &o, const View &out_w, const View &out_i, float *out_pdf)
 {
-	const ModelLaunch L(KIND, n_mat, rows_global);
+	const ModelLaunch L(KIND, n_mat, rows_global, true);
 	hipLaunchKernelGGL((k_scene_model_is<KIND>), g, dim3(BLOCK), L.lds, s, h, L.b, pp, px, rows, (unsigned int)n_mat, L.in_lds, u1, u2, o, out_w, out_i, out_pdf);
 	return hipGetLastError();
 }
@@ -482,7 +282,7 @@ template <int KIND>
 hipError_t launch_model_light(hipStream_t s, const Hits &h, const double *rows, int n_mat, const ModelSetProxy &px, const Params &pp, bool rows_global,
                               const dim3 &g, const View &i, const View &o, const View &out, float *out_pdf)
 {
-	const ModelLaunch L(KIND, n_mat, rows_global);
+	const ModelLaunch L(KIND, n_mat, rows_global, true);
 	hipLaunchKernelGGL((k_scene_model_light<KIND>), g, dim3(BLOCK), L.lds, s, h, L.b, pp, px, rows, (unsigned int)n_mat, L.in_lds, i, o, out, out_pdf);
 	return hipGetLastError();
 }

@@ -22,14 +22,12 @@ using namespace djbdev;
 namespace {
 
 constexpr int BLOCK = 256;
-#ifndef DJB_UTIA_MIN_WAVES
-#define DJB_UTIA_MIN_WAVES 4
-#endif
 constexpr long long GRID_CAP = 256LL * 64;                 // as k_utia_v2
-constexpr unsigned int TABLE_F4 = 288u * 288u * 8u;        // float4 per material
-constexpr unsigned int NO_RECORD = 0xffffffffu;            // an inactive owner: its chunks are not requested
-static_assert(255ull * TABLE_F4 + 8ull * (288ull * 288ull - 1ull) + 7ull < (1ull << 28), "the byte offset of the last chunk fits 32 bits");
 
+#include "djb_hit_source.inc"                              // BatchHits
+#include "djb_utia_hits.inc"                               // DJB_UTIA_MIN_WAVES, TABLE_F4, NO_RECORD, utia_target
+
+// 40 B per hit, touched once: non-temporal (k_utia_v2)
 template <int WANT, bool DENSE>
 __global__ __launch_bounds__(BLOCK, DJB_UTIA_MIN_WAVES) void k_utia_set(const float4 *tab, int n_mat, long long n, const int32_t *mat, View vi, View vo,
                                                                        View vout, unsigned int *list, unsigned int cap, unsigned int *count)
@@ -137,9 +135,7 @@ template <int WANT>
 hipError_t launch_set(hipStream_t s, const float4 *tab, int n_mat, long long n, const int32_t *mat, const View &i, const View &o, const View &out,
                       unsigned int *list, unsigned int cap, unsigned int *count, bool exact_only)
 {
-	Brdf b;
-	memset(&b, 0, sizeof b);
-	b.kind = KIND_UTIA;
+	const Brdf b = utia_target();
 	dim3 t(BLOCK);
 	if (exact_only) {
 		hipLaunchKernelGGL((k_utia_set_fix<WANT>), dim3(djbk::grid_capped(n, BLOCK, GRID_CAP)), t, 0, s, b, tab, n_mat, n, mat, i, o, out, nullptr, 0u, nullptr, 1);

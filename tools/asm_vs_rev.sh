@@ -2,8 +2,14 @@
 # asm_vs_rev.sh <rev> <file.hip>...: is the gfx950 code of these translation units the code they had at <rev>?
 # Both versions (the working tree's and `git archive <rev>`'s, each with its own headers and its own Makefile's flags for that
 # file) are compiled with -S --cuda-device-only; comment lines and the __hip_cuid_* symbol are dropped, function-local LDS symbols
-# (_ZZ<function>E<name>) are renamed to <name>; then the text of every kernel is compared -- a plain diff, one line per kernel:
-# `identical` or `differs`, with both instruction counts.  A kernel of one side only is listed as such.  Only the text between a
+# (_ZZ<function>E<name>) are renamed to <name> and the function ordinal of block labels (.LBB<n>_<m> -> .LBB_<m>: it moves when a
+# function is added or removed anywhere before in the file) is dropped; then the text of every kernel is compared, one line per kernel
+# with both instruction counts:
+#   identical           the same text
+#   same instructions   the same multiset of (mnemonic, non-register operands: immediates, offsets, modifiers, s_waitcnt fields), and
+#                       therefore the same count: register numbers, the order of operands and the order of instructions may differ
+#   differs             anything else
+# A kernel of one side only is listed as such.  Only the text between a
 # function's label and its end is compared: the .amdhsa_* metadata (LDS size, register counts) is not, so read the result together
 # with tools/kernel_resources.sh at both revisions.
 # ASM_KEEP=<dir> keeps the normalised listings (<dir>/{old,new}/<file>.s) for a closer look with diff.
@@ -42,6 +48,7 @@ def kernels(path, side):
         if not l.strip() or l.lstrip().startswith(';') or '__hip_cuid_' in l: continue
         l = re.sub(r'\s*;.*$', '', l)                                   # trailing comments (register-pressure notes and the like)
         l = re.sub(r'_ZZ\w+', local_name, l)
+        l = re.sub(r'\.LBB\d+_', '.LBB_', l)                          # the function's ordinal in the file
         lines.append(l)
     if keep:
         os.makedirs(os.path.join(keep, side), exist_ok=True)
@@ -55,6 +62,15 @@ def kernels(path, side):
             if l.startswith('.Lfunc_end'): cur = None
             else: out[cur].append(l)
     return out
+REG = re.compile(r'^-?\|?(?:[vsa]\d+|[vsa]\[\d+:\d+\]|vcc(?:_lo|_hi)?|exec(?:_lo|_hi)?|scc|m0|off|null|\.LBB_\d+)\|?$')
+def bag(body):          # the multiset of (mnemonic, sorted non-register operands)
+    out = []
+    for l in body:
+        if not l.startswith('\t') or l.lstrip().startswith('.'): continue
+        t = l.split(None, 1)
+        ops = [o for o in re.split(r'[,\s]+', t[1]) if o and not REG.match(o)] if len(t) > 1 else []
+        out.append((t[0], tuple(sorted(ops))))
+    return sorted(out)
 def count(body): return sum(1 for l in body if l.startswith('\t') and not l.lstrip().startswith('.'))
 old, new = kernels(sys.argv[2], 'old'), kernels(sys.argv[3], 'new')
 names = list(dict.fromkeys(list(old) + list(new)))
@@ -65,9 +81,9 @@ for k, p in zip(names, pretty):
     if k not in old: print(f'{name}: {p:60s} only in the working tree ({count(new[k])} instructions)'); n_diff += 1
     elif k not in new: print(f'{name}: {p:60s} only at the revision ({count(old[k])} instructions)'); n_diff += 1
     else:
-        same = old[k] == new[k]
-        n_diff += not same
-        print(f"{name}: {p:60s} {'identical' if same else 'differs  '} {count(old[k]):6d} {count(new[k]):6d}")
+        verdict = 'identical' if old[k] == new[k] else 'same instructions' if bag(old[k]) == bag(new[k]) else 'differs'
+        n_diff += verdict == 'differs'
+        print(f"{name}: {p:60s} {verdict:17s} {count(old[k]):6d} {count(new[k]):6d}")
 print(f'{name}: {len(names)} kernels, {n_diff} differ')
 EOF
 done

@@ -1,5 +1,5 @@
 #!/bin/bash
-# kernel_resources.sh <file.hip> [filter] [extra flags]: VGPRs / spills / scratch / occupancy / LDS of every kernel of one translation unit
+# kernel_resources.sh <file.hip> [filter] [extra flags]: VGPRs / VGPR and SGPR spills / scratch / occupancy / LDS of every kernel of one translation unit
 # (hipcc -Rpass-analysis=kernel-resource-usage with the Makefile's flags; add e.g. "-mllvm -disable-machine-licm=false" as the third argument to see the
 # hoisting MachineLICM would do), demangled, one line per kernel.  Build container; no GPU.
 cd "$(dirname "$0")/../dj_brdf_amd/csrc"
@@ -21,5 +21,5 @@ names = subprocess.run(['c++filt'] + [r['name'] for r in rows], capture_output=T
 for r, n in zip(rows, names):
     n = re.sub(r'\(anonymous namespace\)::', '', n); n = re.sub(r'\(.*', '', n).replace('void ', '')
     if '$2' and not re.search('$2', n): continue
-    print(f\"{n:44s} VGPR {r.get('VGPRs','?'):>4s} AGPR {r.get('AGPRs','?'):>3s} spill {r.get('VGPR Spill','?'):>4s} scratch {r.get('ScratchSize [bytes/lane]','?'):>5s} occ {r.get('Occupancy [waves/SIMD]','?'):>2s} LDS {r.get('LDS Size [bytes/block]','?'):>6s}\")
+    print(f\"{n:44s} VGPR {r.get('VGPRs','?'):>4s} AGPR {r.get('AGPRs','?'):>3s} spill v {r.get('VGPRs Spill','?'):>3s} s {r.get('SGPRs Spill','?'):>3s} scratch {r.get('ScratchSize [bytes/lane]','?'):>5s} occ {r.get('Occupancy [waves/SIMD]','?'):>2s} LDS {r.get('LDS Size [bytes/block]','?'):>6s}\")
 "

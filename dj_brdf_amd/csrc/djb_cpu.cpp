@@ -878,31 +878,45 @@ djb_status sample(djb_ctx *ctx, const djb_brdf *b_, int64_t n, const float *u1, 
 	return DJB_OK;
 }
 
-// the per-bounce step of the dj_merl / dj_utia / dj_sgd / dj_abc plugins (mitsuba/djb_mitsuba.hpp: finish_lobe_sample), any pair of kinds
-template <int PK, int TK>
+// One hit of either per-bounce step of the dj_merl / dj_utia / dj_sgd / dj_abc plugins (mitsuba/djb_mitsuba.hpp), any pair of kinds, on a
+// target (tb, tp) and a proxy (pb, pp) that stand for the hit's material.  The sampling step (finish_lobe_sample): i from the proxy at
+// (u1, u2), then -- unless i.z <= 0, the plugins' side check -- the proxy's pdf, evalp of the target and fr = evalp / pdf, the weight.
+// LIGHT, the light sample: i is given, and unless i.z <= 0 || o.z <= 0, the plugins' guard, the proxy's pdf and evalp of the target.
+// A NaN z passes either guard and is evaluated; a hit that does not pass has +0 in fr and pdf.  Every host loop of the two steps --
+// single-material, set, scene -- runs this text: the guards and the order of the per-unit calls stand nowhere else
+template <int PK, int TK, bool LIGHT>
+static inline void proxy_hit(const Brdf &tb, const Params &tp, const Brdf &pb, const Params &pp, float u1, float u2, v3 o, const GlibcTabs &gt,
+                             v3 &i, v3 &fr, float &pdf)
+{
+	v3 unused_w, unused_fr = mk(0, 0, 0); float unused_pdf = 0.0f;
+	fr = mk(0, 0, 0); pdf = 0.0f;
+	if (!LIGHT) sample_one<PK, false>(pb, pp, u1, u2, o, gt, i, unused_w, unused_pdf);
+	if (i.z <= 0.0f || (LIGHT && o.z <= 0.0f)) return;
+	eval_one<PK, 4>(pb, pp, i, o, unused_fr, pdf);
+	eval_one<TK, 2>(tb, tp, i, o, fr, unused_pdf);
+	if (!LIGHT) fr = divs(fr, pdf);
+}
+// the single-material pair.  LIGHT: va = i, outputs fr and pdf; else va is not read, u1a / u2a are, outputs weight (vfr), i and pdf
+template <int PK, int TK, bool LIGHT>
 void proxy_loop(const Brdf &tb, const Params &tp, const Brdf &pb, const Params &pp, long long k0, long long k1, const float *u1a, const float *u2a,
-                const View &vo, const View &vw_out, const View &vi_out, float *out_pdf)
+                const View &va, const View &vo, const View &vfr, const View &vi_out, float *out_pdf)
 {
 	const GlibcTabs gt = glibc_tabs_global();
 	for (long long k = k0; k < k1; ++k) {
-		const v3 o = load3(vo, k);
-		v3 i_, unused_w, w = mk(0, 0, 0); float pdf = 0.0f, unused_pdf;
-		sample_one<PK, false>(pb, pp, u1a[k], u2a[k], o, gt, i_, unused_w, unused_pdf);
-		if (!(i_.z <= 0.0f)) {                                                          // the plugins' side check; a NaN i.z passes
-			v3 fr = mk(0, 0, 0), unused_fr = mk(0, 0, 0);
-			eval_one<PK, 4>(pb, pp, i_, o, unused_fr, pdf);
-			eval_one<TK, 2>(tb, tp, i_, o, fr, unused_pdf);
-			w = divs(fr, pdf);
-		}
-		store3(vw_out, k, w); store3(vi_out, k, i_); out_pdf[k] = pdf;
+		v3 i_ = LIGHT ? load3(va, k) : mk(0, 0, 0), fr; float pdf;
+		proxy_hit<PK, TK, LIGHT>(tb, tp, pb, pp, LIGHT ? 0.0f : u1a[k], LIGHT ? 0.0f : u2a[k], load3(vo, k), gt, i_, fr, pdf);
+		store3(vfr, k, fr);
+		if (!LIGHT) store3(vi_out, k, i_);
+		out_pdf[k] = pdf;
 	}
 }
-template <int PK>
+template <int PK, bool LIGHT>
 void proxy_target(const Brdf &tb, const Params &tp, const Brdf &pb, const Params &pp, long long k0, long long k1, const float *u1a, const float *u2a,
-                  const View &vo, const View &vw_out, const View &vi_out, float *out_pdf)
+                  const View &va, const View &vo, const View &vfr, const View &vi_out, float *out_pdf)
 {
-	DJB_KIND_SWITCH(tb.kind, (proxy_loop<PK, K>(tb, tp, pb, pp, k0, k1, u1a, u2a, vo, vw_out, vi_out, out_pdf)))
+	DJB_KIND_SWITCH(tb.kind, (proxy_loop<PK, K, LIGHT>(tb, tp, pb, pp, k0, k1, u1a, u2a, va, vo, vfr, vi_out, out_pdf)))
 }
+static const View NO_VIEW = { nullptr, nullptr, nullptr, 0 };
 djb_status evalp_is_proxy(djb_ctx *ctx, const djb_brdf *target, const djb_brdf *proxy, int64_t n, const float *u1, const float *u2,
                           const djb_vec3_view *o, const djb_params *target_params, const djb_params *proxy_params,
                           const djb_vec3_view *out_w, const djb_vec3_view *out_i, float *out_pdf)
@@ -923,34 +937,11 @@ djb_status evalp_is_proxy(djb_ctx *ctx, const djb_brdf *target, const djb_brdf *
 	}
 	const View vo = view_of(o), vw = view_of(out_w), vi = view_of(out_i);
 	parallel_for(C(ctx), n, 2048, [&](long long k0, long long k1) {
-		DJB_KIND_SWITCH(pb.kind, (proxy_target<K>(tb, tp, pb, pp, k0, k1, u1, u2, vo, vw, vi, out_pdf)))
+		DJB_KIND_SWITCH(pb.kind, (proxy_target<K, false>(tb, tp, pb, pp, k0, k1, u1, u2, NO_VIEW, vo, vw, vi, out_pdf)))
 	});
 	return DJB_OK;
 }
 
-// the light sample of the same plugins: evalp of the target and the proxy's pdf for a given pair, any pair of kinds; the plugins' guard
-// (cosTheta(wi) <= 0 || cosTheta(wo) <= 0 -> 0, a NaN z evaluated) applied to both
-template <int PK, int TK>
-void proxy_light_loop(const Brdf &tb, const Params &tp, const Brdf &pb, const Params &pp, long long k0, long long k1, const View &vi, const View &vo,
-                      const View &vout, float *out_pdf)
-{
-	for (long long k = k0; k < k1; ++k) {
-		v3 fr = mk(0, 0, 0); float pdf = 0.0f;
-		const v3 i = load3(vi, k), o = load3(vo, k);
-		if (!(i.z <= 0.0f || o.z <= 0.0f)) {
-			v3 unused_fr = mk(0, 0, 0); float unused_pdf = 0.0f;
-			eval_one<PK, 4>(pb, pp, i, o, unused_fr, pdf);
-			eval_one<TK, 2>(tb, tp, i, o, fr, unused_pdf);
-		}
-		store3(vout, k, fr); out_pdf[k] = pdf;
-	}
-}
-template <int PK>
-void proxy_light_target(const Brdf &tb, const Params &tp, const Brdf &pb, const Params &pp, long long k0, long long k1, const View &vi, const View &vo,
-                        const View &vout, float *out_pdf)
-{
-	DJB_KIND_SWITCH(tb.kind, (proxy_light_loop<PK, K>(tb, tp, pb, pp, k0, k1, vi, vo, vout, out_pdf)))
-}
 djb_status evalp_pdf_proxy(djb_ctx *ctx, const djb_brdf *target, const djb_brdf *proxy, int64_t n, const djb_vec3_view *i, const djb_vec3_view *o,
                            const djb_params *target_params, const djb_params *proxy_params, const djb_vec3_view *out_fr, float *out_pdf)
 {
@@ -966,13 +957,17 @@ djb_status evalp_pdf_proxy(djb_ctx *ctx, const djb_brdf *target, const djb_brdf 
 	if (!valid(i) || !valid(o)) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null vec3 view");
 	const View vi = view_of(i), vo = view_of(o), vout = view_of(out_fr);
 	parallel_for(C(ctx), n, 2048, [&](long long k0, long long k1) {
-		DJB_KIND_SWITCH(pb.kind, (proxy_light_target<K>(tb, tp, pb, pp, k0, k1, vi, vo, vout, out_pdf)))
+		DJB_KIND_SWITCH(pb.kind, (proxy_target<K, true>(tb, tp, pb, pp, k0, k1, nullptr, nullptr, vi, vo, vout, NO_VIEW, out_pdf)))
 	});
 	return DJB_OK;
 }
 
-// ------------------------------------------------------------------ material sets (MERL, UTIA, SGD / ABC): eval_one per hit on a Brdf that
-// the hit's material id points at its table or row; an id outside [0, n_mat) is an inactive hit (+0 in every output, nothing read)
+// ------------------------------------------------------------------ material sets (MERL, UTIA, SGD / ABC) and scenes.  Three layers:
+//   a material binding per kind of set (TableMat, ModelMat) makes a lane's Brdf / Params stand for material m, and runs one hit on it: eval
+//   (eval_one) or one of the two proxy steps (proxy_hit above); a scene's binding (SceneMat) classifies the hit and hands it to its member's;
+//   one loop per output shape (set_eval_loop, set_proxy_loop) over any binding: an id outside [0, n_mat) is an inactive hit, +0 in every
+//   output and nothing read;
+//   one entry per output shape (set_eval, set_evalp_is_proxy, set_evalp_pdf) with the argument checks, behind the sets' and scenes' calls.
 // a member belongs to the set's context (`what`: "merl" / "utia" / "model"); whether it is of the set's kind is each set's own test
 static djb_status set_member_check(const djb_ctx *ctx, const djb_brdf *b, int index, const char *what)
 {
@@ -987,45 +982,186 @@ static djb_status set_batch_head(int64_t n, const int32_t *material)
 	if (!material) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null material array");
 	return DJB_OK;
 }
-static djb_status set_batch_args(int64_t n, const int32_t *material, const djb_vec3_view *i, const djb_vec3_view *o, const djb_vec3_view *out)
+// no_out: what a missing output view is called -- "null output vec3 view" by the eval entries, the model sets' and the scenes' light
+// sample, "null output" by the MERL sets' light sample
+static djb_status set_batch_args(int64_t n, const int32_t *material, const djb_vec3_view *i, const djb_vec3_view *o, const djb_vec3_view *out,
+                                 const char *no_out = "djb_error: null output vec3 view")
 {
 	djb_status st = set_batch_head(n, material);
 	if (st != DJB_OK) return st;
 	if (!valid(i) || !valid(o)) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null vec3 view");
-	if (!valid(out)) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null output vec3 view");
+	if (!valid(out)) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, no_out);
 	return DJB_OK;
 }
-// bind(tb, m): point the lane's Brdf at material m
-template <int KIND, int WANT, typename Bind>
-void set_eval_loop(int n_mat, long long k0, long long k1, const int32_t *material, const View &vi, const View &vo, const View &vout, Bind bind)
-{
-	Brdf tb; memset(&tb, 0, sizeof tb); tb.kind = KIND;
-	Params tp; memset(&tp, 0, sizeof tp);
-	for (long long k = k0; k < k1; ++k) {
+
+// ---- material bindings.  One object per parallel_for range, copied from the call's.  bind(m) points the target at material m;
+// eval<WANT> and hit<PK, LIGHT> (the arguments of proxy_hit; `lobe`: the call's ggx or beckmann object, of kind PK) bind and run one hit
+struct MatTarget {
+	Brdf tb; Params tp;
+	explicit MatTarget(int kind) { memset(&tb, 0, sizeof tb); tb.kind = kind; memset(&tp, 0, sizeof tp); }
+	template <int KIND, int WANT> v3 eval_bound(v3 i, v3 o) const
+	{
 		v3 fr = mk(0, 0, 0); float unused_pdf = 0.0f;
-		const unsigned int m = (unsigned int)material[k];
-		if (m < (unsigned int)n_mat) {
-			bind(tb, m);
-			eval_one<KIND, WANT>(tb, tp, load3(vi, k), load3(vo, k), fr, unused_pdf);
+		eval_one<KIND, WANT>(tb, tp, i, o, fr, unused_pdf);
+		return fr;
+	}
+};
+// MERL and UTIA sets: tables = MerlTexel[n_mat][MERL_N] or float4[n_mat][288 * 288 * 8]; the proxy is the call's lobe with params[m]
+// (Params[n_mat], not read by eval)
+template <int KIND> struct TableMat : MatTarget {
+	const void *tables; const Params *params;
+	TableMat(const void *tables, const void *params) : MatTarget(KIND), tables(tables), params((const Params *)params) {}
+	void bind(unsigned int m)
+	{
+		if (KIND == KIND_MERL) tb.merl = (const MerlTexel *)tables + (size_t)m * (size_t)MERL_N;
+		else tb.utia = (const float4 *)tables + (size_t)m * 8 * (size_t)(UTIA_N / 3);
+	}
+	template <int WANT> v3 eval(unsigned int m, v3 i, v3 o) { bind(m); return eval_bound<KIND, WANT>(i, o); }
+	template <int PK, bool LIGHT> void hit(unsigned int m, const Brdf &lobe, float u1, float u2, v3 o, const GlibcTabs &gt, v3 &i, v3 &fr, float &pdf)
+	{
+		bind(m);
+		proxy_hit<PK, KIND, LIGHT>(tb, tp, lobe, params[m], u1, u2, o, gt, i, fr, pdf);
+	}
+};
+// row m of double[n_mat][33 or 9] becomes the Brdf's `model`, with create_model's Fresnel operands for it
+template <int KIND> static void bind_model_row(Brdf &tb, const double *rows, unsigned int m)
+{
+	const double *row = rows + (size_t)m * (KIND == KIND_SGD ? 33 : 9);
+	tb.model = row; tb.fr.kind = KIND == KIND_SGD ? FR_SGD : FR_UNPOLARIZED;
+	if (KIND == KIND_SGD) for (int c = 0; c < 3; ++c) { tb.fr.a[c] = (float)row[12 + c]; tb.fr.b[c] = (float)row[15 + c]; }
+	else for (int c = 0; c < 3; ++c) tb.fr.a[c] = (float)row[8];
+}
+// SGD / ABC sets: rows = double[n_mat][33 or 9].  The proxy is the material's own fitted lobe with params::standard(): block =
+// float[n_mat][3][res] -- p22, sigma, qf of tabular(model_m, res, shadow) -- then int n_qf[n_mat] (model_set_fit_proxy; not read by eval)
+template <int KIND> struct ModelMat : MatTarget {
+	const double *rows; const float *block; const int *n_qf; size_t res;
+	Brdf pb; Params pp;
+	ModelMat(const double *rows, int n_mat = 0, const float *block = nullptr, int res = 0, int shadow = 0)
+		: MatTarget(KIND), rows(rows), block(block), n_qf(block ? (const int *)(block + 3 * (size_t)n_mat * (size_t)res) : nullptr), res((size_t)res)
+	{
+		memset(&pb, 0, sizeof pb); pb.kind = KIND_TABULAR; pb.shadow = shadow != 0; pb.n_p22 = pb.n_sigma = res;
+		(void)params_for(nullptr, KIND_TABULAR, &pp);                                   // params::standard(): never refused
+	}
+	void bind(unsigned int m) { bind_model_row<KIND>(tb, rows, m); }
+	template <int WANT> v3 eval(unsigned int m, v3 i, v3 o) { bind(m); return eval_bound<KIND, WANT>(i, o); }
+	template <int PK, bool LIGHT> void hit(unsigned int m, const Brdf &, float u1, float u2, v3 o, const GlibcTabs &gt, v3 &i, v3 &fr, float &pdf)
+	{
+		const float *tab = block + 3 * (size_t)m * res;
+		pb.p22 = tab; pb.sigma = tab + res; pb.qf = tab + 2 * res; pb.n_qf = n_qf[m];
+		bind(m);
+		proxy_hit<KIND_TABULAR, KIND, LIGHT>(tb, tp, pb, pp, u1, u2, o, gt, i, fr, pdf);
+	}
+};
+// Scenes: slots = n_slots packed words (kind code 0 merl, 1 utia, 2 sgd, 3 abc in the high 16 bits, the local id in the low 16; anything
+// else: no material), validated by djb_scene_create.  m is the hit's scene id, inside the table; the hit goes to its member's binding with
+// its local id.  A slot without material: the outputs stay as the loop preset them, +0, and nothing is read
+struct SceneMat {
+	const unsigned int *slots;
+	TableMat<KIND_MERL> merl; TableMat<KIND_UTIA> utia; ModelMat<KIND_SGD> sgd; ModelMat<KIND_ABC> abc;
+	explicit SceneMat(const SceneHost &S)
+		: slots(S.slots), merl(S.merl_texels, S.merl_params), utia(S.utia_records, S.utia_params),
+		  sgd(S.sgd_rows, S.n_sgd, S.sgd_block, S.sgd_res, S.sgd_shadow), abc(S.abc_rows, S.n_abc, S.abc_block, S.abc_res, S.abc_shadow) {}
+	template <int WANT> v3 eval(unsigned int m, v3 i, v3 o)
+	{
+		const unsigned int slot = slots[m], local = slot & 0xffffu;
+		switch (slot >> 16) {
+		case 0: return merl.eval<WANT>(local, i, o);
+		case 1: return utia.eval<WANT>(local, i, o);
+		case 2: return sgd.eval<WANT>(local, i, o);
+		case 3: return abc.eval<WANT>(local, i, o);
 		}
-		store3(vout, k, fr);
+		return mk(0, 0, 0);
+	}
+	template <int PK, bool LIGHT> void hit(unsigned int m, const Brdf &lobe, float u1, float u2, v3 o, const GlibcTabs &gt, v3 &i, v3 &fr, float &pdf)
+	{
+		const unsigned int slot = slots[m], local = slot & 0xffffu;
+		switch (slot >> 16) {
+		case 0: merl.hit<PK, LIGHT>(local, lobe, u1, u2, o, gt, i, fr, pdf); break;
+		case 1: utia.hit<PK, LIGHT>(local, lobe, u1, u2, o, gt, i, fr, pdf); break;
+		case 2: sgd.hit<PK, LIGHT>(local, lobe, u1, u2, o, gt, i, fr, pdf); break;
+		case 3: abc.hit<PK, LIGHT>(local, lobe, u1, u2, o, gt, i, fr, pdf); break;
+		}
+	}
+};
+
+// ---- eval / evalp per hit
+template <int WANT, class Mat>
+void set_eval_loop(Mat M, int n_mat, long long k0, long long k1, const int32_t *material, const View &vi, const View &vo, const View &vout)
+{
+	for (long long k = k0; k < k1; ++k) {
+		const unsigned int m = (unsigned int)material[k];
+		store3(vout, k, m < (unsigned int)n_mat ? M.template eval<WANT>(m, load3(vi, k), load3(vo, k)) : mk(0, 0, 0));
 	}
 }
-template <int KIND, typename Bind>
-djb_status set_eval(djb_ctx *ctx, int n_mat, int64_t n, const int32_t *material, const djb_vec3_view *i, const djb_vec3_view *o, int want_cos,
-                    const djb_vec3_view *out_fr, Bind bind)
+template <class Mat>
+djb_status set_eval(djb_ctx *ctx, const Mat &M, int n_mat, int64_t n, const int32_t *material, const djb_vec3_view *i, const djb_vec3_view *o,
+                    int want_cos, const djb_vec3_view *out_fr)
 {
 	djb_status st = set_batch_args(n, material, i, o, out_fr);
 	if (st != DJB_OK) return st;
 	const View vi = view_of(i), vo = view_of(o), vout = view_of(out_fr);
 	parallel_for(C(ctx), n, 4096, [&](long long k0, long long k1) {
-		if (want_cos) set_eval_loop<KIND, 2>(n_mat, k0, k1, material, vi, vo, vout, bind);
-		else set_eval_loop<KIND, 1>(n_mat, k0, k1, material, vi, vo, vout, bind);
+		if (want_cos) set_eval_loop<2>(M, n_mat, k0, k1, material, vi, vo, vout);
+		else set_eval_loop<1>(M, n_mat, k0, k1, material, vi, vo, vout);
 	});
 	return DJB_OK;
 }
 
-// MERL sets: texels = MerlTexel[n_mat][MERL_N]
+// ---- the two proxy steps per hit.  LIGHT: va = i, outputs fr and pdf; else va is not read, u1a / u2a are, outputs weight (vfr), i and pdf
+template <int PK, bool LIGHT, class Mat>
+void set_proxy_loop(Mat M, int n_mat, const Brdf &lobe, long long k0, long long k1, const int32_t *material, const float *u1a, const float *u2a,
+                    const View &va, const View &vo, const View &vfr, const View &vi_out, float *out_pdf)
+{
+	const GlibcTabs gt = glibc_tabs_global();
+	for (long long k = k0; k < k1; ++k) {
+		v3 fr = mk(0, 0, 0), i_ = mk(0, 0, 0); float pdf = 0.0f;
+		const unsigned int m = (unsigned int)material[k];
+		if (m < (unsigned int)n_mat) {
+			if (LIGHT) i_ = load3(va, k);
+			M.template hit<PK, LIGHT>(m, lobe, LIGHT ? 0.0f : u1a[k], LIGHT ? 0.0f : u2a[k], load3(vo, k), gt, i_, fr, pdf);
+		}
+		store3(vfr, k, fr);
+		if (!LIGHT) store3(vi_out, k, i_);
+		out_pdf[k] = pdf;
+	}
+}
+// proxy: checked by the caller (djb_merl_set.hip, djb_scene.hip) but for its context -- a ggx or beckmann object; NULL where no hit reads a
+// lobe (a model set, a scene of model members alone).  `what`: "merl set" / "scene"
+template <bool LIGHT, class Mat>
+static djb_status set_proxy_run(djb_ctx *ctx, const Mat &M, int n_mat, const djb_brdf *proxy, const char *what, int64_t n, const int32_t *material,
+                                const float *u1, const float *u2, const View &va, const View &vo, const View &vfr, const View &vi_out, float *out_pdf)
+{
+	if (proxy && B(proxy)->ctx != C(ctx)) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: %s and proxy belong to different contexts", what);
+	Brdf none; memset(&none, 0, sizeof none); none.kind = KIND_GGX;
+	const Brdf &lobe = proxy ? B(proxy)->dev : none;
+	parallel_for(C(ctx), n, 2048, [&](long long k0, long long k1) {
+		if (lobe.kind == KIND_GGX) set_proxy_loop<KIND_GGX, LIGHT>(M, n_mat, lobe, k0, k1, material, u1, u2, va, vo, vfr, vi_out, out_pdf);
+		else set_proxy_loop<KIND_BECKMANN, LIGHT>(M, n_mat, lobe, k0, k1, material, u1, u2, va, vo, vfr, vi_out, out_pdf);
+	});
+	return DJB_OK;
+}
+template <class Mat>
+static djb_status set_evalp_is_proxy(djb_ctx *ctx, const Mat &M, int n_mat, const djb_brdf *proxy, const char *what, int64_t n, const int32_t *material,
+                                     const float *u1, const float *u2, const djb_vec3_view *o, const djb_vec3_view *out_w, const djb_vec3_view *out_i,
+                                     float *out_pdf)
+{
+	djb_status st = set_batch_head(n, material);
+	if (st != DJB_OK) return st;
+	if (!u1 || !u2 || !valid(o) || !valid(out_w) || !valid(out_i) || !out_pdf) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null argument");
+	return set_proxy_run<false>(ctx, M, n_mat, proxy, what, n, material, u1, u2, NO_VIEW, view_of(o), view_of(out_w), view_of(out_i), out_pdf);
+}
+template <class Mat>
+static djb_status set_evalp_pdf(djb_ctx *ctx, const Mat &M, int n_mat, const djb_brdf *proxy, const char *what, int64_t n, const int32_t *material,
+                                const djb_vec3_view *i, const djb_vec3_view *o, const djb_vec3_view *out_fr, float *out_pdf,
+                                const char *no_out = "djb_error: null output vec3 view")
+{
+	djb_status st = set_batch_args(n, material, i, o, out_fr, no_out);
+	if (st != DJB_OK) return st;
+	if (!out_pdf) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null output");
+	return set_proxy_run<true>(ctx, M, n_mat, proxy, what, n, material, nullptr, nullptr, view_of(i), view_of(o), view_of(out_fr), NO_VIEW, out_pdf);
+}
+
+// ---- MERL sets
 djb_status merl_set_member(const djb_ctx *ctx, const djb_brdf *b, int index, const void **texels)
 {
 	djb_status st = set_member_check(ctx, b, index, "merl");
@@ -1042,11 +1178,21 @@ djb_status merl_set_resolve_params(const djb_params *in, void *out_params)
 djb_status merl_set_eval(djb_ctx *ctx, const void *texels, int n_mat, int64_t n, const int32_t *material, const djb_vec3_view *i,
                          const djb_vec3_view *o, int want_cos, const djb_vec3_view *out_fr)
 {
-	const MerlTexel *tex = (const MerlTexel *)texels;
-	return set_eval<KIND_MERL>(ctx, n_mat, n, material, i, o, want_cos, out_fr,
-	                           [tex](Brdf &tb, unsigned int m) { tb.merl = tex + (size_t)m * (size_t)MERL_N; });
+	return set_eval(ctx, TableMat<KIND_MERL>(texels, nullptr), n_mat, n, material, i, o, want_cos, out_fr);
 }
-// UTIA sets: records = float4[n_mat][288 * 288 * 8]
+djb_status merl_set_evalp_is_proxy(djb_ctx *ctx, const void *texels, const void *params, int n_mat, const djb_brdf *proxy, int64_t n,
+                                   const int32_t *material, const float *u1, const float *u2, const djb_vec3_view *o,
+                                   const djb_vec3_view *out_w, const djb_vec3_view *out_i, float *out_pdf)
+{
+	return set_evalp_is_proxy(ctx, TableMat<KIND_MERL>(texels, params), n_mat, proxy, "merl set", n, material, u1, u2, o, out_w, out_i, out_pdf);
+}
+djb_status merl_set_evalp_pdf(djb_ctx *ctx, const void *texels, const void *params, int n_mat, const djb_brdf *proxy, int64_t n,
+                              const int32_t *material, const djb_vec3_view *i, const djb_vec3_view *o, const djb_vec3_view *out_fr,
+                              float *out_pdf)
+{
+	return set_evalp_pdf(ctx, TableMat<KIND_MERL>(texels, params), n_mat, proxy, "merl set", n, material, i, o, out_fr, out_pdf, "djb_error: null output");
+}
+// ---- UTIA sets
 djb_status utia_set_member(const djb_ctx *ctx, const djb_brdf *b, int index, const void **records)
 {
 	djb_status st = set_member_check(ctx, b, index, "utia");
@@ -1059,11 +1205,9 @@ djb_status utia_set_member(const djb_ctx *ctx, const djb_brdf *b, int index, con
 djb_status utia_set_eval(djb_ctx *ctx, const void *records, int n_mat, int64_t n, const int32_t *material, const djb_vec3_view *i,
                          const djb_vec3_view *o, int want_cos, const djb_vec3_view *out_fr)
 {
-	const float4 *tab = (const float4 *)records;
-	return set_eval<KIND_UTIA>(ctx, n_mat, n, material, i, o, want_cos, out_fr,
-	                           [tab](Brdf &tb, unsigned int m) { tb.utia = tab + (size_t)m * 8 * (size_t)(UTIA_N / 3); });
+	return set_eval(ctx, TableMat<KIND_UTIA>(records, nullptr), n_mat, n, material, i, o, want_cos, out_fr);
 }
-// SGD / ABC sets: rows = double[n_mat][33 or 9]; the Brdf's `model` is the hit's row and its Fresnel operands are create_model's for that row
+// ---- SGD / ABC sets
 djb_status model_set_member(const djb_ctx *ctx, const djb_brdf *b, int index, int *kind, const double **row)
 {
 	djb_status st = set_member_check(ctx, b, index, "model");
@@ -1075,60 +1219,14 @@ djb_status model_set_member(const djb_ctx *ctx, const djb_brdf *b, int index, in
 	*row = B(b)->model.data();
 	return DJB_OK;
 }
-// row m of double[n_mat][33 or 9] becomes the Brdf's `model`, with create_model's Fresnel operands for it
-template <int KIND> static void bind_model_row(Brdf &tb, const double *rows, unsigned int m)
-{
-	const double *row = rows + (size_t)m * (KIND == KIND_SGD ? 33 : 9);
-	tb.model = row; tb.fr.kind = KIND == KIND_SGD ? FR_SGD : FR_UNPOLARIZED;
-	if (KIND == KIND_SGD) for (int c = 0; c < 3; ++c) { tb.fr.a[c] = (float)row[12 + c]; tb.fr.b[c] = (float)row[15 + c]; }
-	else for (int c = 0; c < 3; ++c) tb.fr.a[c] = (float)row[8];
-}
 djb_status model_set_eval(djb_ctx *ctx, int kind, const double *rows, int n_mat, int64_t n, const int32_t *material, const djb_vec3_view *i,
                           const djb_vec3_view *o, int want_cos, const djb_vec3_view *out_fr)
 {
-	if (kind == KIND_SGD)
-		return set_eval<KIND_SGD>(ctx, n_mat, n, material, i, o, want_cos, out_fr, [rows](Brdf &tb, unsigned int m) { bind_model_row<KIND_SGD>(tb, rows, m); });
-	return set_eval<KIND_ABC>(ctx, n_mat, n, material, i, o, want_cos, out_fr, [rows](Brdf &tb, unsigned int m) { bind_model_row<KIND_ABC>(tb, rows, m); });
+	if (kind == KIND_SGD) return set_eval(ctx, ModelMat<KIND_SGD>(rows), n_mat, n, material, i, o, want_cos, out_fr);
+	return set_eval(ctx, ModelMat<KIND_ABC>(rows), n_mat, n, material, i, o, want_cos, out_fr);
 }
-// Scenes: slots = n_slots packed words (kind code 0 merl, 1 utia, 2 sgd, 3 abc in the high 16 bits, the local id in the low 16; anything
-// else: no material), validated by djb_scene_create.  Each hit is classified through the table and handed, alone, to set_eval_loop with its
-// member's binding: the per-hit code the three sets run.  A hit outside the table or on a slot without material: +0, nothing read
-template <int WANT>
-static void scene_eval_loop(const unsigned int *slots, int n_slots, const MerlTexel *tex, const float4 *tab, const double *sgd, const double *abc,
-                            long long k0, long long k1, const int32_t *material, const View &vi, const View &vo, const View &vout)
-{
-	auto at = [](const View &v, long long k) { return View{ v.x + k * v.stride, v.y + k * v.stride, v.z + k * v.stride, v.stride }; };
-	for (long long k = k0; k < k1; ++k) {
-		const unsigned int raw = (unsigned int)material[k];
-		const unsigned int slot = raw < (unsigned int)n_slots ? slots[raw] : 0xffffffffu;
-		const int32_t local = (int32_t)(slot & 0xffffu);
-		const View i1 = at(vi, k), o1 = at(vo, k), out1 = at(vout, k);
-		switch (slot >> 16) {
-		case 0: set_eval_loop<KIND_MERL, WANT>(65536, 0, 1, &local, i1, o1, out1, [tex](Brdf &tb, unsigned int m) { tb.merl = tex + (size_t)m * (size_t)MERL_N; }); break;
-		case 1: set_eval_loop<KIND_UTIA, WANT>(65536, 0, 1, &local, i1, o1, out1, [tab](Brdf &tb, unsigned int m) { tb.utia = tab + (size_t)m * 8 * (size_t)(UTIA_N / 3); }); break;
-		case 2: set_eval_loop<KIND_SGD, WANT>(65536, 0, 1, &local, i1, o1, out1, [sgd](Brdf &tb, unsigned int m) { bind_model_row<KIND_SGD>(tb, sgd, m); }); break;
-		case 3: set_eval_loop<KIND_ABC, WANT>(65536, 0, 1, &local, i1, o1, out1, [abc](Brdf &tb, unsigned int m) { bind_model_row<KIND_ABC>(tb, abc, m); }); break;
-		default: store3(vout, k, mk(0, 0, 0));
-		}
-	}
-}
-djb_status scene_eval(djb_ctx *ctx, const unsigned int *slots, int n_slots, const void *merl_texels, const void *utia_records, const double *sgd_rows,
-                      const double *abc_rows, int64_t n, const int32_t *material, const djb_vec3_view *i, const djb_vec3_view *o, int want_cos,
-                      const djb_vec3_view *out_fr)
-{
-	djb_status st = set_batch_args(n, material, i, o, out_fr);
-	if (st != DJB_OK) return st;
-	const MerlTexel *tex = (const MerlTexel *)merl_texels;
-	const float4 *tab = (const float4 *)utia_records;
-	const View vi = view_of(i), vo = view_of(o), vout = view_of(out_fr);
-	parallel_for(C(ctx), n, 4096, [&](long long k0, long long k1) {
-		if (want_cos) scene_eval_loop<2>(slots, n_slots, tex, tab, sgd_rows, abc_rows, k0, k1, material, vi, vo, vout);
-		else scene_eval_loop<1>(slots, n_slots, tex, tab, sgd_rows, abc_rows, k0, k1, material, vi, vo, vout);
-	});
-	return DJB_OK;
-}
-// the fitted tabular proxies of a model set (djb_model_set_fit_proxy): block = float[n_mat][3][res] -- p22, sigma, qf of tabular(model_m, res,
-// shadow) one after the other -- then int n_qf[n_mat]; each material fitted as create_tabular fits the single object
+// the fitted tabular proxies of a model set (djb_model_set_fit_proxy): the block ModelMat reads, each material fitted as create_tabular fits
+// the single object
 djb_status model_set_fit_proxy(djb_ctx *ctx, int kind, const double *rows, int n_mat, int res, int shadow, float *block)
 {
 	if (res <= 2) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: Invalid Resolution");   // dj_brdf.h:2218
@@ -1151,236 +1249,36 @@ djb_status model_set_fit_proxy(djb_ctx *ctx, int kind, const double *rows, int n
 	});
 	return DJB_OK;
 }
-// the two per-hit steps against those proxies: proxy_loop / proxy_light_loop above per hit with target = model(row_m), proxy = the tabular
-// lobe of material m and params::standard() for it; an inactive hit is +0 in every output, and so is a light-sample hit below the horizon
-// LIGHT: a = i (given), outputs fr and pdf; else a is not read, u1a / u2a are, outputs weight, i and pdf
-template <int KIND, bool LIGHT>
-void model_set_proxy_loop(const double *rows, int n_mat, const float *block, int res, int shadow, const Params &pp, long long k0, long long k1,
-                          const int32_t *material, const float *u1a, const float *u2a, const View &va, const View &vo, const View &vfr,
-                          const View &vi_out, float *out_pdf)
-{
-	const GlibcTabs gt = glibc_tabs_global();
-	const int *n_qf = (const int *)(block + 3 * (size_t)n_mat * (size_t)res);
-	Brdf tb; memset(&tb, 0, sizeof tb); tb.kind = KIND;
-	Brdf pb; memset(&pb, 0, sizeof pb); pb.kind = KIND_TABULAR; pb.shadow = shadow != 0; pb.n_p22 = pb.n_sigma = res;
-	Params tp; memset(&tp, 0, sizeof tp);
-	for (long long k = k0; k < k1; ++k) {
-		v3 fr = mk(0, 0, 0), i_ = mk(0, 0, 0); float pdf = 0.0f;
-		const unsigned int m = (unsigned int)material[k];
-		if (m < (unsigned int)n_mat) {
-			const v3 o = load3(vo, k);
-			if (LIGHT) i_ = load3(va, k);
-			if (!LIGHT || !(i_.z <= 0.0f || o.z <= 0.0f)) {                             // the light sample's guard reads neither row nor table
-				const float *tab = block + 3 * (size_t)m * (size_t)res;
-				pb.p22 = tab; pb.sigma = tab + res; pb.qf = tab + 2 * (size_t)res; pb.n_qf = n_qf[m];
-				v3 unused_w; float unused_pdf;
-				if (!LIGHT) sample_one<KIND_TABULAR, false>(pb, pp, u1a[k], u2a[k], o, gt, i_, unused_w, unused_pdf);
-				if (LIGHT || !(i_.z <= 0.0f)) {                                         // the plugins' side check; a NaN i.z passes
-					v3 unused_fr = mk(0, 0, 0);
-					bind_model_row<KIND>(tb, rows, m);
-					eval_one<KIND_TABULAR, 4>(pb, pp, i_, o, unused_fr, pdf);
-					eval_one<KIND, 2>(tb, tp, i_, o, fr, unused_pdf);
-					if (!LIGHT) fr = divs(fr, pdf);
-				}
-			}
-		}
-		store3(vfr, k, fr); out_pdf[k] = pdf;
-		if (!LIGHT) store3(vi_out, k, i_);
-	}
-}
-template <bool LIGHT>
-static djb_status model_set_proxy_run(djb_ctx *ctx, int kind, const double *rows, int n_mat, const float *block, int res, int shadow, int64_t n,
-                                      const int32_t *material, const float *u1, const float *u2, const View &va, const View &vo, const View &vfr,
-                                      const View &vi_out, float *out_pdf)
-{
-	Params pp;
-	djb_status st = params_for(nullptr, KIND_TABULAR, &pp);
-	if (st != DJB_OK) return st;
-	parallel_for(C(ctx), n, 2048, [&](long long k0, long long k1) {
-		if (kind == KIND_SGD) model_set_proxy_loop<KIND_SGD, LIGHT>(rows, n_mat, block, res, shadow, pp, k0, k1, material, u1, u2, va, vo, vfr, vi_out, out_pdf);
-		else model_set_proxy_loop<KIND_ABC, LIGHT>(rows, n_mat, block, res, shadow, pp, k0, k1, material, u1, u2, va, vo, vfr, vi_out, out_pdf);
-	});
-	return DJB_OK;
-}
 djb_status model_set_evalp_is_proxy(djb_ctx *ctx, int kind, const double *rows, int n_mat, const float *block, int res, int shadow, int64_t n,
                                     const int32_t *material, const float *u1, const float *u2, const djb_vec3_view *o, const djb_vec3_view *out_w,
                                     const djb_vec3_view *out_i, float *out_pdf)
 {
-	djb_status st = set_batch_head(n, material);
-	if (st != DJB_OK) return st;
-	if (!u1 || !u2 || !valid(o) || !valid(out_w) || !valid(out_i) || !out_pdf) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null argument");
-	const View none = { nullptr, nullptr, nullptr, 0 };
-	return model_set_proxy_run<false>(ctx, kind, rows, n_mat, block, res, shadow, n, material, u1, u2, none, view_of(o), view_of(out_w), view_of(out_i), out_pdf);
+	if (kind == KIND_SGD)
+		return set_evalp_is_proxy(ctx, ModelMat<KIND_SGD>(rows, n_mat, block, res, shadow), n_mat, nullptr, "model set", n, material, u1, u2, o, out_w, out_i, out_pdf);
+	return set_evalp_is_proxy(ctx, ModelMat<KIND_ABC>(rows, n_mat, block, res, shadow), n_mat, nullptr, "model set", n, material, u1, u2, o, out_w, out_i, out_pdf);
 }
 djb_status model_set_evalp_pdf(djb_ctx *ctx, int kind, const double *rows, int n_mat, const float *block, int res, int shadow, int64_t n,
                                const int32_t *material, const djb_vec3_view *i, const djb_vec3_view *o, const djb_vec3_view *out_fr, float *out_pdf)
 {
-	djb_status st = set_batch_args(n, material, i, o, out_fr);
-	if (st != DJB_OK) return st;
-	if (!out_pdf) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null output");
-	const View none = { nullptr, nullptr, nullptr, 0 };
-	return model_set_proxy_run<true>(ctx, kind, rows, n_mat, block, res, shadow, n, material, nullptr, nullptr, view_of(i), view_of(o), view_of(out_fr), none, out_pdf);
+	if (kind == KIND_SGD)
+		return set_evalp_pdf(ctx, ModelMat<KIND_SGD>(rows, n_mat, block, res, shadow), n_mat, nullptr, "model set", n, material, i, o, out_fr, out_pdf);
+	return set_evalp_pdf(ctx, ModelMat<KIND_ABC>(rows, n_mat, block, res, shadow), n_mat, nullptr, "model set", n, material, i, o, out_fr, out_pdf);
 }
-// the two MERL-set proxy loops: proxy_loop / proxy_light_loop above per hit, the table and the proxy's parameters selected by the hit's id
-template <int PK>
-void merl_set_proxy_loop(const MerlTexel *tex, const Params *params, int n_mat, const Brdf &pb, long long k0, long long k1, const int32_t *material,
-                         const float *u1a, const float *u2a, const View &vo, const View &vw_out, const View &vi_out, float *out_pdf)
+// ---- scenes: a hit outside the slot table is an inactive hit
+djb_status scene_eval(djb_ctx *ctx, const SceneHost &S, int64_t n, const int32_t *material, const djb_vec3_view *i, const djb_vec3_view *o,
+                      int want_cos, const djb_vec3_view *out_fr)
 {
-	const GlibcTabs gt = glibc_tabs_global();
-	Brdf tb; memset(&tb, 0, sizeof tb); tb.kind = KIND_MERL;
-	Params tp; memset(&tp, 0, sizeof tp);
-	for (long long k = k0; k < k1; ++k) {
-		v3 i_ = mk(0, 0, 0), w = mk(0, 0, 0); float pdf = 0.0f;
-		const unsigned int m = (unsigned int)material[k];
-		if (m < (unsigned int)n_mat) {
-			const Params &pp = params[m];
-			const v3 o = load3(vo, k);
-			v3 unused_w; float unused_pdf;
-			tb.merl = tex + (size_t)m * (size_t)MERL_N;
-			sample_one<PK, false>(pb, pp, u1a[k], u2a[k], o, gt, i_, unused_w, unused_pdf);
-			if (!(i_.z <= 0.0f)) {                                                      // the plugins' side check; a NaN i.z passes
-				v3 fr = mk(0, 0, 0), unused_fr = mk(0, 0, 0);
-				eval_one<PK, 4>(pb, pp, i_, o, unused_fr, pdf);
-				eval_one<KIND_MERL, 2>(tb, tp, i_, o, fr, unused_pdf);
-				w = divs(fr, pdf);
-			}
-		}
-		store3(vw_out, k, w); store3(vi_out, k, i_); out_pdf[k] = pdf;
-	}
+	return set_eval(ctx, SceneMat(S), S.n_slots, n, material, i, o, want_cos, out_fr);
 }
-djb_status merl_set_evalp_is_proxy(djb_ctx *ctx, const void *texels, const void *params_, int n_mat, const djb_brdf *proxy, int64_t n,
-                                   const int32_t *material, const float *u1, const float *u2, const djb_vec3_view *o,
-                                   const djb_vec3_view *out_w, const djb_vec3_view *out_i, float *out_pdf)
-{
-	djb_status st = set_batch_head(n, material);
-	if (st != DJB_OK) return st;
-	if (!u1 || !u2 || !valid(o) || !valid(out_w) || !valid(out_i) || !out_pdf) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null argument");
-	if (B(proxy)->ctx != C(ctx)) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: merl set and proxy belong to different contexts");
-	const Brdf &pb = B(proxy)->dev;
-	const View vo = view_of(o), vw = view_of(out_w), vi = view_of(out_i);
-	const MerlTexel *tex = (const MerlTexel *)texels;
-	const Params *params = (const Params *)params_;
-	parallel_for(C(ctx), n, 2048, [&](long long k0, long long k1) {
-		if (pb.kind == KIND_GGX) merl_set_proxy_loop<KIND_GGX>(tex, params, n_mat, pb, k0, k1, material, u1, u2, vo, vw, vi, out_pdf);
-		else merl_set_proxy_loop<KIND_BECKMANN>(tex, params, n_mat, pb, k0, k1, material, u1, u2, vo, vw, vi, out_pdf);
-	});
-	return DJB_OK;
-}
-
-// the light sample: evalp of the hit's table and the proxy's pdf with the hit's parameters for a given pair; dj_merl's guard
-// (cosTheta(wi) <= 0 || cosTheta(wo) <= 0 -> 0, a NaN z evaluated) applied to both
-template <int PK>
-void merl_set_light_loop(const MerlTexel *tex, const Params *params, int n_mat, const Brdf &pb, long long k0, long long k1, const int32_t *material,
-                         const View &vi, const View &vo, const View &vout, float *out_pdf)
-{
-	Brdf tb; memset(&tb, 0, sizeof tb); tb.kind = KIND_MERL;
-	Params tp; memset(&tp, 0, sizeof tp);
-	for (long long k = k0; k < k1; ++k) {
-		v3 fr = mk(0, 0, 0); float pdf = 0.0f;
-		const unsigned int m = (unsigned int)material[k];
-		if (m < (unsigned int)n_mat) {
-			const v3 i = load3(vi, k), o = load3(vo, k);
-			if (!(i.z <= 0.0f || o.z <= 0.0f)) {
-				v3 unused_fr = mk(0, 0, 0); float unused_pdf = 0.0f;
-				tb.merl = tex + (size_t)m * (size_t)MERL_N;
-				eval_one<PK, 4>(pb, params[m], i, o, unused_fr, pdf);
-				eval_one<KIND_MERL, 2>(tb, tp, i, o, fr, unused_pdf);
-			}
-		}
-		store3(vout, k, fr); out_pdf[k] = pdf;
-	}
-}
-djb_status merl_set_evalp_pdf(djb_ctx *ctx, const void *texels, const void *params_, int n_mat, const djb_brdf *proxy, int64_t n,
-                              const int32_t *material, const djb_vec3_view *i, const djb_vec3_view *o, const djb_vec3_view *out_fr,
-                              float *out_pdf)
-{
-	djb_status st = set_batch_head(n, material);
-	if (st != DJB_OK) return st;
-	if (!valid(i) || !valid(o)) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null vec3 view");
-	if (!valid(out_fr) || !out_pdf) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null output");
-	if (B(proxy)->ctx != C(ctx)) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: merl set and proxy belong to different contexts");
-	const Brdf &pb = B(proxy)->dev;
-	const View vi = view_of(i), vo = view_of(o), vout = view_of(out_fr);
-	const MerlTexel *tex = (const MerlTexel *)texels;
-	const Params *params = (const Params *)params_;
-	parallel_for(C(ctx), n, 2048, [&](long long k0, long long k1) {
-		if (pb.kind == KIND_GGX) merl_set_light_loop<KIND_GGX>(tex, params, n_mat, pb, k0, k1, material, vi, vo, vout, out_pdf);
-		else merl_set_light_loop<KIND_BECKMANN>(tex, params, n_mat, pb, k0, k1, material, vi, vo, vout, out_pdf);
-	});
-	return DJB_OK;
-}
-
-// Scenes, the two per-hit proxy steps: each hit is classified through the slot table and handed, alone, to its member's host loop -- the MERL
-// set's, the model set's, and for utia the single-material pair (proxy_loop / proxy_light_loop) with the hit's table and Params.  LIGHT: a = i
-// (given), outputs fr and pdf; else u1a / u2a are read, outputs weight, i and pdf.  A hit outside the table or on a slot without material: +0
-template <int PK, bool LIGHT>
-static void scene_proxy_loop(const SceneProxyHost &S, const Brdf &pb, const Params &model_p, long long k0, long long k1, const int32_t *material,
-                             const float *u1a, const float *u2a, const View &va, const View &vo, const View &vfr, const View &vi_out, float *out_pdf)
-{
-	auto at = [](const View &v, long long k) { return v.x ? View{ v.x + k * v.stride, v.y + k * v.stride, v.z + k * v.stride, v.stride } : v; };
-	const MerlTexel *tex = (const MerlTexel *)S.merl_texels;
-	const float4 *tab = (const float4 *)S.utia_records;
-	const Params *merl_p = (const Params *)S.merl_params, *utia_p = (const Params *)S.utia_params;
-	Brdf tb; memset(&tb, 0, sizeof tb); tb.kind = KIND_UTIA;
-	Params tp; memset(&tp, 0, sizeof tp);
-	for (long long k = k0; k < k1; ++k) {
-		const unsigned int raw = (unsigned int)material[k];
-		const unsigned int slot = raw < (unsigned int)S.n_slots ? S.slots[raw] : 0xffffffffu;
-		const int32_t local = (int32_t)(slot & 0xffffu);
-		const View a1 = at(va, k), o1 = at(vo, k), fr1 = at(vfr, k), i1 = at(vi_out, k);
-		const float *u1 = LIGHT ? nullptr : u1a + k, *u2 = LIGHT ? nullptr : u2a + k;
-		switch (slot >> 16) {
-		case 0:
-			if (LIGHT) merl_set_light_loop<PK>(tex, merl_p, 65536, pb, 0, 1, &local, a1, o1, fr1, out_pdf + k);
-			else merl_set_proxy_loop<PK>(tex, merl_p, 65536, pb, 0, 1, &local, u1, u2, o1, fr1, i1, out_pdf + k);
-			break;
-		case 1:
-			tb.utia = tab + (size_t)local * 8 * (size_t)(UTIA_N / 3);
-			if (LIGHT) proxy_light_loop<PK, KIND_UTIA>(tb, tp, pb, utia_p[local], 0, 1, a1, o1, fr1, out_pdf + k);
-			else proxy_loop<PK, KIND_UTIA>(tb, tp, pb, utia_p[local], 0, 1, u1, u2, o1, fr1, i1, out_pdf + k);
-			break;
-		case 2: model_set_proxy_loop<KIND_SGD, LIGHT>(S.sgd_rows, S.n_sgd, S.sgd_block, S.sgd_res, S.sgd_shadow, model_p, 0, 1, &local, u1, u2, a1, o1, fr1, i1, out_pdf + k); break;
-		case 3: model_set_proxy_loop<KIND_ABC, LIGHT>(S.abc_rows, S.n_abc, S.abc_block, S.abc_res, S.abc_shadow, model_p, 0, 1, &local, u1, u2, a1, o1, fr1, i1, out_pdf + k); break;
-		default:
-			store3(vfr, k, mk(0, 0, 0)); out_pdf[k] = 0.0f;
-			if (!LIGHT) store3(vi_out, k, mk(0, 0, 0));
-		}
-	}
-}
-// proxy: checked by the caller (djb_scene.hip) -- a ggx or beckmann object of this context when the scene has a merl or utia member, else unused
-template <bool LIGHT>
-static djb_status scene_proxy_run(djb_ctx *ctx, const SceneProxyHost &S, const djb_brdf *proxy, int64_t n, const int32_t *material, const float *u1,
-                                  const float *u2, const View &va, const View &vo, const View &vfr, const View &vi_out, float *out_pdf)
-{
-	Params model_p;
-	djb_status st = params_for(nullptr, KIND_TABULAR, &model_p);
-	if (st != DJB_OK) return st;
-	if (proxy && B(proxy)->ctx != C(ctx)) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: scene and proxy belong to different contexts");
-	Brdf none; memset(&none, 0, sizeof none); none.kind = KIND_GGX;                  // a scene of model members alone: no hit reads the lobe
-	const Brdf &pb = proxy ? B(proxy)->dev : none;
-	parallel_for(C(ctx), n, 2048, [&](long long k0, long long k1) {
-		if (pb.kind == KIND_GGX) scene_proxy_loop<KIND_GGX, LIGHT>(S, pb, model_p, k0, k1, material, u1, u2, va, vo, vfr, vi_out, out_pdf);
-		else scene_proxy_loop<KIND_BECKMANN, LIGHT>(S, pb, model_p, k0, k1, material, u1, u2, va, vo, vfr, vi_out, out_pdf);
-	});
-	return DJB_OK;
-}
-djb_status scene_evalp_is_proxy(djb_ctx *ctx, const SceneProxyHost &S, const djb_brdf *proxy, int64_t n, const int32_t *material, const float *u1,
+djb_status scene_evalp_is_proxy(djb_ctx *ctx, const SceneHost &S, const djb_brdf *proxy, int64_t n, const int32_t *material, const float *u1,
                                 const float *u2, const djb_vec3_view *o, const djb_vec3_view *out_w, const djb_vec3_view *out_i, float *out_pdf)
 {
-	djb_status st = set_batch_head(n, material);
-	if (st != DJB_OK) return st;
-	if (!u1 || !u2 || !valid(o) || !valid(out_w) || !valid(out_i) || !out_pdf) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null argument");
-	const View none = { nullptr, nullptr, nullptr, 0 };
-	return scene_proxy_run<false>(ctx, S, proxy, n, material, u1, u2, none, view_of(o), view_of(out_w), view_of(out_i), out_pdf);
+	return set_evalp_is_proxy(ctx, SceneMat(S), S.n_slots, proxy, "scene", n, material, u1, u2, o, out_w, out_i, out_pdf);
 }
-djb_status scene_evalp_pdf(djb_ctx *ctx, const SceneProxyHost &S, const djb_brdf *proxy, int64_t n, const int32_t *material, const djb_vec3_view *i,
+djb_status scene_evalp_pdf(djb_ctx *ctx, const SceneHost &S, const djb_brdf *proxy, int64_t n, const int32_t *material, const djb_vec3_view *i,
                            const djb_vec3_view *o, const djb_vec3_view *out_fr, float *out_pdf)
 {
-	djb_status st = set_batch_args(n, material, i, o, out_fr);
-	if (st != DJB_OK) return st;
-	if (!out_pdf) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null output");
-	const View none = { nullptr, nullptr, nullptr, 0 };
-	return scene_proxy_run<true>(ctx, S, proxy, n, material, nullptr, nullptr, view_of(i), view_of(o), view_of(out_fr), none, out_pdf);
+	return set_evalp_pdf(ctx, SceneMat(S), S.n_slots, proxy, "scene", n, material, i, o, out_fr, out_pdf);
 }
 
 djb_status eval_pp(djb_ctx *ctx, const djb_brdf *b_, int64_t n, const djb_vec3_view *i, const djb_vec3_view *o, const float *rec,

@@ -114,23 +114,22 @@ djb_status utia_set_eval(djb_ctx *, const void *records, int n_mat, int64_t n, c
 djb_status model_set_member(const djb_ctx *ctx, const djb_brdf *b, int index, int *kind, const double **row);
 djb_status model_set_eval(djb_ctx *, int kind, const double *rows, int n_mat, int64_t n, const int32_t *material, const djb_vec3_view *i,
                           const djb_vec3_view *o, int want_cos, const djb_vec3_view *out_fr);
-// Scenes on the host (include/djb_hip.h: djb_scene).  slots: n_slots packed words (djb_internal.hpp) in host memory; the four blocks are
-// those of the member sets above, NULL for a kind the scene has no set for (no slot names it)
-djb_status scene_eval(djb_ctx *, const unsigned int *slots, int n_slots, const void *merl_texels, const void *utia_records, const double *sgd_rows,
-                      const double *abc_rows, int64_t n, const int32_t *material, const djb_vec3_view *i, const djb_vec3_view *o, int want_cos,
-                      const djb_vec3_view *out_fr);
-// ... and the two per-hit proxy steps of a scene: the blocks of the members the scene has (NULL / 0 for the others) -- the MERL and UTIA
-// tables with their resolved Params[M], the model rows with their fitted proxy blocks (model_set_fit_proxy below).  proxy: the ggx or
-// beckmann lobe of the merl and utia parts, checked by the caller; not read when the scene has neither
-struct SceneProxyHost {
+// Scenes on the host (include/djb_hip.h: djb_scene).  slots: n_slots packed words (djb_internal.hpp) in host memory; then the blocks of the
+// members the scene has (NULL / 0 for the others, no slot names them) -- the MERL and UTIA tables with their resolved Params[M], the model
+// rows with their fitted proxy blocks (model_set_fit_proxy below).  eval reads the tables and rows alone
+struct SceneHost {
 	const unsigned int *slots; int n_slots;
 	const void *merl_texels, *merl_params, *utia_records, *utia_params;
 	const double *sgd_rows; const float *sgd_block; int n_sgd, sgd_res, sgd_shadow;
 	const double *abc_rows; const float *abc_block; int n_abc, abc_res, abc_shadow;
 };
-djb_status scene_evalp_is_proxy(djb_ctx *, const SceneProxyHost &, const djb_brdf *proxy, int64_t n, const int32_t *material, const float *u1,
+djb_status scene_eval(djb_ctx *, const SceneHost &, int64_t n, const int32_t *material, const djb_vec3_view *i, const djb_vec3_view *o, int want_cos,
+                      const djb_vec3_view *out_fr);
+// ... and the two per-hit proxy steps of a scene.  proxy: the ggx or beckmann lobe of the merl and utia parts, checked by the caller; NULL
+// when the scene has neither
+djb_status scene_evalp_is_proxy(djb_ctx *, const SceneHost &, const djb_brdf *proxy, int64_t n, const int32_t *material, const float *u1,
                                 const float *u2, const djb_vec3_view *o, const djb_vec3_view *out_w, const djb_vec3_view *out_i, float *out_pdf);
-djb_status scene_evalp_pdf(djb_ctx *, const SceneProxyHost &, const djb_brdf *proxy, int64_t n, const int32_t *material, const djb_vec3_view *i,
+djb_status scene_evalp_pdf(djb_ctx *, const SceneHost &, const djb_brdf *proxy, int64_t n, const int32_t *material, const djb_vec3_view *i,
                            const djb_vec3_view *o, const djb_vec3_view *out_fr, float *out_pdf);
 // the set's fitted tabular proxies: block = float[n_mat][3][res] (p22, sigma, qf of tabular(model_m, res, shadow)) then int n_qf[n_mat], host
 // memory; and the two per-hit steps against them (evalp_is_proxy / evalp_pdf_proxy above with target = model_m, proxy = that lobe, no params)

@@ -107,20 +107,11 @@ try {
 	if (st != DJB_OK) return st;
 	if ((st = proxy_check(ctx, s, proxy, "evalp_is_proxy")) != DJB_OK) return st;
 	if (is_cpu(ctx)) return djbcpu::merl_set_evalp_is_proxy(ctx, s->tex, s->params, s->n_mat, proxy, n, material, u1, u2, o, out_weight, out_i, out_pdf);
-	if ((st = check_call(ctx, proxy, n, mem)) != DJB_OK) return st;
-	std::lock_guard<std::recursive_mutex> call_lock(ctx->call_mu);
-	Staged sg(ctx, n, mem);
-	const int32_t *dmat; View vo, vi, vw; const float *d1, *d2; float *dpdf = nullptr;
-	if ((st = stage_material(sg, material, &dmat)) != DJB_OK) return st;
-	if ((st = sg.in_f(u1, &d1)) != DJB_OK) return st;
-	if ((st = sg.in_f(u2, &d2)) != DJB_OK) return st;
-	if ((st = sg.in_vec(o, &vo)) != DJB_OK) return st;
-	if ((st = sg.out_vec(out_i, &vi)) != DJB_OK) return st;
-	if ((st = sg.out_vec(out_weight, &vw)) != DJB_OK) return st;
-	if ((st = sg.out_arr(out_pdf, &dpdf)) != DJB_OK) return st;
-	HIP_TRY(djbk::launch_merl_set_evalp_is_proxy(ctx->stream, proxy->dev, s->params, s->tex, s->n_mat, n, dmat, d1, d2, vo, vw, vi, dpdf,
+	SampleBatch c(ctx, proxy, n, mem, material, u1, u2, o, out_i, out_weight, out_pdf);
+	if (c.st != DJB_OK) return c.st;
+	HIP_TRY(djbk::launch_merl_set_evalp_is_proxy(ctx->stream, proxy->dev, s->params, s->tex, s->n_mat, n, c.dmat, c.d1, c.d2, c.vo, c.vw, c.vi, c.dpdf,
 	                                             ctx->merl_exact_only != 0));
-	return sg.finish();
+	return c.sg.finish();
 }
 DJB_ABI_CATCH
 

@@ -263,23 +263,14 @@ try {
 		return djbcpu::model_set_evalp_is_proxy(ctx, s->kind, s->rows, s->n_mat, s->proxy_host.data(), s->proxy_res, s->proxy_shadow, n, material, u1, u2,
 		                                        o, out_weight, out_i, out_pdf);
 	if (!Staged::valid(out_weight) || !Staged::valid(out_i) || !out_pdf) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null output");
-	if ((st = check_call(ctx, nullptr, n, mem)) != DJB_OK) return st;
-	std::lock_guard<std::recursive_mutex> call_lock(ctx->call_mu);
 	Params pp;
 	if ((st = device_params(nullptr, &pp, DJB_KIND_TABULAR)) != DJB_OK) return st;         // as the single-material call resolves NULL proxy params
-	Staged sg(ctx, n, mem);
-	const int32_t *dmat; View vo, vi, vw; const float *d1, *d2; float *dpdf = nullptr;
-	if ((st = stage_material(sg, material, &dmat)) != DJB_OK) return st;
-	if ((st = sg.in_f(u1, &d1)) != DJB_OK) return st;
-	if ((st = sg.in_f(u2, &d2)) != DJB_OK) return st;
-	if ((st = sg.in_vec(o, &vo)) != DJB_OK) return st;
-	if ((st = sg.out_vec(out_i, &vi)) != DJB_OK) return st;
-	if ((st = sg.out_vec(out_weight, &vw)) != DJB_OK) return st;
-	if ((st = sg.out_arr(out_pdf, &dpdf)) != DJB_OK) return st;
+	SampleBatch c(ctx, nullptr, n, mem, material, u1, u2, o, out_i, out_weight, out_pdf);
+	if (c.st != DJB_OK) return c.st;
 	const djbk::ModelSetProxy px = { s->proxy_dev, s->proxy_res, s->proxy_shadow };
-	HIP_TRY(djbk::launch_model_set_evalp_is_proxy(ctx->stream, s->kind, s->rows, s->n_mat, ctx->model_set_rows_global != 0, px, pp, n, dmat, d1, d2, vo,
-	                                              vw, vi, dpdf));
-	return sg.finish();
+	HIP_TRY(djbk::launch_model_set_evalp_is_proxy(ctx->stream, s->kind, s->rows, s->n_mat, ctx->model_set_rows_global != 0, px, pp, n, c.dmat, c.d1, c.d2,
+	                                              c.vo, c.vw, c.vi, c.dpdf));
+	return c.sg.finish();
 }
 DJB_ABI_CATCH
 

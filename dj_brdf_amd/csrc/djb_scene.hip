@@ -44,6 +44,17 @@ djb_status scene_scratch(djb_ctx *ctx, long long n, size_t wl_cap, long long *ch
 	*sc = { w, w + 16, w + 16 + tiles, w + 8, w + 16 + tiles + (size_t)mc, (unsigned int)wl_cap };
 	return DJB_OK;
 }
+// a call of n hits: launch(lo, m, sc) for the m hits from `lo` on, chunk after chunk, back to back on the context's stream
+template <class Launch> djb_status scene_chunks(djb_ctx *ctx, long long n, size_t wl_cap, Launch launch)
+{
+	if (n <= 0) return DJB_OK;
+	long long chunk;
+	djbk::SceneScratch sc;
+	djb_status st = scene_scratch(ctx, n, wl_cap, &chunk, &sc);
+	if (st != DJB_OK) return st;
+	for (long long lo = 0; lo < n; lo += chunk) HIP_TRY(launch(lo, std::min(n - lo, chunk), sc));
+	return DJB_OK;
+}
 
 // What the two proxy calls ask of the scene's MEMBERS, before anything is launched: a ggx or beckmann `proxy` of the call's context when
 // there is a merl or utia member (the text of the MERL set's proxy_check), and on every member the block its hits will read
@@ -67,9 +78,9 @@ djbk::SceneProxies proxies_of(const djb_scene *s)
 	if (s->abc) p.abc = { s->abc->proxy_dev, s->abc->proxy_res, s->abc->proxy_shadow };
 	return p;
 }
-djbcpu::SceneProxyHost proxy_host_of(const djb_scene *s)
+djbcpu::SceneHost host_of(const djb_scene *s)
 {
-	djbcpu::SceneProxyHost h = {};
+	djbcpu::SceneHost h = {};
 	h.slots = s->slots; h.n_slots = s->n_mat;
 	if (s->merl) { h.merl_texels = s->merl->tex; h.merl_params = s->merl->params; }
 	if (s->utia) { h.utia_records = s->utia->tab; h.utia_params = s->utia->params; }
@@ -150,11 +161,9 @@ try {
 	djb_status st = set_check(ctx, s, "scene");
 	if (st != DJB_OK) return st;
 	if (is_cpu(ctx))
-		return djbcpu::scene_eval(ctx, s->slots, s->n_mat, s->merl ? s->merl->tex : nullptr, s->utia ? s->utia->tab : nullptr,
-		                          s->sgd ? s->sgd->rows : nullptr, s->abc ? s->abc->rows : nullptr, n, material, i, o, want_cos, out_fr);
+		return djbcpu::scene_eval(ctx, host_of(s), n, material, i, o, want_cos, out_fr);
 	SetBatch c(ctx, nullptr, n, mem, material, i, o, out_fr);
 	if (c.st != DJB_OK) return c.st;
-	if (n <= 0) return c.sg.finish();
 	const View &vi = c.vi, &vo = c.vo, &vout = c.vout;
 	// Every lane reads its hit before it writes it and kinds touch disjoint hits, so index-aligned in-place views are supported.  The utia
 	// fix pass reads a hit again after tier 1 stored it: a device-resident caller whose outputs overlap an input stream, the ids included,
@@ -166,14 +175,10 @@ try {
 	const djbk::SceneMembers mb = members_of(s);
 	size_t cap = (size_t)(std::min<long long>(n, ctx->test_scene_chunk > 0 ? ctx->test_scene_chunk : SCENE_CHUNK) / 256 + 4096);
 	if (ctx->test_worklist_cap >= 0) cap = (size_t)ctx->test_worklist_cap;                         // DJB_OPT_TEST_WORKLIST_CAP (tests): force the overflow path
-	long long chunk;
-	djbk::SceneScratch sc;
-	if ((st = scene_scratch(ctx, n, cap, &chunk, &sc)) != DJB_OK) return st;
-	for (long long lo = 0; lo < n; lo += chunk) {                                                  // back to back on the context's stream
-		const long long m = std::min(n - lo, chunk);
-		HIP_TRY(djbk::launch_scene_eval(ctx->stream, mb, s->slots, s->n_mat, m, c.dmat + lo, offset_view(vi, lo), offset_view(vo, lo), offset_view(vout, lo),
-		                                want_cos != 0, sc, ctx->merl_exact_only != 0, utia_exact, ctx->model_set_rows_global != 0));
-	}
+	if ((st = scene_chunks(ctx, n, cap, [&](long long lo, long long m, const djbk::SceneScratch &sc) {
+		return djbk::launch_scene_eval(ctx->stream, mb, s->slots, s->n_mat, m, c.dmat + lo, offset_view(vi, lo), offset_view(vo, lo), offset_view(vout, lo),
+		                               want_cos != 0, sc, ctx->merl_exact_only != 0, utia_exact, ctx->model_set_rows_global != 0);
+	})) != DJB_OK) return st;
 	return c.sg.finish();
 }
 DJB_ABI_CATCH
@@ -188,34 +193,20 @@ try {
 	if (st != DJB_OK) return st;
 	if ((st = proxy_members_check(ctx, s, proxy, "evalp_is_proxy")) != DJB_OK) return st;
 	const djb_brdf *lobe = s->merl || s->utia ? proxy : nullptr;                                   // not looked at without such a member
-	if (is_cpu(ctx)) return djbcpu::scene_evalp_is_proxy(ctx, proxy_host_of(s), lobe, n, material, u1, u2, o, out_weight, out_i, out_pdf);
+	if (is_cpu(ctx)) return djbcpu::scene_evalp_is_proxy(ctx, host_of(s), lobe, n, material, u1, u2, o, out_weight, out_i, out_pdf);
 	if (!Staged::valid(out_weight) || !Staged::valid(out_i) || !out_pdf) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null output");
-	if ((st = check_call(ctx, lobe, n, mem)) != DJB_OK) return st;
-	std::lock_guard<std::recursive_mutex> call_lock(ctx->call_mu);
 	Params model_p;
 	if ((st = device_params(nullptr, &model_p, DJB_KIND_TABULAR)) != DJB_OK) return st;            // as the model set's call resolves it
-	Staged sg(ctx, n, mem);
-	const int32_t *dmat; View vo, vi, vw; const float *d1, *d2; float *dpdf = nullptr;
-	if ((st = stage_material(sg, material, &dmat)) != DJB_OK) return st;
-	if ((st = sg.in_f(u1, &d1)) != DJB_OK) return st;
-	if ((st = sg.in_f(u2, &d2)) != DJB_OK) return st;
-	if ((st = sg.in_vec(o, &vo)) != DJB_OK) return st;
-	if ((st = sg.out_vec(out_i, &vi)) != DJB_OK) return st;
-	if ((st = sg.out_vec(out_weight, &vw)) != DJB_OK) return st;
-	if ((st = sg.out_arr(out_pdf, &dpdf)) != DJB_OK) return st;
-	if (n <= 0) return sg.finish();
-	long long chunk;
-	djbk::SceneScratch sc;
-	if ((st = scene_scratch(ctx, n, 0, &chunk, &sc)) != DJB_OK) return st;
+	SampleBatch c(ctx, lobe, n, mem, material, u1, u2, o, out_i, out_weight, out_pdf);
+	if (c.st != DJB_OK) return c.st;
 	const djbk::SceneMembers mb = members_of(s);
 	const djbk::SceneProxies px = proxies_of(s);
-	for (long long lo = 0; lo < n; lo += chunk) {                                                  // back to back on the context's stream
-		const long long m = std::min(n - lo, chunk);
-		HIP_TRY(djbk::launch_scene_evalp_is_proxy(ctx->stream, mb, px, lobe ? &lobe->dev : nullptr, model_p, s->slots, s->n_mat, m, dmat + lo, d1 + lo, d2 + lo,
-		                                          offset_view(vo, lo), offset_view(vw, lo), offset_view(vi, lo), dpdf + lo, sc, ctx->merl_exact_only != 0,
-		                                          ctx->model_set_rows_global != 0));
-	}
-	return sg.finish();
+	if ((st = scene_chunks(ctx, n, 0, [&](long long lo, long long m, const djbk::SceneScratch &sc) {
+		return djbk::launch_scene_evalp_is_proxy(ctx->stream, mb, px, lobe ? &lobe->dev : nullptr, model_p, s->slots, s->n_mat, m, c.dmat + lo, c.d1 + lo,
+		                                         c.d2 + lo, offset_view(c.vo, lo), offset_view(c.vw, lo), offset_view(c.vi, lo), c.dpdf + lo, sc,
+		                                         ctx->merl_exact_only != 0, ctx->model_set_rows_global != 0);
+	})) != DJB_OK) return st;
+	return c.sg.finish();
 }
 DJB_ABI_CATCH
 
@@ -227,25 +218,20 @@ try {
 	if ((st = proxy_members_check(ctx, s, proxy, "evalp_pdf_proxy")) != DJB_OK) return st;
 	if (!out_pdf) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null out_pdf (evalp alone: djb_scene_eval_batch)");
 	const djb_brdf *lobe = s->merl || s->utia ? proxy : nullptr;                                   // not looked at without such a member
-	if (is_cpu(ctx)) return djbcpu::scene_evalp_pdf(ctx, proxy_host_of(s), lobe, n, material, i, o, out_fr, out_pdf);
+	if (is_cpu(ctx)) return djbcpu::scene_evalp_pdf(ctx, host_of(s), lobe, n, material, i, o, out_fr, out_pdf);
 	Params model_p;
 	if ((st = device_params(nullptr, &model_p, DJB_KIND_TABULAR)) != DJB_OK) return st;
 	SetBatch c(ctx, lobe, n, mem, material, i, o, out_fr);
 	if (c.st != DJB_OK) return c.st;
 	float *dpdf = nullptr;
 	if ((st = c.sg.out_arr(out_pdf, &dpdf)) != DJB_OK) return st;
-	if (n <= 0) return c.sg.finish();
-	long long chunk;
-	djbk::SceneScratch sc;
-	if ((st = scene_scratch(ctx, n, 0, &chunk, &sc)) != DJB_OK) return st;
 	const djbk::SceneMembers mb = members_of(s);
 	const djbk::SceneProxies px = proxies_of(s);
-	for (long long lo = 0; lo < n; lo += chunk) {
-		const long long m = std::min(n - lo, chunk);
-		HIP_TRY(djbk::launch_scene_evalp_pdf_proxy(ctx->stream, mb, px, lobe ? &lobe->dev : nullptr, model_p, s->slots, s->n_mat, m, c.dmat + lo,
-		                                           offset_view(c.vi, lo), offset_view(c.vo, lo), offset_view(c.vout, lo), dpdf + lo, sc,
-		                                           ctx->merl_exact_only != 0, ctx->model_set_rows_global != 0));
-	}
+	if ((st = scene_chunks(ctx, n, 0, [&](long long lo, long long m, const djbk::SceneScratch &sc) {
+		return djbk::launch_scene_evalp_pdf_proxy(ctx->stream, mb, px, lobe ? &lobe->dev : nullptr, model_p, s->slots, s->n_mat, m, c.dmat + lo,
+		                                          offset_view(c.vi, lo), offset_view(c.vo, lo), offset_view(c.vout, lo), dpdf + lo, sc,
+		                                          ctx->merl_exact_only != 0, ctx->model_set_rows_global != 0);
+	})) != DJB_OK) return st;
 	return c.sg.finish();
 }
 DJB_ABI_CATCH

@@ -1,7 +1,8 @@
 // djb_set_host.hpp -- what the C ABIs of the three material sets and of scenes share (djb_merl_set.hip, djb_utia_set.hip, djb_model_set.hip,
 // djb_scene.hip; included by those alone): the checks of a handle, a member and a count, the construction and release of the resident block,
-// the proxy parameter block of the MERL and UTIA sets and the check of a proxy object, and the entry of an eval batch.  `what` is the set's
-// noun in the messages: "merl" / "utia" / "model" / "scene".  Everything works on djb_set_base (djb_host.hpp).
+// the proxy parameter block of the MERL and UTIA sets and the check of a proxy object, and the entry of a batch of either shape (eval or
+// light sample; sampling).  `what` is the set's noun in the messages: "merl" / "utia" / "model" / "scene".  Everything works on
+// djb_set_base (djb_host.hpp).
 #pragma once
 #include "djb_host.hpp"
 
@@ -118,26 +119,52 @@ inline djb_status proxy_object_check(const djb_ctx *ctx, const djb_brdf *proxy, 
 }
 
 // The entry of a batch call on a GPU context's set, after set_check and the CPU dispatch: check_call, the call lock (held while this
-// object lives), then the ids, i, o and the output where the kernels read and write them.  `st` is the first failure; the caller
-// launches on dmat / vi / vo / vout and returns sg.finish().
-struct SetBatch {
+// object lives), then the call's arrays where the kernels read and write them, staged by the two shapes below.  `st` is the first
+// failure; the caller launches on the staged members and returns sg.finish().
+struct BatchEntry {
 	djb_status st;
 	std::unique_lock<std::recursive_mutex> call_lock;
 	Staged sg;
 	const int32_t *dmat = nullptr;
+
+	BatchEntry(djb_ctx *ctx, const djb_brdf *b, long long n, int mem)
+		: st(check_call(ctx, b, n, mem)),
+		  call_lock(st == DJB_OK ? std::unique_lock<std::recursive_mutex>(ctx->call_mu) : std::unique_lock<std::recursive_mutex>()),
+		  sg(ctx, n, mem) {}
+};
+// an eval or light-sample batch: the ids, i, o and the output (a light sample's out_pdf: the caller's, after this)
+struct SetBatch : BatchEntry {
 	View vi, vo, vout;
 
 	SetBatch(djb_ctx *ctx, const djb_brdf *b, long long n, int mem, const int32_t *material, const djb_vec3_view *i, const djb_vec3_view *o,
 	         const djb_vec3_view *out)
-		: st(check_call(ctx, b, n, mem)),
-		  call_lock(st == DJB_OK ? std::unique_lock<std::recursive_mutex>(ctx->call_mu) : std::unique_lock<std::recursive_mutex>()),
-		  sg(ctx, n, mem)
+		: BatchEntry(ctx, b, n, mem)
 	{
 		if (st != DJB_OK) return;
 		if ((st = stage_material(sg, material, &dmat)) != DJB_OK) return;
 		if ((st = sg.in_vec(i, &vi)) != DJB_OK) return;
 		if ((st = sg.in_vec(o, &vo)) != DJB_OK) return;
 		st = sg.out_vec(out, &vout);
+	}
+};
+// a sampling batch: the ids, u1, u2, o, then the outputs i, weight and pdf
+struct SampleBatch : BatchEntry {
+	const float *d1 = nullptr, *d2 = nullptr;
+	View vo, vi, vw;
+	float *dpdf = nullptr;
+
+	SampleBatch(djb_ctx *ctx, const djb_brdf *b, long long n, int mem, const int32_t *material, const float *u1, const float *u2, const djb_vec3_view *o,
+	            const djb_vec3_view *out_i, const djb_vec3_view *out_weight, float *out_pdf)
+		: BatchEntry(ctx, b, n, mem)
+	{
+		if (st != DJB_OK) return;
+		if ((st = stage_material(sg, material, &dmat)) != DJB_OK) return;
+		if ((st = sg.in_f(u1, &d1)) != DJB_OK) return;
+		if ((st = sg.in_f(u2, &d2)) != DJB_OK) return;
+		if ((st = sg.in_vec(o, &vo)) != DJB_OK) return;
+		if ((st = sg.out_vec(out_i, &vi)) != DJB_OK) return;
+		if ((st = sg.out_vec(out_weight, &vw)) != DJB_OK) return;
+		st = sg.out_arr(out_pdf, &dpdf);
 	}
 };
 

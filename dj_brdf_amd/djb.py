@@ -221,6 +221,54 @@ def _scalar_in(u, like: _Vec):
     return u, u.ctypes.data
 
 
+def _material_ids(material, like: _Vec):
+    """the int32 ids of a batch on a material set, one per hit, in the memory space of ``like``: (the array to keep alive, its address)"""
+    if like.is_torch:
+        if not _is_dev(material):
+            material = torch.as_tensor(np.asarray(material.cpu() if hasattr(material, "cpu") else material).astype(np.int32), device=like.device)
+        material = material.to(torch.int32).contiguous()
+        n, ptr = material.numel(), material.data_ptr()
+    else:
+        material = np.ascontiguousarray(material.cpu().numpy() if hasattr(material, "cpu") else material, dtype=np.int32)
+        n, ptr = material.size, material.ctypes.data
+    if n != like.n or material.ndim != 1:
+        raise exc(1, f"djb_error: material must hold one int32 id per hit ({like.n}), got shape {tuple(material.shape)}")
+    return material, ptr
+
+
+def _sampling_call(fn, head, material, u1, u2, o, tail=()):
+    """The marshalling of every sampling step: ``fn(*head, n, [ids,] u1, u2, o, *tail, out_weight, out_i, out_pdf, mem)`` -> (weight, i,
+    pdf).  ``head``: the handles that precede n; ``material``: the per-hit ids of a set or scene call, else None; ``tail``: the parameter
+    sets of a single-material call.  The staged arrays live until the call has returned."""
+    vo = _Vec(o)
+    keep, mp = (None, None) if material is None else _material_ids(material, vo)
+    ids = () if material is None else (C.c_void_p(mp),)
+    k1, p1 = _scalar_in(u1, vo)
+    k2, p2 = _scalar_in(u2, vo)
+    w, i = vo.like(), vo.like()
+    pdf, pdf_ptr = vo.scalars()
+    _lib.check(fn(*head, C.c_int64(vo.n), *ids, C.c_void_p(p1), C.c_void_p(p2), C.byref(vo.view),
+                  *tail, C.byref(w.view), C.byref(i.view), C.c_void_p(pdf_ptr), C.c_int(vo.mem)))
+    del keep, k1, k2
+    return w.keep, i.keep, pdf
+
+
+def _light_call(fn, head, material, i, o, tail=()):
+    """The marshalling of every light sample: ``fn(*head, n, [ids,] i, o, *tail, out_fr, out_pdf, mem)`` -> (fr, pdf); the arguments as
+    in ``_sampling_call``."""
+    vi, vo = _Vec(i), _Vec(o)
+    if vi.n != vo.n or vi.mem != vo.mem:
+        raise exc(1, "djb_error: i and o must have the same length and memory space")
+    keep, mp = (None, None) if material is None else _material_ids(material, vi)
+    ids = () if material is None else (C.c_void_p(mp),)
+    fr = vi.like()
+    pdf, pdf_ptr = vi.scalars()
+    _lib.check(fn(*head, C.c_int64(vi.n), *ids, C.byref(vi.view), C.byref(vo.view), *tail,
+                  C.byref(fr.view), C.c_void_p(pdf_ptr), C.c_int(vi.mem)))
+    del keep
+    return fr.keep, pdf
+
+
 # --------------------------------------------------------------------------- fresnel (dj_brdf.h:149-207)
 def vec3_from_angles(theta, phi) -> np.ndarray:
     """``djb::vec3(theta, phi)`` (dj_brdf.h:67, 589-595): [n,3] unit vectors, the reference's float/double order
@@ -406,17 +454,7 @@ class brdf:
 
     def evalp_is(self, u1, u2, o, user_param=None):
         """(f_r cos / pdf, i, pdf) (dj_brdf.h:87-90)."""
-        lib = _lib.load()
-        vo = _Vec(o)
-        k1, p1 = _scalar_in(u1, vo)
-        k2, p2 = _scalar_in(u2, vo)
-        w, i = vo.like(), vo.like()
-        pdf, pdf_ptr = vo.scalars()
-        _lib.check(lib.djb_evalp_is_batch(self.ctx._h, self._h, C.c_int64(vo.n), C.c_void_p(p1), C.c_void_p(p2),
-                                          C.byref(vo.view), _params_ptr(user_param), C.byref(w.view),
-                                          C.byref(i.view), C.c_void_p(pdf_ptr), C.c_int(vo.mem)))
-        del k1, k2
-        return w.keep, i.keep, pdf
+        return _sampling_call(_lib.load().djb_evalp_is_batch, (self.ctx._h, self._h), None, u1, u2, o, (_params_ptr(user_param),))
 
     def evalp_is_proxy(self, proxy, u1, u2, o, user_param=None, proxy_param=None):
         """(weight, i, pdf) of proxy importance sampling, the per-bounce step of the dj_merl / dj_utia / dj_sgd / dj_abc plugins:
@@ -424,17 +462,8 @@ class brdf:
         and weight = 0, pdf = 0 where i.z <= 0.  One kernel launch on the GPU (djb_evalp_is_proxy_batch)."""
         if not isinstance(proxy, brdf) or not proxy._h or not self._h:     # host code on either side (a user_brdf)
             return _evalp_is_proxy_composed(self, proxy, u1, u2, o, user_param, proxy_param)
-        lib = _lib.load()
-        vo = _Vec(o)
-        k1, p1 = _scalar_in(u1, vo)
-        k2, p2 = _scalar_in(u2, vo)
-        w, i = vo.like(), vo.like()
-        pdf, pdf_ptr = vo.scalars()
-        _lib.check(lib.djb_evalp_is_proxy_batch(self.ctx._h, self._h, proxy._h, C.c_int64(vo.n), C.c_void_p(p1), C.c_void_p(p2),
-                                                C.byref(vo.view), _params_ptr(user_param), _params_ptr(proxy_param),
-                                                C.byref(w.view), C.byref(i.view), C.c_void_p(pdf_ptr), C.c_int(vo.mem)))
-        del k1, k2
-        return w.keep, i.keep, pdf
+        return _sampling_call(_lib.load().djb_evalp_is_proxy_batch, (self.ctx._h, self._h, proxy._h), None, u1, u2, o,
+                              (_params_ptr(user_param), _params_ptr(proxy_param)))
 
     def evalp_pdf_proxy(self, proxy, i, o, user_param=None, proxy_param=None):
         """(fr, pdf) for GIVEN pairs, the light sample of the dj_merl / dj_utia / dj_sgd / dj_abc plugins (next-event estimation / MIS):
@@ -442,15 +471,8 @@ class brdf:
         eval() / pdf() return (a NaN z is evaluated).  One kernel launch on the GPU (djb_evalp_pdf_proxy_batch)."""
         if not isinstance(proxy, brdf) or not proxy._h or not self._h:     # host code on either side (a user_brdf)
             return _evalp_pdf_proxy_composed(self, proxy, i, o, user_param, proxy_param)
-        vi, vo = _Vec(i), _Vec(o)
-        if vi.n != vo.n or vi.mem != vo.mem:
-            raise exc(1, "djb_error: i and o must have the same length and memory space")
-        fr = vi.like()
-        pdf, pdf_ptr = vi.scalars()
-        _lib.check(_lib.load().djb_evalp_pdf_proxy_batch(self.ctx._h, self._h, proxy._h, C.c_int64(vi.n), C.byref(vi.view), C.byref(vo.view),
-                                                        _params_ptr(user_param), _params_ptr(proxy_param), C.byref(fr.view),
-                                                        C.c_void_p(pdf_ptr), C.c_int(vi.mem)))
-        return fr.keep, pdf
+        return _light_call(_lib.load().djb_evalp_pdf_proxy_batch, (self.ctx._h, self._h, proxy._h), None, i, o,
+                           (_params_ptr(user_param), _params_ptr(proxy_param)))
 
     # ---- static utilities (dj_brdf.h:99-100)
     @staticmethod
@@ -1113,30 +1135,16 @@ class merl(brdf):
 
 
 class _material_set:
-    """what merl_set, utia_set and model_set share: the id array of a batch, eval / evalp, and the handle's lifetime.  ``_C`` names the
-    set's C entry points (``{_C}_eval_batch``, ``{_C}_destroy``)."""
+    """what merl_set, utia_set, model_set and scene share: eval / evalp and the handle's lifetime.  ``_C`` names the set's C entry points
+    (``{_C}_eval_batch``, ``{_C}_destroy``)."""
 
     _C = None
-
-    @staticmethod
-    def _ids(material, like: _Vec):
-        if like.is_torch:
-            if not _is_dev(material):
-                material = torch.as_tensor(np.asarray(material.cpu() if hasattr(material, "cpu") else material).astype(np.int32), device=like.device)
-            material = material.to(torch.int32).contiguous()
-            n, ptr = material.numel(), material.data_ptr()
-        else:
-            material = np.ascontiguousarray(material.cpu().numpy() if hasattr(material, "cpu") else material, dtype=np.int32)
-            n, ptr = material.size, material.ctypes.data
-        if n != like.n or material.ndim != 1:
-            raise exc(1, f"djb_error: material must hold one int32 id per hit ({like.n}), got shape {tuple(material.shape)}")
-        return material, ptr
 
     def _eval(self, material, i, o, want_cos):
         vi, vo = _Vec(i), _Vec(o)
         if vi.n != vo.n or vi.mem != vo.mem:
             raise exc(1, "djb_error: i and o must have the same length and memory space")
-        keep, mp = self._ids(material, vi)
+        keep, mp = _material_ids(material, vi)
         out = vi.like()
         _lib.check(getattr(_lib.load(), f"{self._C}_eval_batch")(self.ctx._h, self._h, C.c_int64(vi.n), C.c_void_p(mp), C.byref(vi.view),
                                                                  C.byref(vo.view), C.c_int(want_cos), C.byref(out.view), C.c_int(vi.mem)))
@@ -1163,7 +1171,45 @@ class _material_set:
             pass
 
 
-class merl_set(_material_set):
+class _proxy_params_set(_material_set):
+    """what merl_set and utia_set add: one ``microfacet.params`` per material, the lobe the material's hits are sampled from, given
+    (``{_C}_set_proxy_params``) or fitted from the member objects (``self._members``).  ``_HAS_PARAMS``: the C entry point that reports
+    whether a set is installed, and how many ints it returns before that flag."""
+
+    _HAS_PARAMS = None
+
+    @staticmethod
+    def _params_array(proxy_params, n):
+        if proxy_params is None:
+            return None
+        proxy_params = list(proxy_params)
+        if len(proxy_params) != n or not all(isinstance(p, microfacet.params) for p in proxy_params):
+            raise exc(1, f"djb_error: proxy_params must be {n} microfacet.params (one per material)")
+        return (_lib.Params * max(n, 1))(*[p._p for p in proxy_params])
+
+    @property
+    def has_proxy_params(self) -> bool:
+        entry, before = self._HAS_PARAMS
+        ints = [C.c_int() for _ in range(before + 1)]
+        _lib.check(getattr(_lib.load(), entry)(self._h, *[C.byref(v) for v in ints]))
+        return bool(ints[-1].value)
+
+    def _set_proxy_params(self, proxy_params):
+        _lib.check(getattr(_lib.load(), f"{self._C}_set_proxy_params")(self._h, self._params_array(proxy_params, self.n_materials)))
+
+    def _fit_proxies(self, res, shadow):
+        if any(not b._h for b in self._members):
+            raise exc(1, "djb_error: fit_proxies needs the member objects the set was built from (one was closed)")
+        uniq = list({id(b): b for b in self._members}.values())
+        ab_u, ag_u = fit_brdf_batch(uniq, res, shadow, ctx=self.ctx)
+        at = {id(b): k for k, b in enumerate(uniq)}
+        sel = [at[id(b)] for b in self._members]
+        ab, ag = ab_u[sel], ag_u[sel]
+        self.set_proxy_params([microfacet.params.isotropic(float(a)) for a in ag])
+        return ab, ag
+
+
+class merl_set(_proxy_params_set):
     """M MERL materials resident in ONE block on their context's device, with one fitted proxy parameter set per material: hits that
     land on many measured materials are evaluated / importance-sampled / light-sampled in one call, each hit naming its material by id
     (djb_merl_set, include/djb_hip.h).  An extension: the reference's objects are one material each.
@@ -1173,6 +1219,7 @@ class merl_set(_material_set):
     layouts the other operators take; the ids travel in the memory space of the directions."""
 
     _C = "djb_merl_set"
+    _HAS_PARAMS = ("djb_merl_set_info", 1)
 
     def __init__(self, brdfs, proxy_params=None, ctx: Optional[Context] = None):
         brdfs = list(brdfs)
@@ -1190,67 +1237,25 @@ class merl_set(_material_set):
         ctx = ctx or default_context()
         return cls([merl.from_table(t, ctx=ctx) for t in tables], proxy_params, ctx)
 
-    @staticmethod
-    def _params_array(proxy_params, n):
-        if proxy_params is None:
-            return None
-        proxy_params = list(proxy_params)
-        if len(proxy_params) != n or not all(isinstance(p, microfacet.params) for p in proxy_params):
-            raise exc(1, f"djb_error: proxy_params must be {n} microfacet.params (one per material)")
-        return (_lib.Params * max(n, 1))(*[p._p for p in proxy_params])
-
-    @property
-    def has_proxy_params(self) -> bool:
-        n, has = C.c_int(), C.c_int()
-        _lib.check(_lib.load().djb_merl_set_info(self._h, C.byref(n), C.byref(has)))
-        return bool(has.value)
-
     def set_proxy_params(self, proxy_params):
         """one ``microfacet.params`` per material; replaces the resident set in stream order"""
-        _lib.check(_lib.load().djb_merl_set_set_proxy_params(self._h, self._params_array(proxy_params, self.n_materials)))
+        self._set_proxy_params(proxy_params)
 
     def fit_proxies(self, res: int = 90, shadow: bool = False):
         """``fit_ggx_parameters(tabular(merl, res, shadow))`` of every member (mitsuba/dj_merl.cpp:32 for the whole set, one batched fit)
         installed as ``params.isotropic(alpha_ggx)`` per material.  Returns (alpha_beckmann[M], alpha_ggx[M])."""
-        if any(not b._h for b in self._members):
-            raise exc(1, "djb_error: fit_proxies needs the member objects the set was built from (one was closed)")
-        uniq = list({id(b): b for b in self._members}.values())
-        ab_u, ag_u = fit_brdf_batch(uniq, res, shadow, ctx=self.ctx)
-        at = {id(b): k for k, b in enumerate(uniq)}
-        sel = [at[id(b)] for b in self._members]
-        ab, ag = ab_u[sel], ag_u[sel]
-        self.set_proxy_params([microfacet.params.isotropic(float(a)) for a in ag])
-        return ab, ag
+        return self._fit_proxies(res, shadow)
 
     def evalp_is_proxy(self, proxy, material, u1, u2, o):
         """(weight, i, pdf) per hit as ``brdf.evalp_is_proxy``: direction and pdf from ``proxy`` (a ggx or beckmann object) with the
         hit's material's proxy parameters, f_r cos from the hit's material.  One kernel launch on the GPU."""
-        vo = _Vec(o)
-        keep, mp = self._ids(material, vo)
-        k1, p1 = _scalar_in(u1, vo)
-        k2, p2 = _scalar_in(u2, vo)
-        w, i = vo.like(), vo.like()
-        pdf, pdf_ptr = vo.scalars()
-        _lib.check(_lib.load().djb_merl_set_evalp_is_proxy_batch(self.ctx._h, self._h, proxy._h, C.c_int64(vo.n), C.c_void_p(mp), C.c_void_p(p1),
-                                                                C.c_void_p(p2), C.byref(vo.view), C.byref(w.view), C.byref(i.view),
-                                                                C.c_void_p(pdf_ptr), C.c_int(vo.mem)))
-        del keep, k1, k2
-        return w.keep, i.keep, pdf
+        return _sampling_call(_lib.load().djb_merl_set_evalp_is_proxy_batch, (self.ctx._h, self._h, proxy._h), material, u1, u2, o)
 
     def evalp_pdf_proxy(self, proxy, material, i, o):
         """(fr, pdf) per hit for GIVEN pairs, the light sample of dj_merl (next-event estimation / MIS): f_r * cos(theta_i) of
         material[k] and the pdf of ``proxy`` (a ggx or beckmann object) with the hit's material's proxy parameters; both are +0 where
         i.z <= 0 or o.z <= 0, as the plugin's eval() / pdf() return.  One kernel launch on the GPU."""
-        vi, vo = _Vec(i), _Vec(o)
-        if vi.n != vo.n or vi.mem != vo.mem:
-            raise exc(1, "djb_error: i and o must have the same length and memory space")
-        keep, mp = self._ids(material, vi)
-        fr = vi.like()
-        pdf, pdf_ptr = vi.scalars()
-        _lib.check(_lib.load().djb_merl_set_evalp_pdf_proxy_batch(self.ctx._h, self._h, proxy._h, C.c_int64(vi.n), C.c_void_p(mp), C.byref(vi.view),
-                                                                 C.byref(vo.view), C.byref(fr.view), C.c_void_p(pdf_ptr), C.c_int(vi.mem)))
-        del keep
-        return fr.keep, pdf
+        return _light_call(_lib.load().djb_merl_set_evalp_pdf_proxy_batch, (self.ctx._h, self._h, proxy._h), material, i, o)
 
 
 class utia(brdf):
@@ -1274,7 +1279,7 @@ class utia(brdf):
         return _get_samples(self)
 
 
-class utia_set(_material_set):
+class utia_set(_proxy_params_set):
     """M UTIA materials resident in ONE block on their context's device: hits that land on many measured materials are evaluated in one
     call, each hit naming its material by id (djb_utia_set, include/djb_hip.h).  An extension: the reference's objects are one material
     each.  ``eval`` / ``evalp`` are all that dj_utia asks of its table (it samples the cosine hemisphere), so the set has no sampling
@@ -1286,6 +1291,7 @@ class utia_set(_material_set):
     other operators take; the ids travel in the memory space of the directions."""
 
     _C = "djb_utia_set"
+    _HAS_PARAMS = ("djb_utia_set_proxy_info", 0)
 
     def __init__(self, brdfs, ctx: Optional[Context] = None):
         brdfs = list(brdfs)
@@ -1312,30 +1318,16 @@ class utia_set(_material_set):
         _lib.check(_lib.load().djb_utia_set_info(self._h, C.byref(n)))
         return n.value
 
-    @property
-    def has_proxy_params(self) -> bool:
-        has = C.c_int()
-        _lib.check(_lib.load().djb_utia_set_proxy_info(self._h, C.byref(has)))
-        return bool(has.value)
-
     def set_proxy_params(self, proxy_params):
         """one ``microfacet.params`` per material, the lobe a ``scene`` samples this material's hits from; replaces the resident set in
         stream order"""
-        _lib.check(_lib.load().djb_utia_set_set_proxy_params(self._h, merl_set._params_array(proxy_params, self.n_materials)))
+        self._set_proxy_params(proxy_params)
 
     def fit_proxies(self, res: int = 90, shadow: bool = False):
         """``fit_ggx_parameters(tabular(utia, res, shadow))`` of every member, one batched fit, installed as
         ``params.isotropic(alpha_ggx)`` per material, as ``merl_set.fit_proxies``.  Returns (alpha_beckmann[M], alpha_ggx[M]).  Needs the
         member objects the set was built from (``from_tables`` closes its own)."""
-        if any(not b._h for b in self._members):
-            raise exc(1, "djb_error: fit_proxies needs the member objects the set was built from (one was closed)")
-        uniq = list({id(b): b for b in self._members}.values())
-        ab_u, ag_u = fit_brdf_batch(uniq, res, shadow, ctx=self.ctx)
-        at = {id(b): k for k, b in enumerate(uniq)}
-        sel = [at[id(b)] for b in self._members]
-        ab, ag = ab_u[sel], ag_u[sel]
-        self.set_proxy_params([microfacet.params.isotropic(float(a)) for a in ag])
-        return ab, ag
+        return self._fit_proxies(res, shadow)
 
 
 class model_set(_material_set):
@@ -1430,31 +1422,12 @@ class model_set(_material_set):
     def evalp_is_proxy(self, material, u1, u2, o):
         """(weight, i, pdf) per hit as ``brdf.evalp_is_proxy(tabular(material m), ...)``: direction and pdf from the hit's material's fitted
         lobe, f_r cos from its row; weight = 0 and pdf = 0 where i.z <= 0.  One kernel launch on the GPU."""
-        vo = _Vec(o)
-        keep, mp = self._ids(material, vo)
-        k1, p1 = _scalar_in(u1, vo)
-        k2, p2 = _scalar_in(u2, vo)
-        w, i = vo.like(), vo.like()
-        pdf, pdf_ptr = vo.scalars()
-        _lib.check(_lib.load().djb_model_set_evalp_is_proxy_batch(self.ctx._h, self._h, C.c_int64(vo.n), C.c_void_p(mp), C.c_void_p(p1), C.c_void_p(p2),
-                                                                 C.byref(vo.view), C.byref(w.view), C.byref(i.view), C.c_void_p(pdf_ptr),
-                                                                 C.c_int(vo.mem)))
-        del keep, k1, k2
-        return w.keep, i.keep, pdf
+        return _sampling_call(_lib.load().djb_model_set_evalp_is_proxy_batch, (self.ctx._h, self._h), material, u1, u2, o)
 
     def evalp_pdf_proxy(self, material, i, o):
         """(fr, pdf) per hit for GIVEN pairs, the light sample of dj_sgd / dj_abc: f_r * cos(theta_i) of material[k] and the pdf of its
         fitted lobe; both are +0 where i.z <= 0 or o.z <= 0.  One kernel launch on the GPU."""
-        vi, vo = _Vec(i), _Vec(o)
-        if vi.n != vo.n or vi.mem != vo.mem:
-            raise exc(1, "djb_error: i and o must have the same length and memory space")
-        keep, mp = self._ids(material, vi)
-        fr = vi.like()
-        pdf, pdf_ptr = vi.scalars()
-        _lib.check(_lib.load().djb_model_set_evalp_pdf_proxy_batch(self.ctx._h, self._h, C.c_int64(vi.n), C.c_void_p(mp), C.byref(vi.view),
-                                                                  C.byref(vo.view), C.byref(fr.view), C.c_void_p(pdf_ptr), C.c_int(vi.mem)))
-        del keep
-        return fr.keep, pdf
+        return _light_call(_lib.load().djb_model_set_evalp_pdf_proxy_batch, (self.ctx._h, self._h), material, i, o)
 
 
 class scene(_material_set):
@@ -1514,32 +1487,13 @@ class scene(_material_set):
         """(weight, i, pdf) per hit, the sampling step of a path vertex: what the hit's member set's ``evalp_is_proxy`` returns for it (utia:
         ``brdf.evalp_is_proxy`` on the material with the utia set's parameters); an inactive hit is +0 in all three.  ``proxy`` may be
         None for a scene without merl and utia members."""
-        vo = _Vec(o)
-        keep, mp = self._ids(material, vo)
-        k1, p1 = _scalar_in(u1, vo)
-        k2, p2 = _scalar_in(u2, vo)
-        w, i = vo.like(), vo.like()
-        pdf, pdf_ptr = vo.scalars()
-        _lib.check(_lib.load().djb_scene_evalp_is_proxy_batch(self.ctx._h, self._h, getattr(proxy, "_h", None), C.c_int64(vo.n), C.c_void_p(mp),
-                                                             C.c_void_p(p1), C.c_void_p(p2), C.byref(vo.view), C.byref(w.view), C.byref(i.view),
-                                                             C.c_void_p(pdf_ptr), C.c_int(vo.mem)))
-        del keep, k1, k2
-        return w.keep, i.keep, pdf
+        return _sampling_call(_lib.load().djb_scene_evalp_is_proxy_batch, (self.ctx._h, self._h, getattr(proxy, "_h", None)), material, u1, u2, o)
 
     def evalp_pdf_proxy(self, proxy, material, i, o):
         """(fr, pdf) per hit for GIVEN pairs, the light sample of a path vertex: what the hit's member set's ``evalp_pdf_proxy`` returns
         for it (utia: ``brdf.evalp_pdf_proxy`` with the utia set's parameters); both +0 where i.z <= 0 or o.z <= 0, and for an inactive
         hit.  ``proxy`` may be None for a scene without merl and utia members."""
-        vi, vo = _Vec(i), _Vec(o)
-        if vi.n != vo.n or vi.mem != vo.mem:
-            raise exc(1, "djb_error: i and o must have the same length and memory space")
-        keep, mp = self._ids(material, vi)
-        fr = vi.like()
-        pdf, pdf_ptr = vi.scalars()
-        _lib.check(_lib.load().djb_scene_evalp_pdf_proxy_batch(self.ctx._h, self._h, getattr(proxy, "_h", None), C.c_int64(vi.n), C.c_void_p(mp),
-                                                              C.byref(vi.view), C.byref(vo.view), C.byref(fr.view), C.c_void_p(pdf_ptr), C.c_int(vi.mem)))
-        del keep
-        return fr.keep, pdf
+        return _light_call(_lib.load().djb_scene_evalp_pdf_proxy_batch, (self.ctx._h, self._h, getattr(proxy, "_h", None)), material, i, o)
 
 
 # --------------------------------------------------------------------------- user-defined BRDFs (dj_brdf.h:74-109)

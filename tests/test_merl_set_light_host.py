@@ -149,6 +149,7 @@ def test_error_cases(cpu, mset, proxies):
         assert st == INVALID and "out_pdf" in msg and (out == 7).all(), (st, msg)
         st, msg, *_ = _call(cpu, mset, proxies["ggx"], fr=False)
         assert st == INVALID, (st, msg)
+        assert "null output" in msg and "vec3 view" not in msg, msg      # a missing out_fr: this entry's own wording, not the eval entries'
         st, msg, *_ = _call(cpu, mset, proxies["ggx"], material=False)
         assert st == INVALID and "null material" in msg, (st, msg)
         st, msg, *_ = _call(cpu, mset, djb.ggx(ctx=other))

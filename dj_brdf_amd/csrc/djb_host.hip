@@ -213,7 +213,7 @@ void build_twin(const djb_brdf *b, djb_ctx *via)
 // with calls on the same object.
 const djb_brdf *scalar_twin(const djb_ctx *ctx, const djb_brdf *b, long long n, int mem)
 {
-	if (mem != DJB_MEM_HOST || n > ctx->host_batch_max || n < 0 || !b || ctx->scalar_on_device) return nullptr;
+	if (!b || !scalar_sized(ctx, n, mem)) return nullptr;
 	if (b->device != ctx->device) return nullptr;
 	if (!b->twin_built.load(std::memory_order_acquire)) {
 		std::call_once(b->twin_once, build_twin, b, const_cast<djb_ctx *>(ctx));       // returns once the twin exists, whoever built it

@@ -330,14 +330,16 @@ struct Staged {
 		}
 		return DJB_OK;
 	}
-	djb_status in_f(const float *h, const float **out)
+	// `width` contiguous elements per unit: 1 for a uniform or an id, 2 for (u, v), 5 for a parameter record
+	template <typename T> djb_status in_f(const T *h, const T **out, int width = 1)
 	{
 		if (!h) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null input array");
 		if (mem == DJB_MEM_DEVICE) { *out = h; return DJB_OK; }
-		float *d = nullptr;
-		djb_status st = alloc(sizeof(float) * (size_t)n, (void **)&d);
+		T *d = nullptr;
+		const size_t bytes = sizeof(T) * (size_t)width * (size_t)n;
+		djb_status st = alloc(bytes, (void **)&d);
 		if (st != DJB_OK) return st;
-		if (n) { djb_status cs_ = copy(d, h, sizeof(float) * (size_t)n, hipMemcpyHostToDevice); if (cs_ != DJB_OK) return cs_; }
+		if (n) { djb_status cs_ = copy(d, h, bytes, hipMemcpyHostToDevice); if (cs_ != DJB_OK) return cs_; }
 		*out = d;
 		return DJB_OK;
 	}
@@ -353,14 +355,15 @@ struct Staged {
 		outs.push_back(Out{ *out, *v, lay });
 		return DJB_OK;
 	}
-	template <typename T> djb_status out_arr(T *h, T **out)
+	template <typename T> djb_status out_arr(T *h, T **out, int width = 1)
 	{
 		if (!h) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null output array");
 		if (mem == DJB_MEM_DEVICE) { *out = h; return DJB_OK; }
 		T *d = nullptr;
-		djb_status st = alloc(sizeof(T) * (size_t)n, (void **)&d);
+		const size_t bytes = sizeof(T) * (size_t)width * (size_t)n;
+		djb_status st = alloc(bytes, (void **)&d);
 		if (st != DJB_OK) return st;
-		out_raw.push_back({ d, { h, sizeof(T) * (size_t)n } });
+		out_raw.push_back({ d, { h, bytes } });
 		*out = d;
 		return DJB_OK;
 	}
@@ -398,7 +401,12 @@ struct Staged {
 };
 
 djb_status check_call(djb_ctx *ctx, const djb_brdf *b, long long n, int mem);
-// scalar-size DJB_MEM_HOST calls: the host twin of a GPU object, or NULL when the call belongs on the GPU (djb_host.hip)
+// "this host call is scalar-sized": the host twin answers it on the caller's thread (DJB_OPT_HOST_BATCH_MAX, DJB_OPT_SCALAR_ON_DEVICE)
+inline bool scalar_sized(const djb_ctx *ctx, long long n, int mem)
+{
+	return mem == DJB_MEM_HOST && n >= 0 && n <= ctx->host_batch_max && !ctx->scalar_on_device;
+}
+// such a call's host twin of a GPU object, or NULL when the call belongs on the GPU (djb_host.hip)
 const djb_brdf *scalar_twin(const djb_ctx *ctx, const djb_brdf *b, long long n, int mem);
 djb_status cpu_pair_check(const djb_ctx *ctx, const djb_brdf *b);
 // LEAN maps (djb_leanmap.hip): the map belongs to the context; the pyramid in host memory (a GPU map's copy is made on first use)
@@ -408,27 +416,16 @@ djb_status leanmap_host_texels(const djb_leanmap *m, const float **out);
 inline djb_status stage_leanmap_coords(Staged &sg, const float *uv, const float *lod, djbdev::LeanSrc *src)
 {
 	if (!uv) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null uv array");
-	if (sg.mem == DJB_MEM_DEVICE) { src->uv = uv; src->lod = lod; return DJB_OK; }
-	float *d = nullptr;
-	djb_status st = sg.alloc(sizeof(float) * 2 * (size_t)sg.n, (void **)&d);
+	djb_status st = sg.in_f(uv, &src->uv, 2);
 	if (st != DJB_OK) return st;
-	if (sg.n && (st = sg.copy(d, uv, sizeof(float) * 2 * (size_t)sg.n, hipMemcpyHostToDevice)) != DJB_OK) return st;
-	src->uv = d;
 	src->lod = nullptr;
-	if (lod && (st = sg.in_f(lod, &src->lod)) != DJB_OK) return st;
-	return DJB_OK;
+	return lod ? sg.in_f(lod, &src->lod) : DJB_OK;
 }
 // material sets: the n material ids of a batch where the kernels read them (the rest of what the set files share: djb_set_host.hpp)
 inline djb_status stage_material(Staged &sg, const int32_t *material, const int32_t **out)
 {
 	if (!material) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null material array");
-	if (sg.mem == DJB_MEM_DEVICE) { *out = material; return DJB_OK; }
-	int32_t *d = nullptr;
-	djb_status st = sg.alloc(sizeof(int32_t) * (size_t)sg.n, (void **)&d);
-	if (st != DJB_OK) return st;
-	if (sg.n && (st = sg.copy(d, material, sizeof(int32_t) * (size_t)sg.n, hipMemcpyHostToDevice)) != DJB_OK) return st;
-	*out = d;
-	return DJB_OK;
+	return sg.in_f(material, out);
 }
 // ------------------------------------------------------------------ shared by eval_common (djb_host_ops.hip) and the UTIA set's eval batch
 // Do the n elements of any output stream share memory with those of any input stream?  A stream is a pointer and a stride in 4-byte
@@ -478,9 +475,6 @@ namespace djbk {
 // per-slot rgb samples in HBM as a fit source (djbdev::Brdf::merl_sparse; djb_host.hip): never handed to the eval kernels
 djb_status wrap_merl_slots(djb_ctx *ctx, djbdev::MerlTexel *slots, djb_brdf **out);
 }
-namespace djbh {
-
-} // namespace djbh
 
 // No C++ exception may cross the C ABI (a ctypes / C caller would abort): every entry point is a
 // function-try-block that maps std::bad_alloc and anything else to a status + message.

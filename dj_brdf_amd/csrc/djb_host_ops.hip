@@ -1,16 +1,13 @@
-// djb_host_ops.hip -- the C ABI of libdjb_hip.so, part 2: the operator surface.  Host <-> HBM pipelines of large
-// DJB_MEM_HOST batches, the tier-2 worklist bookkeeping of the two-tier kernels, eval / evalp / pdf / sample / evalp_is /
-// io_to_hd / query / merl_index / per-pair-parameter entry points, beckmann::lrep, the synthetic-workload generators and
-// the device self-tests.  Shared internals: djb_host.hpp.
+// djb_host_ops.hip -- the C ABI of libdjb_hip.so, part 2: the operator surface.  The chunked host <-> HBM pipeline of large
+// DJB_MEM_HOST batches; CallArrays / run_call, through which each of the six operator bodies (eval, sample, the proxy pair, the _pp
+// pair) names its arrays once and has both host paths derived from that list; the tier-2 worklist bookkeeping of the two-tier kernels;
+// the eval / evalp / pdf / sample / evalp_is / proxy / io_to_hd / query / merl_index / per-pair-parameter entry points, beckmann::lrep,
+// the synthetic-workload generators and the device self-tests.  Shared internals: djb_host.hpp.
 #include "djb_host.hpp"
 
 using namespace djbh;
 
 namespace {
-
-djb_status eval_common(djb_ctx *ctx, const djb_brdf *b, int64_t n, const djb_vec3_view *i,
-                       const djb_vec3_view *o, const djb_params *params, const djb_vec3_view *out_fr,
-                       float *out_pdf, int mem, int want);
 
 // ------------------------------------------------------------------ large host batches: both PCIe directions in flight
 // A DJB_MEM_HOST batch of >= 2 chunks is cut into chunks of DJB_HOST_PIPE_CHUNK units (default: n/8 clamped
@@ -52,14 +49,14 @@ struct PipeArr {
 	float *f = nullptr; int width = 1;                    // `width` contiguous floats per unit (1 = scalar, 5 = params record)
 	float *dev[2] = { nullptr, nullptr };                 // the two HBM slots
 	long long C = 0;
-	static PipeArr vec(const djb_vec3_view *v) { PipeArr a; a.v = v; a.layout = Staged::layout_of(v); return a; }
+	static PipeArr vec(const djb_vec3_view *v) { PipeArr a; a.v = v; a.layout = v ? Staged::layout_of(v) : 0; return a; }   // null: declined below
 	static PipeArr arr(const float *f, int width = 1) { PipeArr a; a.f = const_cast<float *>(f); a.width = width; return a; }
 	HostSpan span(long long n) const { return v ? span_of(v, n) : HostSpan{ (uintptr_t)f, (uintptr_t)(f + (size_t)width * n) }; }
 	size_t floats_per_unit() const { return v ? 3 : (size_t)width; }
-	djb_vec3_view view(int s) const   // device view of slot s (vec3 arrays)
+	View view(int s) const   // device view of slot s (vec3 arrays)
 	{
 		float *d = dev[s];
-		return layout == 0 ? djb_vec3_view{ d, d + 1, d + 2, 3 } : djb_vec3_view{ d, d + C, d + 2 * C, 1 };
+		return layout == 0 ? View{ d, d + 1, d + 2, 3 } : View{ d, d + C, d + 2 * C, 1 };
 	}
 	// units [lo, lo + m) between the caller's memory and slot s; one pageable copy at a time (Staged::copy)
 	hipError_t move(int s, long long lo, long long m, bool to_dev, hipStream_t st) const
@@ -184,20 +181,65 @@ djb_status host_pipeline(djb_ctx *ctx, long long n, std::vector<PipeArr> &ins, s
 	return DJB_OK;
 }
 
-djb_status eval_host_pipelined(djb_ctx *ctx, const djb_brdf *b, long long n, const djb_vec3_view *i,
-                               const djb_vec3_view *o, const djb_params *params, const djb_vec3_view *out_fr,
-                               float *out_pdf, int want, bool *taken)
+// ------------------------------------------------------------------ the arrays of one call, named once
+// A body lists its per-unit arrays in the order in which the plain path reports a missing one: input views, input arrays of `width`
+// floats per unit (1: u1 / u2 / lod, 2: uv, 5: a parameter record), output views, output arrays.  An array the call does not have is
+// left out of the list; the body keeps -1 as its index, for which view() is the all-null view and arr() is null.  run_call derives
+// both host paths from the list and calls the body's device part -- everything after device_params, a function of what the kernels
+// read and write -- with view(k) / arr(k) set: to the whole batch (the caller's own arrays, or their Staged copies), or to one chunk.
+struct CallArrays {
+	struct Arr { bool vec, out; const djb_vec3_view *v; float *f; int width; View dv; float *df; int pipe; };
+	Arr a[10];
+	int count = 0;
+	int add(bool vec, bool out, const djb_vec3_view *v, const float *f, int width)
+	{
+		a[count] = Arr{ vec, out, v, const_cast<float *>(f), width, View{ nullptr, nullptr, nullptr, 0 }, nullptr, 0 };
+		return count++;
+	}
+	int in(const djb_vec3_view *v) { return add(true, false, v, nullptr, 3); }
+	int in(const float *f, int width = 1) { return add(false, false, nullptr, f, width); }
+	int out(const djb_vec3_view *v) { return add(true, true, v, nullptr, 3); }
+	int out(float *f, int width = 1) { return add(false, true, nullptr, f, width); }
+	View view(int k) const { return k < 0 ? View{ nullptr, nullptr, nullptr, 0 } : a[k].dv; }
+	float *arr(int k) const { return k < 0 ? nullptr : a[k].df; }
+};
+
+// device(m): enqueue the call's kernels for the m units that A.view / A.arr now name.  may_chunk: a large DJB_MEM_HOST batch tries the
+// chunked pipeline first (device runs once per chunk, on the slots); host_pipeline declines a batch with a missing array, which the
+// plain path below then reports in list order.
+template <class Device>
+djb_status run_call(djb_ctx *ctx, long long n, int mem, bool may_chunk, CallArrays &A, Device device)
 {
-	*taken = false;
-	const bool wfr = (want & 3) != 0, wpdf = (want & 4) != 0;
-	if (!i || !o || (wfr && !out_fr)) return DJB_OK;                      // the plain path reports the error
-	std::vector<PipeArr> ins{ PipeArr::vec(i), PipeArr::vec(o) }, outs;
-	if (wfr) outs.push_back(PipeArr::vec(out_fr));
-	if (wpdf) outs.push_back(PipeArr::arr(out_pdf));
-	return host_pipeline(ctx, n, ins, outs, [&](long long m, int s) {
-		djb_vec3_view vi = ins[0].view(s), vo = ins[1].view(s), vf = wfr ? outs[0].view(s) : djb_vec3_view{ nullptr, nullptr, nullptr, 0 };
-		return eval_common(ctx, b, m, &vi, &vo, params, wfr ? &vf : nullptr, wpdf ? outs.back().dev[s] : nullptr, DJB_MEM_DEVICE, want);
-	}, taken);
+	djb_status st;
+	if (may_chunk && mem == DJB_MEM_HOST && n > SMALL_N) {
+		std::vector<PipeArr> ins, outs;
+		for (int k = 0; k < A.count; ++k) {
+			CallArrays::Arr &e = A.a[k];
+			std::vector<PipeArr> &set = e.out ? outs : ins;
+			e.pipe = (int)set.size();
+			set.push_back(e.vec ? PipeArr::vec(e.v) : PipeArr::arr(e.f, e.width));
+		}
+		bool taken = false;
+		st = host_pipeline(ctx, n, ins, outs, [&](long long m, int s) {
+			for (int k = 0; k < A.count; ++k) {
+				CallArrays::Arr &e = A.a[k];
+				const PipeArr &pa = (e.out ? outs : ins)[e.pipe];
+				if (e.vec) e.dv = pa.view(s); else e.df = pa.dev[s];
+			}
+			return device(m);
+		}, &taken);
+		if (taken || st != DJB_OK) return st;
+	}
+	Staged sg(ctx, n, mem);
+	for (int k = 0; k < A.count; ++k) {
+		CallArrays::Arr &e = A.a[k];
+		if (e.vec) st = e.out ? sg.out_vec(e.v, &e.dv) : sg.in_vec(e.v, &e.dv);
+		else if (e.out) st = sg.out_arr(e.f, &e.df, e.width);
+		else st = sg.in_f(e.f, const_cast<const float **>(&e.df), e.width);
+		if (st != DJB_OK) return st;
+	}
+	if ((st = device(n)) != DJB_OK) return st;
+	return sg.finish();
 }
 
 // worklist capacity bookkeeping (ctx->call_mu held).  wl_adapt: if the previous large call has finished and its list
@@ -232,40 +274,18 @@ bool wl_note(djb_ctx *ctx, const unsigned int *count, size_t cap, long long n, i
 	return true;
 }
 
-djb_status eval_common(djb_ctx *ctx, const djb_brdf *b, int64_t n, const djb_vec3_view *i,
-                       const djb_vec3_view *o, const djb_params *params, const djb_vec3_view *out_fr,
-                       float *out_pdf, int mem, int want)
+// the device part of eval / evalp / pdf / eval_pdf (ctx->call_mu held): the kernels of n pairs on device views; vout is all-null and
+// dpdf null where not asked for.  A chunk of a host batch is a call of n units to everything here, the contract bookkeeping included.
+djb_status eval_device(djb_ctx *ctx, const djb_brdf *b, const Params &p, long long n, View vi, View vo, View vout, float *dpdf, int want)
 {
-	if (!b) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null brdf");
-	if (!ctx) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null ctx");
-	djb_status st = cpu_pair_check(ctx, b);
-	if (st != DJB_OK) return st;
-	if (is_cpu(ctx)) return djbcpu::eval(ctx, b, n, i, o, params, out_fr, out_pdf, want);
-	if (const djb_brdf *tw = scalar_twin(ctx, b, n, mem)) return djbcpu::eval(djbcpu::twin_ctx(), tw, n, i, o, params, out_fr, out_pdf, want);
-	st = check_call(ctx, b, n, mem);
-	if (st != DJB_OK) return st;
-	std::lock_guard<std::recursive_mutex> call_lock(ctx->call_mu);
-	Params p;
-	if ((st = device_params(params, &p, b->dev.kind)) != DJB_OK) return st;
-	if (mem == DJB_MEM_HOST && n > SMALL_N) {
-		bool taken = false;
-		st = eval_host_pipelined(ctx, b, n, i, o, params, out_fr, out_pdf, want, &taken);
-		if (taken || st != DJB_OK) return st;
-	}
-	Staged sg(ctx, n, mem);
-	View vi, vo, vout{ nullptr, nullptr, nullptr, 0 };
-	float *dpdf = nullptr;
-	if ((st = sg.in_vec(i, &vi)) != DJB_OK) return st;
-	if ((st = sg.in_vec(o, &vo)) != DJB_OK) return st;
-	if ((want & 3) && (st = sg.out_vec(out_fr, &vout)) != DJB_OK) return st;
-	if ((want & 4) && (st = sg.out_arr(out_pdf, &dpdf)) != DJB_OK) return st;
+	djb_status st;
 	// The two-tier kernels write placeholders in tier 1 and re-read their inputs in tier 2 (worklist overflow: the whole
 	// batch), so a device-resident caller whose OUTPUT arrays overlap its INPUT arrays (in-place evalp) must not use them:
 	// such calls take the one-kernel forms, which read a pair before they write it (index-aligned in-place views are
-	// the only supported kind of overlap, as for any elementwise kernel).
+	// the only supported kind of overlap, as for any elementwise kernel).  Staged copies and pipeline slots never overlap.
 	const Stream ins[6] = { { vi.x, vi.stride }, { vi.y, vi.stride }, { vi.z, vi.stride }, { vo.x, vo.stride }, { vo.y, vo.stride }, { vo.z, vo.stride } };
 	const Stream outs[4] = { { vout.x, vout.stride }, { vout.y, vout.stride }, { vout.z, vout.stride }, { dpdf, 1 } };   // null where not asked for
-	const bool aliased = mem == DJB_MEM_DEVICE && outputs_overlap_inputs(n, ins, 6, outs, 4);
+	const bool aliased = outputs_overlap_inputs(n, ins, 6, outs, 4);
 	if (b->dev.kind == DJB_KIND_MERL && (want & 3) && !ctx->merl_exact_only && !aliased) {
 		// two-tier exact lookup (both tiers in one kernel: tier 2 is drained from per-wave LDS queues); pair indices travel as uint32, so very
 		// large batches are chunked
@@ -274,7 +294,7 @@ djb_status eval_common(djb_ctx *ctx, const djb_brdf *b, int64_t n, const djb_vec
 			HIP_TRY(djbk::launch_merl_twotier(ctx->stream, b->dev, m, offset_view(vi, lo), offset_view(vo, lo), offset_view(vout, lo),
 			                                  dpdf ? dpdf + lo : nullptr, want));
 		}
-		return sg.finish();
+		return DJB_OK;
 	}
 	if (b->dev.kind == DJB_KIND_UTIA && (want & 3) && !ctx->utia_exact_only && !aliased) {
 		// two-tier (djb_kernels_eval.hip): pair indices travel as uint32, so very large batches are chunked; the
@@ -288,7 +308,7 @@ djb_status eval_common(djb_ctx *ctx, const djb_brdf *b, int64_t n, const djb_vec
 			HIP_TRY(djbk::launch_utia_twotier(ctx->stream, b->dev, m, offset_view(vi, lo), offset_view(vo, lo), offset_view(vout, lo),
 			                                  dpdf ? dpdf + lo : nullptr, want, list, (unsigned int)cap, count, ctx->contract_1e5 != 0));
 		}
-		return sg.finish();
+		return DJB_OK;
 	}
 	// contract mode pays while tier 2 is a small share of the batch.  A narrow Beckmann lobe sends most pairs there (the
 	// denormal tail of exp(-r^2): 73 % at alpha = 0.05 on the bench distribution) and would cost tier 1 ON TOP of the exact
@@ -335,12 +355,108 @@ djb_status eval_common(djb_ctx *ctx, const djb_brdf *b, int64_t n, const djb_vec
 				                                   dpdf ? dpdf + lo : nullptr, want, list, (unsigned int)cap, count));
 				if (wl_note(ctx, count, cap, m, (int)djbk::CONTRACT_SHARDS, (int)djbk::CONTRACT_COUNTER_STRIDE)) ctx->wl_note_key = ct_key;
 			}
-			return sg.finish();
+			return DJB_OK;
 		}
 	}
 	HIP_TRY(djbk::launch_eval(ctx->stream, b->dev, p, n, vi, vo, vout, dpdf, want));
-	return sg.finish();
+	return DJB_OK;
 }
+
+djb_status eval_common(djb_ctx *ctx, const djb_brdf *b, int64_t n, const djb_vec3_view *i,
+                       const djb_vec3_view *o, const djb_params *params, const djb_vec3_view *out_fr,
+                       float *out_pdf, int mem, int want)
+{
+	if (!b) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null brdf");
+	if (!ctx) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null ctx");
+	djb_status st = cpu_pair_check(ctx, b);
+	if (st != DJB_OK) return st;
+	if (is_cpu(ctx)) return djbcpu::eval(ctx, b, n, i, o, params, out_fr, out_pdf, want);
+	if (const djb_brdf *tw = scalar_twin(ctx, b, n, mem)) return djbcpu::eval(djbcpu::twin_ctx(), tw, n, i, o, params, out_fr, out_pdf, want);
+	st = check_call(ctx, b, n, mem);
+	if (st != DJB_OK) return st;
+	std::lock_guard<std::recursive_mutex> call_lock(ctx->call_mu);
+	Params p;
+	if ((st = device_params(params, &p, b->dev.kind)) != DJB_OK) return st;
+	CallArrays A;
+	const int ki = A.in(i), ko = A.in(o), kf = (want & 3) ? A.out(out_fr) : -1, kp = (want & 4) ? A.out(out_pdf) : -1;
+	return run_call(ctx, n, mem, true, A, [&](long long m) { return eval_device(ctx, b, p, m, A.view(ki), A.view(ko), A.view(kf), A.arr(kp), want); });
+}
+
+// What the two proxy entries (`op` names the one, for the message) do with their pair of non-null objects before they stage anything: the
+// back-end match, the CPU context's and the host twin's answer -- host(ctx, target, proxy) is the entry's djbcpu call; the twin answers
+// when both objects have one -- and the refusals of a GPU call.  *on_gpu: the call goes on to the GPU (DJB_OK); else the result is final.
+template <class Host>
+djb_status proxy_pair_checks(const char *op, djb_ctx *ctx, const djb_brdf *target, const djb_brdf *proxy, int64_t n, int mem, Host host, bool *on_gpu)
+{
+	*on_gpu = false;
+	djb_status st = cpu_pair_check(ctx, target);
+	if (st != DJB_OK) return st;
+	if ((st = cpu_pair_check(ctx, proxy)) != DJB_OK) return st;
+	if (is_cpu(ctx)) return host(ctx, target, proxy);
+	if (target->ctx != proxy->ctx || target->device != proxy->device)
+		return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: target and proxy belong to different contexts");
+	if (const djb_brdf *tt = scalar_twin(ctx, target, n, mem))
+		if (const djb_brdf *pt = scalar_twin(ctx, proxy, n, mem)) return host(djbcpu::twin_ctx(), tt, pt);
+	if ((st = check_call(ctx, target, n, mem)) != DJB_OK) return st;
+	if ((st = check_call(ctx, proxy, n, mem)) != DJB_OK) return st;
+	if (!djbk::evalp_is_proxy_supported(target->dev.kind, proxy->dev.kind) || (target->dev.kind == DJB_KIND_MERL && target->dev.merl_sparse))
+		return fail(DJB_ERR_NOT_IMPLEMENTED, "djb_error: %s on the GPU takes a merl / utia / sgd / abc target and a ggx / beckmann / tabular / "
+		            "tabular_anisotropic proxy (target kind %d, proxy kind %d)", op, target->dev.kind, proxy->dev.kind);
+	*on_gpu = true;
+	return DJB_OK;
+}
+
+// mode 2 (the fused LEAN-map calls): the records are looked up in `hit->map` at (hit->uv, hit->lod); `rec` is not used
+struct LeanHit { const djb_leanmap *map; const float *uv, *lod; };
+// the host path's form of a mode 2 call: the records by the host lookup, then mode 1 (what the kernels do per lane)
+djb_status leanmap_host_records(const djb_ctx *ctx, const LeanHit *hit, int64_t n, std::vector<float> *rec)
+{
+	const float *texels;
+	djb_status st = leanmap_host_texels(hit->map, &texels);
+	if (st != DJB_OK) return st;
+	rec->resize(5 * (size_t)n);
+	djbcpu::leanmap_lookup(is_cpu(ctx) ? const_cast<djb_ctx *>(ctx) : djbcpu::twin_ctx(), texels, hit->map->lw, hit->map->lh, n, hit->uv, hit->lod, rec->data());
+	return DJB_OK;
+}
+// What the two _pp bodies do between their own argument checks and the context's lock: the back-end and map checks, the CPU context's and
+// the host twin's answer -- host(ctx, b, rec, mode) is the body's djbcpu call; a LEAN-map call reaches it as mode 1 on the records of the
+// host lookup -- and check_call.  *on_gpu: the call goes on to the GPU (DJB_OK); else the result is final.
+template <class Host>
+djb_status pp_checks(djb_ctx *ctx, const djb_brdf *b, int64_t n, int mem, const LeanHit *hit, const float *rec, int mode, Host host, bool *on_gpu)
+{
+	*on_gpu = false;
+	djb_status st = cpu_pair_check(ctx, b);
+	if (st != DJB_OK) return st;
+	if (hit && (st = leanmap_check(ctx, hit->map)) != DJB_OK) return st;
+	if (n < 0 && hit) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: negative batch size");
+	const djb_brdf *tw = is_cpu(ctx) ? nullptr : scalar_twin(ctx, b, n, mem);
+	if (is_cpu(ctx) || tw) {
+		if (n <= 0) return DJB_OK;
+		std::vector<float> looked_up;
+		if (hit) { if ((st = leanmap_host_records(ctx, hit, n, &looked_up)) != DJB_OK) return st; rec = looked_up.data(); mode = 1; }
+		return is_cpu(ctx) ? host(ctx, b, rec, mode) : host(djbcpu::twin_ctx(), tw, rec, mode);
+	}
+	if ((st = check_call(ctx, b, n, mem)) != DJB_OK) return st;
+	*on_gpu = true;
+	return DJB_OK;
+}
+// where the kernels of a _pp call find their records, as entries of the call's array list: the caller's records, or -- a LEAN-map call --
+// the (u, v) pairs and, if given, the lods
+struct PpSource {
+	const LeanHit *hit;
+	int krec = -1, kuv = -1, klod = -1;
+	PpSource(CallArrays &A, const LeanHit *h, const float *rec) : hit(h)
+	{
+		if (!hit) krec = A.in(rec, 5);
+		else { kuv = A.in(hit->uv, 2); if (hit->lod) klod = A.in(hit->lod); }
+	}
+	const float *rec(const CallArrays &A) const { return A.arr(krec); }
+	djbdev::LeanSrc lean_src(const CallArrays &A) const
+	{
+		if (!hit) return djbdev::LeanSrc{ { nullptr, 0, 0 }, nullptr, nullptr };
+		return djbdev::LeanSrc{ { hit->map->dev, hit->map->lw, hit->map->lh }, A.arr(kuv), A.arr(klod) };
+	}
+};
 
 } // namespace
 
@@ -392,31 +508,15 @@ static djb_status sample_common(djb_ctx *ctx, const djb_brdf *b, int64_t n, cons
 	std::lock_guard<std::recursive_mutex> call_lock(ctx->call_mu);
 	Params p;
 	if ((st = device_params(params, &p, b->dev.kind)) != DJB_OK) return st;
-	if (mem == DJB_MEM_HOST && n > SMALL_N && o && out_i && (!is || out_w)) {   // large host batch: chunked, both PCIe directions busy
-		bool taken = false;
-		std::vector<PipeArr> ins{ PipeArr::arr(u1), PipeArr::arr(u2), PipeArr::vec(o) }, outs{ PipeArr::vec(out_i) };
-		if (is) { outs.push_back(PipeArr::vec(out_w)); outs.push_back(PipeArr::arr(out_pdf)); }
-		st = host_pipeline(ctx, n, ins, outs, [&](long long m, int s) {
-			djb_vec3_view dvo = ins[2].view(s), dvi = outs[0].view(s), dvw = is ? outs[1].view(s) : djb_vec3_view{ nullptr, nullptr, nullptr, 0 };
-			return sample_common(ctx, b, m, ins[0].dev[s], ins[1].dev[s], &dvo, params, is ? &dvw : nullptr, &dvi,
-			                     is ? outs[2].dev[s] : nullptr, DJB_MEM_DEVICE, is);
-		}, &taken);
-		if (taken || st != DJB_OK) return st;
-	}
-	Staged sg(ctx, n, mem);
-	View vo, vi, vw; const float *d1, *d2; float *dpdf = nullptr;
-	if ((st = sg.in_f(u1, &d1)) != DJB_OK) return st;
-	if ((st = sg.in_f(u2, &d2)) != DJB_OK) return st;
-	if ((st = sg.in_vec(o, &vo)) != DJB_OK) return st;
-	if ((st = sg.out_vec(out_i, &vi)) != DJB_OK) return st;
-	if (is) {
-		if ((st = sg.out_vec(out_w, &vw)) != DJB_OK) return st;
-		if ((st = sg.out_arr(out_pdf, &dpdf)) != DJB_OK) return st;
-	}
+	CallArrays A;
+	const int k1 = A.in(u1), k2 = A.in(u2), ko = A.in(o), ki = A.out(out_i), kw = is ? A.out(out_w) : -1, kp = is ? A.out(out_pdf) : -1;
 	// DJB_OPT_CONTRACT_1E5 reaches `sample` of a Beckmann lobe (directions within 1e-5 per component) and the weight / pdf of
 	// evalp_is (GGX, Beckmann) -- for the reference's own direction: the pdf moves by 1e-3 for a 1e-5 change of direction
-	HIP_TRY(djbk::launch_sample(ctx->stream, b->dev, p, n, d1, d2, 0, 0, 0, vo, vi, is ? &vw : nullptr, dpdf, ctx->contract_1e5));
-	return sg.finish();
+	return run_call(ctx, n, mem, true, A, [&](long long m) {
+		const View vw = A.view(kw);
+		HIP_TRY(djbk::launch_sample(ctx->stream, b->dev, p, m, A.arr(k1), A.arr(k2), 0, 0, 0, A.view(ko), A.view(ki), is ? &vw : nullptr, A.arr(kp), ctx->contract_1e5));
+		return DJB_OK;
+	});
 }
 
 djb_status djb_sample_batch(djb_ctx *ctx, const djb_brdf *b, int64_t n, const float *u1, const float *u2,
@@ -443,45 +543,22 @@ static djb_status evalp_is_proxy_common(djb_ctx *ctx, const djb_brdf *target, co
 {
 	if (!target || !proxy) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null brdf (%s)", !target ? "target" : "proxy");
 	if (!ctx) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null ctx");
-	djb_status st = cpu_pair_check(ctx, target);
-	if (st != DJB_OK) return st;
-	if ((st = cpu_pair_check(ctx, proxy)) != DJB_OK) return st;
-	if (is_cpu(ctx)) return djbcpu::evalp_is_proxy(ctx, target, proxy, n, u1, u2, o, target_params, proxy_params, out_w, out_i, out_pdf);
-	if (target->ctx != proxy->ctx || target->device != proxy->device)
-		return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: target and proxy belong to different contexts");
-	if (const djb_brdf *tt = scalar_twin(ctx, target, n, mem)) {
-		const djb_brdf *pt = scalar_twin(ctx, proxy, n, mem);
-		if (pt) return djbcpu::evalp_is_proxy(djbcpu::twin_ctx(), tt, pt, n, u1, u2, o, target_params, proxy_params, out_w, out_i, out_pdf);
-	}
-	if ((st = check_call(ctx, target, n, mem)) != DJB_OK) return st;
-	if ((st = check_call(ctx, proxy, n, mem)) != DJB_OK) return st;
-	if (!djbk::evalp_is_proxy_supported(target->dev.kind, proxy->dev.kind) || (target->dev.kind == DJB_KIND_MERL && target->dev.merl_sparse))
-		return fail(DJB_ERR_NOT_IMPLEMENTED, "djb_error: evalp_is_proxy on the GPU takes a merl / utia / sgd / abc target and a ggx / beckmann / tabular / "
-		            "tabular_anisotropic proxy (target kind %d, proxy kind %d)", target->dev.kind, proxy->dev.kind);
+	bool on_gpu;
+	djb_status st = proxy_pair_checks("evalp_is_proxy", ctx, target, proxy, n, mem, [&](djb_ctx *c, const djb_brdf *t, const djb_brdf *p) {
+		return djbcpu::evalp_is_proxy(c, t, p, n, u1, u2, o, target_params, proxy_params, out_w, out_i, out_pdf);
+	}, &on_gpu);
+	if (!on_gpu) return st;
 	std::lock_guard<std::recursive_mutex> call_lock(ctx->call_mu);
 	Params tp, pp;
 	if ((st = device_params(target_params, &tp, target->dev.kind)) != DJB_OK) return st;
 	if ((st = device_params(proxy_params, &pp, proxy->dev.kind)) != DJB_OK) return st;
-	if (mem == DJB_MEM_HOST && n > SMALL_N && u1 && u2 && o && out_i && out_w && out_pdf) {   // large host batch: chunked, both PCIe directions busy
-		bool taken = false;
-		std::vector<PipeArr> ins{ PipeArr::arr(u1), PipeArr::arr(u2), PipeArr::vec(o) }, outs{ PipeArr::vec(out_i), PipeArr::vec(out_w), PipeArr::arr(out_pdf) };
-		st = host_pipeline(ctx, n, ins, outs, [&](long long m, int s) {
-			djb_vec3_view dvo = ins[2].view(s), dvi = outs[0].view(s), dvw = outs[1].view(s);
-			return evalp_is_proxy_common(ctx, target, proxy, m, ins[0].dev[s], ins[1].dev[s], &dvo, target_params, proxy_params, &dvw, &dvi,
-			                             outs[2].dev[s], DJB_MEM_DEVICE);
-		}, &taken);
-		if (taken || st != DJB_OK) return st;
-	}
-	Staged sg(ctx, n, mem);
-	View vo, vi, vw; const float *d1, *d2; float *dpdf = nullptr;
-	if ((st = sg.in_f(u1, &d1)) != DJB_OK) return st;
-	if ((st = sg.in_f(u2, &d2)) != DJB_OK) return st;
-	if ((st = sg.in_vec(o, &vo)) != DJB_OK) return st;
-	if ((st = sg.out_vec(out_i, &vi)) != DJB_OK) return st;
-	if ((st = sg.out_vec(out_w, &vw)) != DJB_OK) return st;
-	if ((st = sg.out_arr(out_pdf, &dpdf)) != DJB_OK) return st;
-	HIP_TRY(djbk::launch_evalp_is_proxy(ctx->stream, target->dev, tp, proxy->dev, pp, n, d1, d2, vo, vw, vi, dpdf, ctx->merl_exact_only != 0));
-	return sg.finish();
+	CallArrays A;
+	const int k1 = A.in(u1), k2 = A.in(u2), ko = A.in(o), ki = A.out(out_i), kw = A.out(out_w), kp = A.out(out_pdf);
+	return run_call(ctx, n, mem, true, A, [&](long long m) {
+		HIP_TRY(djbk::launch_evalp_is_proxy(ctx->stream, target->dev, tp, proxy->dev, pp, m, A.arr(k1), A.arr(k2), A.view(ko), A.view(kw), A.view(ki), A.arr(kp),
+		                                    ctx->merl_exact_only != 0));
+		return DJB_OK;
+	});
 }
 
 djb_status djb_evalp_is_proxy_batch(djb_ctx *ctx, const djb_brdf *target, const djb_brdf *proxy, int64_t n, const float *u1, const float *u2,
@@ -503,42 +580,21 @@ static djb_status evalp_pdf_proxy_common(djb_ctx *ctx, const djb_brdf *target, c
 	if (!ctx) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null ctx");
 	if (!out_fr) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null out_fr (the pdf alone: djb_pdf_batch)");
 	if (!out_pdf) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null out_pdf (evalp alone: djb_evalp_batch)");
-	djb_status st = cpu_pair_check(ctx, target);
-	if (st != DJB_OK) return st;
-	if ((st = cpu_pair_check(ctx, proxy)) != DJB_OK) return st;
-	if (is_cpu(ctx)) return djbcpu::evalp_pdf_proxy(ctx, target, proxy, n, i, o, target_params, proxy_params, out_fr, out_pdf);
-	if (target->ctx != proxy->ctx || target->device != proxy->device)
-		return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: target and proxy belong to different contexts");
-	if (const djb_brdf *tt = scalar_twin(ctx, target, n, mem)) {
-		const djb_brdf *pt = scalar_twin(ctx, proxy, n, mem);
-		if (pt) return djbcpu::evalp_pdf_proxy(djbcpu::twin_ctx(), tt, pt, n, i, o, target_params, proxy_params, out_fr, out_pdf);
-	}
-	if ((st = check_call(ctx, target, n, mem)) != DJB_OK) return st;
-	if ((st = check_call(ctx, proxy, n, mem)) != DJB_OK) return st;
-	if (!djbk::evalp_is_proxy_supported(target->dev.kind, proxy->dev.kind) || (target->dev.kind == DJB_KIND_MERL && target->dev.merl_sparse))
-		return fail(DJB_ERR_NOT_IMPLEMENTED, "djb_error: evalp_pdf_proxy on the GPU takes a merl / utia / sgd / abc target and a ggx / beckmann / tabular / "
-		            "tabular_anisotropic proxy (target kind %d, proxy kind %d)", target->dev.kind, proxy->dev.kind);
+	bool on_gpu;
+	djb_status st = proxy_pair_checks("evalp_pdf_proxy", ctx, target, proxy, n, mem, [&](djb_ctx *c, const djb_brdf *t, const djb_brdf *p) {
+		return djbcpu::evalp_pdf_proxy(c, t, p, n, i, o, target_params, proxy_params, out_fr, out_pdf);
+	}, &on_gpu);
+	if (!on_gpu) return st;
 	std::lock_guard<std::recursive_mutex> call_lock(ctx->call_mu);
 	Params tp, pp;
 	if ((st = device_params(target_params, &tp, target->dev.kind)) != DJB_OK) return st;
 	if ((st = device_params(proxy_params, &pp, proxy->dev.kind)) != DJB_OK) return st;
-	if (mem == DJB_MEM_HOST && n > SMALL_N && i && o) {                          // large host batch: chunked, both PCIe directions busy
-		bool taken = false;
-		std::vector<PipeArr> ins{ PipeArr::vec(i), PipeArr::vec(o) }, outs{ PipeArr::vec(out_fr), PipeArr::arr(out_pdf) };
-		st = host_pipeline(ctx, n, ins, outs, [&](long long m, int s) {
-			djb_vec3_view dvi = ins[0].view(s), dvo = ins[1].view(s), dvf = outs[0].view(s);
-			return evalp_pdf_proxy_common(ctx, target, proxy, m, &dvi, &dvo, target_params, proxy_params, &dvf, outs[1].dev[s], DJB_MEM_DEVICE);
-		}, &taken);
-		if (taken || st != DJB_OK) return st;
-	}
-	Staged sg(ctx, n, mem);
-	View vi, vo, vout; float *dpdf = nullptr;
-	if ((st = sg.in_vec(i, &vi)) != DJB_OK) return st;
-	if ((st = sg.in_vec(o, &vo)) != DJB_OK) return st;
-	if ((st = sg.out_vec(out_fr, &vout)) != DJB_OK) return st;
-	if ((st = sg.out_arr(out_pdf, &dpdf)) != DJB_OK) return st;
-	HIP_TRY(djbk::launch_evalp_pdf_proxy(ctx->stream, target->dev, tp, proxy->dev, pp, n, vi, vo, vout, dpdf, ctx->merl_exact_only != 0));
-	return sg.finish();
+	CallArrays A;
+	const int ki = A.in(i), ko = A.in(o), kf = A.out(out_fr), kp = A.out(out_pdf);
+	return run_call(ctx, n, mem, true, A, [&](long long m) {
+		HIP_TRY(djbk::launch_evalp_pdf_proxy(ctx->stream, target->dev, tp, proxy->dev, pp, m, A.view(ki), A.view(ko), A.view(kf), A.arr(kp), ctx->merl_exact_only != 0));
+		return DJB_OK;
+	});
 }
 
 djb_status djb_evalp_pdf_proxy_batch(djb_ctx *ctx, const djb_brdf *target, const djb_brdf *proxy, int64_t n, const djb_vec3_view *i,
@@ -576,7 +632,7 @@ static djb_status hd_common(djb_ctx *ctx, int64_t n, const djb_vec3_view *a, con
 {
 	if (!ctx) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null ctx");
 	if (is_cpu(ctx)) return djbcpu::io_hd(ctx, n, a, b, c, d, inverse);
-	if (mem == DJB_MEM_HOST && n >= 0 && n <= ctx->host_batch_max && !ctx->scalar_on_device) return djbcpu::io_hd(djbcpu::twin_ctx(), n, a, b, c, d, inverse);
+	if (scalar_sized(ctx, n, mem)) return djbcpu::io_hd(djbcpu::twin_ctx(), n, a, b, c, d, inverse);
 	djb_status st = check_call(ctx, nullptr, n, mem);
 	if (st != DJB_OK) return st;
 	std::lock_guard<std::recursive_mutex> call_lock(ctx->call_mu);
@@ -648,42 +704,33 @@ try {
 }
 DJB_ABI_CATCH
 
+// merl_index, and with `keys` the tier-1 bin keys.  The host path has no fast tier: its keys are the exact indices (a key equals
+// merl_index wherever tier 1 is certain -- always, here)
+static djb_status merl_index_common(djb_ctx *ctx, int64_t n, const djb_vec3_view *i, const djb_vec3_view *o, int32_t *out, int mem, bool keys)
+{
+	if (!ctx) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null ctx");
+	if (is_cpu(ctx)) return djbcpu::merl_index(ctx, n, i, o, out);
+	if (scalar_sized(ctx, n, mem)) return djbcpu::merl_index(djbcpu::twin_ctx(), n, i, o, out);
+	djb_status st = check_call(ctx, nullptr, n, mem);
+	if (st != DJB_OK) return st;
+	std::lock_guard<std::recursive_mutex> call_lock(ctx->call_mu);
+	Staged sg(ctx, n, mem);
+	View vi, vo; int32_t *d;
+	if ((st = sg.in_vec(i, &vi)) != DJB_OK) return st;
+	if ((st = sg.in_vec(o, &vo)) != DJB_OK) return st;
+	if ((st = sg.out_arr(out, &d)) != DJB_OK) return st;
+	HIP_TRY(keys ? djbk::launch_merl_keys(ctx->stream, n, vi, vo, reinterpret_cast<uint32_t *>(d)) : djbk::launch_merl_index(ctx->stream, n, vi, vo, d));
+	return sg.finish();
+}
 djb_status djb_merl_index_batch(djb_ctx *ctx, int64_t n, const djb_vec3_view *i, const djb_vec3_view *o,
                                 int32_t *out_index, int mem)
 try {
-	if (!ctx) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null ctx");
-	if (is_cpu(ctx)) return djbcpu::merl_index(ctx, n, i, o, out_index);
-	if (mem == DJB_MEM_HOST && n >= 0 && n <= ctx->host_batch_max && !ctx->scalar_on_device) return djbcpu::merl_index(djbcpu::twin_ctx(), n, i, o, out_index);
-	djb_status st = check_call(ctx, nullptr, n, mem);
-	if (st != DJB_OK) return st;
-	std::lock_guard<std::recursive_mutex> call_lock(ctx->call_mu);
-	Staged sg(ctx, n, mem);
-	View vi, vo; int32_t *didx;
-	if ((st = sg.in_vec(i, &vi)) != DJB_OK) return st;
-	if ((st = sg.in_vec(o, &vo)) != DJB_OK) return st;
-	if ((st = sg.out_arr(out_index, &didx)) != DJB_OK) return st;
-	HIP_TRY(djbk::launch_merl_index(ctx->stream, n, vi, vo, didx));
-	return sg.finish();
+	return merl_index_common(ctx, n, i, o, out_index, mem, false);
 }
 DJB_ABI_CATCH
-
 djb_status djb_merl_bin_keys_batch(djb_ctx *ctx, int64_t n, const djb_vec3_view *i, const djb_vec3_view *o, uint32_t *out_keys, int mem)
 try {
-	if (!ctx) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null ctx");
-	// the host path has no fast tier: its keys are the exact indices (a key equals merl_index wherever tier 1 is certain -- always, here)
-	if (is_cpu(ctx)) return djbcpu::merl_index(ctx, n, i, o, reinterpret_cast<int32_t *>(out_keys));
-	if (mem == DJB_MEM_HOST && n >= 0 && n <= ctx->host_batch_max && !ctx->scalar_on_device)
-		return djbcpu::merl_index(djbcpu::twin_ctx(), n, i, o, reinterpret_cast<int32_t *>(out_keys));
-	djb_status st = check_call(ctx, nullptr, n, mem);
-	if (st != DJB_OK) return st;
-	std::lock_guard<std::recursive_mutex> call_lock(ctx->call_mu);
-	Staged sg(ctx, n, mem);
-	View vi, vo; int32_t *dkeys;
-	if ((st = sg.in_vec(i, &vi)) != DJB_OK) return st;
-	if ((st = sg.in_vec(o, &vo)) != DJB_OK) return st;
-	if ((st = sg.out_arr(reinterpret_cast<int32_t *>(out_keys), &dkeys)) != DJB_OK) return st;
-	HIP_TRY(djbk::launch_merl_keys(ctx->stream, n, vi, vo, reinterpret_cast<uint32_t *>(dkeys)));
-	return sg.finish();
+	return merl_index_common(ctx, n, i, o, reinterpret_cast<int32_t *>(out_keys), mem, true);
 }
 DJB_ABI_CATCH
 
@@ -767,17 +814,15 @@ try {
 }
 DJB_ABI_CATCH
 
-// mode 2 (the fused LEAN-map calls): the records are looked up in `hit->map` at (hit->uv, hit->lod); `rec` is not used
-struct LeanHit { const djb_leanmap *map; const float *uv, *lod; };
-// the host path's form of a mode 2 call: the records by the host lookup, then mode 1 (what the kernels do per lane)
-static djb_status leanmap_host_records(const djb_ctx *ctx, const LeanHit *hit, int64_t n, std::vector<float> *rec)
+// the LEAN arguments of the _lean_ and _leanmap_ entries: `allowed` is the mask of DJB_LEAN_* flags the entry takes (a LEAN map holds the
+// unbiased moments); lrep::operator*= asserts sc >= 0, dj_brdf.h:2024; base5 = lrep2, dj_beckmannconductor.cpp:312
+static djb_status lean_call_args(int allowed, float scale, int lean_flags, const djb_params *base, float *base5)
 {
-	const float *texels;
-	djb_status st = leanmap_host_texels(hit->map, &texels);
-	if (st != DJB_OK) return st;
-	rec->resize(5 * (size_t)n);
-	djbcpu::leanmap_lookup(is_cpu(ctx) ? const_cast<djb_ctx *>(ctx) : djbcpu::twin_ctx(), texels, hit->map->lw, hit->map->lh, n, hit->uv, hit->lod, rec->data());
-	return DJB_OK;
+	if (lean_flags & DJB_LEAN_BIASED & ~allowed)
+		return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: DJB_LEAN_BIASED does not apply to a LEAN map (it holds the unbiased moments)");
+	if (lean_flags & ~allowed) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: unknown LEAN flag");
+	if (!(scale >= 0.0f)) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: Invalid scale");
+	return djb_params_to_lrep(base, base5);
 }
 
 static djb_status eval_pp_common(djb_ctx *ctx, const djb_brdf *b, int64_t n, const djb_vec3_view *i,
@@ -791,62 +836,22 @@ static djb_status eval_pp_common(djb_ctx *ctx, const djb_brdf *b, int64_t n, con
 		return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: per-pair params need a microfacet brdf");
 	if (want != 1 && want != 2 && want != 4 && want != 5 && want != 6)
 		return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: want must be eval(1)|evalp(2) and/or pdf(4)");
-	djb_status st = cpu_pair_check(ctx, b);
-	if (st != DJB_OK) return st;
-	if (hit && (st = leanmap_check(ctx, hit->map)) != DJB_OK) return st;
-	if (n < 0 && hit) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: negative batch size");
-	const djb_brdf *tw = is_cpu(ctx) ? nullptr : scalar_twin(ctx, b, n, mem);
-	if (is_cpu(ctx) || tw) {
-		if (n <= 0) return DJB_OK;
-		std::vector<float> looked_up;
-		if (hit) { if ((st = leanmap_host_records(ctx, hit, n, &looked_up)) != DJB_OK) return st; rec = looked_up.data(); mode = 1; }
-		return is_cpu(ctx) ? djbcpu::eval_pp(ctx, b, n, i, o, rec, mode, base5, scale, lean_flags, want, out_fr, out_pdf, out_pp)
-		                   : djbcpu::eval_pp(djbcpu::twin_ctx(), tw, n, i, o, rec, mode, base5, scale, lean_flags, want, out_fr, out_pdf, out_pp);
-	}
-	st = check_call(ctx, b, n, mem);
-	if (st != DJB_OK) return st;
+	bool on_gpu;
+	djb_status st = pp_checks(ctx, b, n, mem, hit, rec, mode, [&](djb_ctx *c, const djb_brdf *bb, const float *r, int md) {
+		return djbcpu::eval_pp(c, bb, n, i, o, r, md, base5, scale, lean_flags, want, out_fr, out_pdf, out_pp);
+	}, &on_gpu);
+	if (!on_gpu) return st;
 	std::lock_guard<std::recursive_mutex> call_lock(ctx->call_mu);
-	if (!hit && mem == DJB_MEM_HOST && n > SMALL_N && i && o && (!(want & 3) || out_fr)) {   // large host batch: chunked, both PCIe directions busy
-		bool taken = false;
-		const bool wfr = (want & 3) != 0, wpdf = (want & 4) != 0;
-		std::vector<PipeArr> ins{ PipeArr::vec(i), PipeArr::vec(o), PipeArr::arr(rec, 5) }, outs;
-		int kf = -1, kp = -1, kq = -1;
-		if (wfr) { kf = (int)outs.size(); outs.push_back(PipeArr::vec(out_fr)); }
-		if (wpdf) { kp = (int)outs.size(); outs.push_back(PipeArr::arr(out_pdf)); }
-		if (out_pp) { kq = (int)outs.size(); outs.push_back(PipeArr::arr(out_pp, 5)); }
-		st = host_pipeline(ctx, n, ins, outs, [&](long long m, int s) {
-			djb_vec3_view dvi = ins[0].view(s), dvo = ins[1].view(s), dvf = wfr ? outs[kf].view(s) : djb_vec3_view{ nullptr, nullptr, nullptr, 0 };
-			return eval_pp_common(ctx, b, m, &dvi, &dvo, ins[2].dev[s], mode, base5, scale, lean_flags, want, wfr ? &dvf : nullptr,
-			                      wpdf ? outs[kp].dev[s] : nullptr, out_pp ? outs[kq].dev[s] : nullptr, DJB_MEM_DEVICE);
-		}, &taken);
-		if (taken || st != DJB_OK) return st;
-	}
-	Staged sg(ctx, n, mem);
-	View vi, vo, vout{ nullptr, nullptr, nullptr, 0 };
-	float *dpdf = nullptr, *dpp = nullptr; const float *drec = rec;
-	if ((st = sg.in_vec(i, &vi)) != DJB_OK) return st;
-	if ((st = sg.in_vec(o, &vo)) != DJB_OK) return st;
-	djbdev::LeanSrc src{ { nullptr, 0, 0 }, nullptr, nullptr };
-	if (hit) {
-		src.map = djbdev::LeanMap{ hit->map->dev, hit->map->lw, hit->map->lh };
-		if ((st = stage_leanmap_coords(sg, hit->uv, hit->lod, &src)) != DJB_OK) return st;
-	} else if (mem == DJB_MEM_HOST) {
-		float *d = nullptr;
-		if ((st = sg.alloc(sizeof(float) * 5 * (size_t)n, (void **)&d)) != DJB_OK) return st;
-		if (n && (st = sg.copy(d, rec, sizeof(float) * 5 * (size_t)n, hipMemcpyHostToDevice)) != DJB_OK) return st;
-		drec = d;
-	}
-	if ((want & 3) && (st = sg.out_vec(out_fr, &vout)) != DJB_OK) return st;
-	if ((want & 4) && (st = sg.out_arr(out_pdf, &dpdf)) != DJB_OK) return st;
-	if (out_pp) {
-		if (mem == DJB_MEM_DEVICE) dpp = out_pp;
-		else {
-			if ((st = sg.alloc(sizeof(float) * 5 * (size_t)n, (void **)&dpp)) != DJB_OK) return st;
-			sg.out_raw.push_back({ dpp, { out_pp, sizeof(float) * 5 * (size_t)n } });
-		}
-	}
-	HIP_TRY(djbk::launch_eval_pp(ctx->stream, b->dev, n, vi, vo, drec, mode, base5, scale, lean_flags, vout, dpdf, dpp, want, hit ? &src : nullptr));
-	return sg.finish();
+	CallArrays A;
+	const int ki = A.in(i), ko = A.in(o);
+	const PpSource ks(A, hit, rec);
+	const int kf = (want & 3) ? A.out(out_fr) : -1, kp = (want & 4) ? A.out(out_pdf) : -1, kq = out_pp ? A.out(out_pp, 5) : -1;
+	return run_call(ctx, n, mem, !hit, A, [&](long long m) {
+		const djbdev::LeanSrc src = ks.lean_src(A);
+		HIP_TRY(djbk::launch_eval_pp(ctx->stream, b->dev, m, A.view(ki), A.view(ko), ks.rec(A), mode, base5, scale, lean_flags, A.view(kf), A.arr(kp), A.arr(kq), want,
+		                             hit ? &src : nullptr));
+		return DJB_OK;
+	});
 }
 
 djb_status djb_eval_pp_batch(djb_ctx *ctx, const djb_brdf *b, int64_t n, const djb_vec3_view *i,
@@ -862,11 +867,8 @@ djb_status djb_eval_lean_batch(djb_ctx *ctx, const djb_brdf *b, int64_t n, const
                                const float *lean, int want, const djb_vec3_view *out_fr, float *out_pdf,
                                float *out_pdfparams, int mem)
 try {
-	if (lean_flags & ~(DJB_LEAN_NAIVE_MIP | DJB_LEAN_BIASED))
-		return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: unknown LEAN flag");
-	if (!(scale >= 0.0f)) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: Invalid scale");   // lrep::operator*= asserts sc >= 0, dj_brdf.h:2024
 	float base5[5];
-	djb_status st = djb_params_to_lrep(base, base5);                                           // lrep2, dj_beckmannconductor.cpp:312
+	djb_status st = lean_call_args(DJB_LEAN_NAIVE_MIP | DJB_LEAN_BIASED, scale, lean_flags, base, base5);
 	if (st != DJB_OK) return st;
 	return eval_pp_common(ctx, b, n, i, o, lean, 1, base5, scale, lean_flags, want, out_fr, out_pdf, out_pdfparams, mem);
 }
@@ -884,63 +886,23 @@ static djb_status sample_pp_common(djb_ctx *ctx, const djb_brdf *b, int64_t n, c
 		return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: per-pair params need a microfacet brdf");
 	const bool is = out_w != nullptr;
 	if (is && !out_pdf) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null argument");
-	djb_status st = cpu_pair_check(ctx, b);
-	if (st != DJB_OK) return st;
-	if (hit && (st = leanmap_check(ctx, hit->map)) != DJB_OK) return st;
-	if (n < 0 && hit) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: negative batch size");
-	const djb_brdf *tw = is_cpu(ctx) ? nullptr : scalar_twin(ctx, b, n, mem);
-	if (is_cpu(ctx) || tw) {
-		if (n <= 0) return DJB_OK;
-		std::vector<float> looked_up;
-		if (hit) { if ((st = leanmap_host_records(ctx, hit, n, &looked_up)) != DJB_OK) return st; rec = looked_up.data(); mode = 1; }
-		return is_cpu(ctx) ? djbcpu::sample_pp(ctx, b, n, u1, u2, o, rec, mode, base5, scale, lean_flags, out_w, out_i, out_pdf, out_pp)
-		                   : djbcpu::sample_pp(djbcpu::twin_ctx(), tw, n, u1, u2, o, rec, mode, base5, scale, lean_flags, out_w, out_i, out_pdf, out_pp);
-	}
-	st = check_call(ctx, b, n, mem);
-	if (st != DJB_OK) return st;
+	bool on_gpu;
+	djb_status st = pp_checks(ctx, b, n, mem, hit, rec, mode, [&](djb_ctx *c, const djb_brdf *bb, const float *r, int md) {
+		return djbcpu::sample_pp(c, bb, n, u1, u2, o, r, md, base5, scale, lean_flags, out_w, out_i, out_pdf, out_pp);
+	}, &on_gpu);
+	if (!on_gpu) return st;
 	std::lock_guard<std::recursive_mutex> call_lock(ctx->call_mu);
-	if (!hit && mem == DJB_MEM_HOST && n > SMALL_N && o && out_i) {          // large host batch: chunked, both PCIe directions busy
-		bool taken = false;
-		std::vector<PipeArr> ins{ PipeArr::arr(u1), PipeArr::arr(u2), PipeArr::vec(o), PipeArr::arr(rec, 5) }, outs{ PipeArr::vec(out_i) };
-		int kq = -1;
-		if (is) { outs.push_back(PipeArr::vec(out_w)); outs.push_back(PipeArr::arr(out_pdf)); }
-		if (out_pp) { kq = (int)outs.size(); outs.push_back(PipeArr::arr(out_pp, 5)); }
-		st = host_pipeline(ctx, n, ins, outs, [&](long long m, int s) {
-			djb_vec3_view dvo = ins[2].view(s), dvi = outs[0].view(s), dvw = is ? outs[1].view(s) : djb_vec3_view{ nullptr, nullptr, nullptr, 0 };
-			return sample_pp_common(ctx, b, m, ins[0].dev[s], ins[1].dev[s], &dvo, ins[3].dev[s], mode, base5, scale, lean_flags,
-			                        is ? &dvw : nullptr, &dvi, is ? outs[2].dev[s] : nullptr, out_pp ? outs[kq].dev[s] : nullptr, DJB_MEM_DEVICE);
-		}, &taken);
-		if (taken || st != DJB_OK) return st;
-	}
-	Staged sg(ctx, n, mem);
-	View vo, vi, vw; const float *d1, *d2, *drec = rec; float *dpdf = nullptr, *dpp = nullptr;
-	if ((st = sg.in_f(u1, &d1)) != DJB_OK) return st;
-	if ((st = sg.in_f(u2, &d2)) != DJB_OK) return st;
-	if ((st = sg.in_vec(o, &vo)) != DJB_OK) return st;
-	djbdev::LeanSrc src{ { nullptr, 0, 0 }, nullptr, nullptr };
-	if (hit) {
-		src.map = djbdev::LeanMap{ hit->map->dev, hit->map->lw, hit->map->lh };
-		if ((st = stage_leanmap_coords(sg, hit->uv, hit->lod, &src)) != DJB_OK) return st;
-	} else if (mem == DJB_MEM_HOST) {
-		float *d = nullptr;
-		if ((st = sg.alloc(sizeof(float) * 5 * (size_t)n, (void **)&d)) != DJB_OK) return st;
-		if (n && (st = sg.copy(d, rec, sizeof(float) * 5 * (size_t)n, hipMemcpyHostToDevice)) != DJB_OK) return st;
-		drec = d;
-	}
-	if ((st = sg.out_vec(out_i, &vi)) != DJB_OK) return st;
-	if (is) {
-		if ((st = sg.out_vec(out_w, &vw)) != DJB_OK) return st;
-		if ((st = sg.out_arr(out_pdf, &dpdf)) != DJB_OK) return st;
-	}
-	if (out_pp) {
-		if (mem == DJB_MEM_DEVICE) dpp = out_pp;
-		else {
-			if ((st = sg.alloc(sizeof(float) * 5 * (size_t)n, (void **)&dpp)) != DJB_OK) return st;
-			sg.out_raw.push_back({ dpp, { out_pp, sizeof(float) * 5 * (size_t)n } });
-		}
-	}
-	HIP_TRY(djbk::launch_sample_pp(ctx->stream, b->dev, n, d1, d2, vo, drec, mode, base5, scale, lean_flags, vi, is ? &vw : nullptr, dpdf, dpp, hit ? &src : nullptr));
-	return sg.finish();
+	CallArrays A;
+	const int k1 = A.in(u1), k2 = A.in(u2), ko = A.in(o);
+	const PpSource ks(A, hit, rec);
+	const int ki = A.out(out_i), kw = is ? A.out(out_w) : -1, kp = is ? A.out(out_pdf) : -1, kq = out_pp ? A.out(out_pp, 5) : -1;
+	return run_call(ctx, n, mem, !hit, A, [&](long long m) {
+		const djbdev::LeanSrc src = ks.lean_src(A);
+		const View vw = A.view(kw);
+		HIP_TRY(djbk::launch_sample_pp(ctx->stream, b->dev, m, A.arr(k1), A.arr(k2), A.view(ko), ks.rec(A), mode, base5, scale, lean_flags, A.view(ki), is ? &vw : nullptr,
+		                               A.arr(kp), A.arr(kq), hit ? &src : nullptr));
+		return DJB_OK;
+	});
 }
 
 djb_status djb_sample_pp_batch(djb_ctx *ctx, const djb_brdf *b, int64_t n, const float *u1, const float *u2,
@@ -956,31 +918,20 @@ djb_status djb_sample_lean_batch(djb_ctx *ctx, const djb_brdf *b, int64_t n, con
                                  const float *lean, const djb_vec3_view *out_w, const djb_vec3_view *out_i,
                                  float *out_pdf, float *out_pdfparams, int mem)
 try {
-	if (lean_flags & ~(DJB_LEAN_NAIVE_MIP | DJB_LEAN_BIASED))
-		return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: unknown LEAN flag");
-	if (!(scale >= 0.0f)) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: Invalid scale");
 	float base5[5];
-	djb_status st = djb_params_to_lrep(base, base5);
+	djb_status st = lean_call_args(DJB_LEAN_NAIVE_MIP | DJB_LEAN_BIASED, scale, lean_flags, base, base5);
 	if (st != DJB_OK) return st;
 	return sample_pp_common(ctx, b, n, u1, u2, o, lean, 1, base5, scale, lean_flags, out_w, out_i, out_pdf, out_pdfparams, mem);
 }
 DJB_ABI_CATCH
 
 // the fused LEAN-map calls: per hit, the filtered lookup of the resident map, then what the _lean_ entries do with that record
-static djb_status leanmap_call_args(float scale, int lean_flags, const djb_params *base, float *base5)
-{
-	if (lean_flags & DJB_LEAN_BIASED) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: DJB_LEAN_BIASED does not apply to a LEAN map (it holds the unbiased moments)");
-	if (lean_flags & ~DJB_LEAN_NAIVE_MIP) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: unknown LEAN flag");
-	if (!(scale >= 0.0f)) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: Invalid scale");
-	return djb_params_to_lrep(base, base5);
-}
-
 djb_status djb_eval_leanmap_batch(djb_ctx *ctx, const djb_brdf *b, const djb_leanmap *map, int64_t n, const djb_vec3_view *i,
                                   const djb_vec3_view *o, const float *uv, const float *lod, const djb_params *base, float scale,
                                   int lean_flags, int want, const djb_vec3_view *out_fr, float *out_pdf, float *out_pdfparams, int mem)
 try {
 	float base5[5];
-	djb_status st = leanmap_call_args(scale, lean_flags, base, base5);
+	djb_status st = lean_call_args(DJB_LEAN_NAIVE_MIP, scale, lean_flags, base, base5);
 	if (st != DJB_OK) return st;
 	if (!map) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null leanmap");
 	const LeanHit hit{ map, uv, lod };
@@ -994,7 +945,7 @@ djb_status djb_sample_leanmap_batch(djb_ctx *ctx, const djb_brdf *b, const djb_l
                                     float *out_pdfparams, int mem)
 try {
 	float base5[5];
-	djb_status st = leanmap_call_args(scale, lean_flags, base, base5);
+	djb_status st = lean_call_args(DJB_LEAN_NAIVE_MIP, scale, lean_flags, base, base5);
 	if (st != DJB_OK) return st;
 	if (!map) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: null leanmap");
 	const LeanHit hit{ map, uv, lod };

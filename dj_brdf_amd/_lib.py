@@ -42,6 +42,10 @@ class FresnelDesc(C.Structure):
                 ("points", C.c_void_p), ("npoints", C.c_int)]
 
 
+class MicrofacetMaterial(C.Structure):
+    _fields_ = [("fresnel", FresnelDesc), ("shadow", C.c_int), ("params", Params)]
+
+
 class SceneSlot(C.Structure):
     _fields_ = [("kind", C.c_int32), ("local", C.c_int32)]
 
@@ -83,6 +87,8 @@ EXPORTS = [
     "djb_model_set_evalp_pdf_proxy_batch",
     "djb_scene_create", "djb_scene_info", "djb_scene_destroy", "djb_scene_eval_batch",
     "djb_utia_set_set_proxy_params", "djb_utia_set_proxy_info", "djb_scene_evalp_is_proxy_batch", "djb_scene_evalp_pdf_proxy_batch",
+    "djb_microfacet_set_create", "djb_microfacet_set_create_from_brdfs", "djb_microfacet_set_set_params", "djb_microfacet_set_info",
+    "djb_microfacet_set_destroy", "djb_microfacet_set_eval_batch", "djb_microfacet_set_sample_batch",
 ]
 
 _lib = None
@@ -133,6 +139,13 @@ def load() -> C.CDLL:
     lib.djb_utia_set_proxy_info.argtypes = [P, P]
     lib.djb_scene_evalp_is_proxy_batch.argtypes = [P, P, P, C.c_int64, P, P, P, P, P, P, P, C.c_int]
     lib.djb_scene_evalp_pdf_proxy_batch.argtypes = [P, P, P, C.c_int64, P, P, P, P, P, C.c_int]
+    lib.djb_microfacet_set_create.argtypes = [P, C.c_int, C.c_int, P, P]
+    lib.djb_microfacet_set_create_from_brdfs.argtypes = [P, C.c_int, P, P, P]
+    lib.djb_microfacet_set_set_params.argtypes = [P, P]
+    lib.djb_microfacet_set_info.argtypes = [P, P, P]
+    lib.djb_microfacet_set_destroy.argtypes = [P]
+    lib.djb_microfacet_set_eval_batch.argtypes = [P, P, C.c_int64, P, P, P, C.c_int, P, P, C.c_int]
+    lib.djb_microfacet_set_sample_batch.argtypes = [P, P, C.c_int64, P, P, P, P, P, P, P, C.c_int]
     if lib.djb_version() // 100 != ABI_VERSION // 100:
         raise ImportError(f"{LIB_PATH} has ABI version {lib.djb_version()}, this binding was written against {ABI_VERSION} "
                           "(include/djb_hip.h: DJB_HIP_VERSION) -- rebuild the library")

@@ -5,6 +5,7 @@
 // phase with the sums in the reference's order (dj_brdf.h:2215-2762, 3133-3184).
 #define DJB_HOST_MATH 1
 #include "djb_device.hpp"
+#include "djb_microfacet_row.hpp"
 #include "djb_cpu.hpp"
 #include "djb_merl_file.hpp"
 
@@ -963,9 +964,9 @@ djb_status evalp_pdf_proxy(djb_ctx *ctx, const djb_brdf *target, const djb_brdf 
 }
 
 // ------------------------------------------------------------------ material sets (MERL, UTIA, SGD / ABC) and scenes.  Three layers:
-//   a material binding per kind of set (TableMat, ModelMat) makes a lane's Brdf / Params stand for material m, and runs one hit on it: eval
+//   a material binding per kind of set (TableMat, ModelMat, LobeMat) makes a lane's Brdf / Params stand for material m, and runs one hit on it: eval
 //   (eval_one) or one of the two proxy steps (proxy_hit above); a scene's binding (SceneMat) classifies the hit and hands it to its member's;
-//   one loop per output shape (set_eval_loop, set_proxy_loop) over any binding: an id outside [0, n_mat) is an inactive hit, +0 in every
+//   one loop per output shape (set_eval_loop, set_sample_loop, set_proxy_loop) over any binding: an id outside [0, n_mat) is an inactive hit, +0 in every
 //   output and nothing read;
 //   one entry per output shape (set_eval, set_evalp_is_proxy, set_evalp_pdf) with the argument checks, behind the sets' and scenes' calls.
 // a member belongs to the set's context (`what`: "merl" / "utia" / "model"); whether it is of the set's kind is each set's own test
@@ -1052,6 +1053,26 @@ template <int KIND> struct ModelMat : MatTarget {
 		proxy_hit<KIND_TABULAR, KIND, LIGHT>(tb, tp, pb, pp, u1, u2, o, gt, i, fr, pdf);
 	}
 };
+// Microfacet sets: rows = MfRow[n_mat] of ONE NDF kind (djb_microfacet_row.hpp).  Row m becomes the lane's Params, Fresnel term and shadowing
+// flag: the object and the parameter set of the single-material call.  eval_pdf<WANT> (WANT with the pdf bit) and sample<IS> run eval_one /
+// sample_one, the calls of eval_loop / sample_loop, on them
+template <int KIND> struct LobeMat : MatTarget {
+	const MfRow *rows;
+	explicit LobeMat(const void *rows) : MatTarget(KIND), rows((const MfRow *)rows) {}
+	void bind(unsigned int m)
+	{
+		const MfRow &r = rows[m];
+		tp = r.p; tb.shadow = r.shadow; tb.fr.kind = r.fr_kind;
+		for (int c = 0; c < 3; ++c) { tb.fr.a[c] = r.a[c]; tb.fr.b[c] = r.b[c]; }
+	}
+	template <int WANT> v3 eval(unsigned int m, v3 i, v3 o) { bind(m); return eval_bound<KIND, WANT>(i, o); }
+	template <int WANT> void eval_pdf(unsigned int m, v3 i, v3 o, v3 &fr, float &pdf) { bind(m); eval_one<KIND, WANT>(tb, tp, i, o, fr, pdf); }
+	template <bool IS> void sample(unsigned int m, float u1, float u2, v3 o, const GlibcTabs &gt, v3 &i, v3 &w, float &pdf)
+	{
+		bind(m);
+		sample_one<KIND, IS>(tb, tp, u1, u2, o, gt, i, w, pdf);
+	}
+};
 // Scenes: slots = n_slots packed words (kind code 0 merl, 1 utia, 2 sgd, 3 abc in the high 16 bits, the local id in the low 16; anything
 // else: no material), validated by djb_scene_create.  m is the hit's scene id, inside the table; the hit goes to its member's binding with
 // its local id.  A slot without material: the outputs stay as the loop preset them, +0, and nothing is read
@@ -1085,12 +1106,34 @@ struct SceneMat {
 };
 
 // ---- eval / evalp per hit
+// WANT with the pdf bit (4; a binding with eval_pdf: LobeMat): fr where WANT & 3, and out_pdf
 template <int WANT, class Mat>
-void set_eval_loop(Mat M, int n_mat, long long k0, long long k1, const int32_t *material, const View &vi, const View &vo, const View &vout)
+void set_eval_loop(Mat M, int n_mat, long long k0, long long k1, const int32_t *material, const View &vi, const View &vo, const View &vout,
+                   float *out_pdf = nullptr)
 {
 	for (long long k = k0; k < k1; ++k) {
 		const unsigned int m = (unsigned int)material[k];
-		store3(vout, k, m < (unsigned int)n_mat ? M.template eval<WANT>(m, load3(vi, k), load3(vo, k)) : mk(0, 0, 0));
+		if constexpr ((WANT & 4) != 0) {
+			v3 fr = mk(0, 0, 0); float pdf = 0.0f;
+			if (m < (unsigned int)n_mat) M.template eval_pdf<WANT>(m, load3(vi, k), load3(vo, k), fr, pdf);
+			if (WANT & 3) store3(vout, k, fr);
+			out_pdf[k] = pdf;
+		} else
+			store3(vout, k, m < (unsigned int)n_mat ? M.template eval<WANT>(m, load3(vi, k), load3(vo, k)) : mk(0, 0, 0));
+	}
+}
+// ---- sample (IS false: i alone) / evalp_is per hit, on a binding with sample<IS>
+template <bool IS, class Mat>
+void set_sample_loop(Mat M, int n_mat, long long k0, long long k1, const int32_t *material, const float *u1a, const float *u2a, const View &vo,
+                     const View &vw_out, const View &vi_out, float *out_pdf)
+{
+	const GlibcTabs gt = glibc_tabs_global();
+	for (long long k = k0; k < k1; ++k) {
+		v3 w = mk(0, 0, 0), i_ = mk(0, 0, 0); float pdf = 0.0f;
+		const unsigned int m = (unsigned int)material[k];
+		if (m < (unsigned int)n_mat) M.template sample<IS>(m, u1a[k], u2a[k], load3(vo, k), gt, i_, w, pdf);
+		store3(vi_out, k, i_);
+		if (IS) { store3(vw_out, k, w); out_pdf[k] = pdf; }
 	}
 }
 template <class Mat>
@@ -1224,6 +1267,67 @@ djb_status model_set_eval(djb_ctx *ctx, int kind, const double *rows, int n_mat,
 {
 	if (kind == KIND_SGD) return set_eval(ctx, ModelMat<KIND_SGD>(rows), n_mat, n, material, i, o, want_cos, out_fr);
 	return set_eval(ctx, ModelMat<KIND_ABC>(rows), n_mat, n, material, i, o, want_cos, out_fr);
+}
+// ---- microfacet sets
+djb_status microfacet_set_member(const djb_ctx *ctx, const djb_brdf *b, int index, int *kind, int *shadow, djb_fresnel_desc *fresnel)
+{
+	djb_status st = set_member_check(ctx, b, index, "microfacet");
+	if (st != DJB_OK) return st;
+	const Brdf &d = B(b)->dev;
+	*kind = d.kind; *shadow = d.shadow;
+	memset(fresnel, 0, sizeof *fresnel);
+	fresnel->kind = d.fr.kind;
+	for (int c = 0; c < 3; ++c) { fresnel->a[c] = d.fr.a[c]; fresnel->b[c] = d.fr.b[c]; }
+	return DJB_OK;
+}
+template <int KIND>
+static void lobe_set_eval(const CpuCtx *ctx, const void *rows, int n_mat, int64_t n, const int32_t *material, const View &vi, const View &vo, const View &vout,
+                          float *out_pdf, int want)
+{
+	const LobeMat<KIND> M(rows);
+	parallel_for(ctx, n, 4096, [&](long long k0, long long k1) {
+		switch (want) {
+		case 1: set_eval_loop<1>(M, n_mat, k0, k1, material, vi, vo, vout); break;
+		case 2: set_eval_loop<2>(M, n_mat, k0, k1, material, vi, vo, vout); break;
+		case 4: set_eval_loop<4>(M, n_mat, k0, k1, material, vi, vo, vout, out_pdf); break;
+		case 5: set_eval_loop<5>(M, n_mat, k0, k1, material, vi, vo, vout, out_pdf); break;
+		case 6: set_eval_loop<6>(M, n_mat, k0, k1, material, vi, vo, vout, out_pdf); break;
+		}
+	});
+}
+djb_status microfacet_set_eval(djb_ctx *ctx, int kind, const void *rows, int n_mat, int64_t n, const int32_t *material, const djb_vec3_view *i,
+                               const djb_vec3_view *o, int want, const djb_vec3_view *out_fr, float *out_pdf)
+{
+	djb_status st = set_batch_head(n, material);
+	if (st != DJB_OK) return st;
+	if (!valid(i) || !valid(o)) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null vec3 view");
+	if ((want & 3) && !valid(out_fr)) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null output vec3 view");
+	if ((want & 4) && !out_pdf) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null output array");
+	const View vi = view_of(i), vo = view_of(o), vout = (want & 3) ? view_of(out_fr) : NO_VIEW;
+	if (kind == KIND_GGX) lobe_set_eval<KIND_GGX>(C(ctx), rows, n_mat, n, material, vi, vo, vout, out_pdf, want);
+	else lobe_set_eval<KIND_BECKMANN>(C(ctx), rows, n_mat, n, material, vi, vo, vout, out_pdf, want);
+	return DJB_OK;
+}
+template <int KIND>
+static void lobe_set_sample(const CpuCtx *ctx, const void *rows, int n_mat, int64_t n, const int32_t *material, const float *u1, const float *u2,
+                            const View &vo, bool is, const View &vw, const View &vi, float *out_pdf)
+{
+	const LobeMat<KIND> M(rows);
+	parallel_for(ctx, n, 2048, [&](long long k0, long long k1) {
+		if (is) set_sample_loop<true>(M, n_mat, k0, k1, material, u1, u2, vo, vw, vi, out_pdf);
+		else set_sample_loop<false>(M, n_mat, k0, k1, material, u1, u2, vo, vw, vi, out_pdf);
+	});
+}
+djb_status microfacet_set_sample(djb_ctx *ctx, int kind, const void *rows, int n_mat, int64_t n, const int32_t *material, const float *u1, const float *u2,
+                                 const djb_vec3_view *o, bool is, const djb_vec3_view *out_w, const djb_vec3_view *out_i, float *out_pdf)
+{
+	djb_status st = set_batch_head(n, material);
+	if (st != DJB_OK) return st;
+	if (!u1 || !u2 || !valid(o) || !valid(out_i) || (is && (!valid(out_w) || !out_pdf))) return djbk::set_error(DJB_ERR_INVALID_ARGUMENT, "djb_error: null argument");
+	const View vo = view_of(o), vi = view_of(out_i), vw = is ? view_of(out_w) : NO_VIEW;
+	if (kind == KIND_GGX) lobe_set_sample<KIND_GGX>(C(ctx), rows, n_mat, n, material, u1, u2, vo, is, vw, vi, out_pdf);
+	else lobe_set_sample<KIND_BECKMANN>(C(ctx), rows, n_mat, n, material, u1, u2, vo, is, vw, vi, out_pdf);
+	return DJB_OK;
 }
 // the fitted tabular proxies of a model set (djb_model_set_fit_proxy): the block ModelMat reads, each material fitted as create_tabular fits
 // the single object

@@ -114,6 +114,14 @@ djb_status utia_set_eval(djb_ctx *, const void *records, int n_mat, int64_t n, c
 djb_status model_set_member(const djb_ctx *ctx, const djb_brdf *b, int index, int *kind, const double **row);
 djb_status model_set_eval(djb_ctx *, int kind, const double *rows, int n_mat, int64_t n, const int32_t *material, const djb_vec3_view *i,
                           const djb_vec3_view *o, int want_cos, const djb_vec3_view *out_fr);
+// Microfacet sets on the host (include/djb_hip.h: djb_microfacet_set).  rows = djbdev::MfRow[n_mat] in host memory (djb_microfacet_row.hpp); a
+// hit whose id is outside [0, n_mat) gets +0 in every output.  microfacet_set_member: kind, shadowing flag and Fresnel term (no spline
+// points) of a ggx / beckmann object of `ctx`, or the reason it is refused.  eval: want bits 1 eval, 2 evalp, 4 pdf; sample: is = evalp_is()
+djb_status microfacet_set_member(const djb_ctx *ctx, const djb_brdf *b, int index, int *kind, int *shadow, djb_fresnel_desc *fresnel);
+djb_status microfacet_set_eval(djb_ctx *, int kind, const void *rows, int n_mat, int64_t n, const int32_t *material, const djb_vec3_view *i,
+                               const djb_vec3_view *o, int want, const djb_vec3_view *out_fr, float *out_pdf);
+djb_status microfacet_set_sample(djb_ctx *, int kind, const void *rows, int n_mat, int64_t n, const int32_t *material, const float *u1, const float *u2,
+                                 const djb_vec3_view *o, bool is, const djb_vec3_view *out_w, const djb_vec3_view *out_i, float *out_pdf);
 // Scenes on the host (include/djb_hip.h: djb_scene).  slots: n_slots packed words (djb_internal.hpp) in host memory; then the blocks of the
 // members the scene has (NULL / 0 for the others, no slot names them) -- the MERL and UTIA tables with their resolved Params[M], the model
 // rows with their fitted proxy blocks (model_set_fit_proxy below).  eval reads the tables and rows alone

@@ -756,6 +756,7 @@ try {
 		return DJB_OK;
 	}
 	if (option == DJB_OPT_MODEL_SET_ROWS_GLOBAL) { ctx->model_set_rows_global = value != 0; return DJB_OK; }
+	if (option == DJB_OPT_MICROFACET_SET_ROWS_GLOBAL) { ctx->microfacet_set_rows_global = value != 0; return DJB_OK; }
 	if (option == DJB_OPT_TEST_WORKLIST_CAP) { ctx->test_worklist_cap = value; return DJB_OK; }
 	if (option == DJB_OPT_TEST_SCENE_CHUNK) {
 		if (value < 0 || value > (1 << 26)) return fail(DJB_ERR_INVALID_ARGUMENT, "djb_error: a scene chunk holds 1 .. %d hits, 0 = default (got %d)", 1 << 26, value);

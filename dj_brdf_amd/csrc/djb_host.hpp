@@ -59,6 +59,7 @@ struct djb_ctx {
 	unsigned long long wl_note_key = 0, ct_key = 0; double ct_key_share = 0.0;   // contract mode: (lobe, params) of that call and its share
 	unsigned int ct_hopeless_calls = 0;        // calls answered by the exact kernel because of ct_key_share: every 16th re-probes
 	int model_set_rows_global = 0;   // DJB_OPT_MODEL_SET_ROWS_GLOBAL: model-set kernels read their rows from global memory whatever M is (tests, A/B timing)
+	int microfacet_set_rows_global = 0;   // DJB_OPT_MICROFACET_SET_ROWS_GLOBAL: the same for the microfacet-set kernels
 	long long test_worklist_cap = -1;   // DJB_OPT_TEST_WORKLIST_CAP (tests): >= 0 overrides the tier-2 worklist capacity
 	long long test_scene_chunk = 0;     // DJB_OPT_TEST_SCENE_CHUNK (tests): > 0 overrides the hits per chunk of a scene call
 	int contract_1e5 = 0;      // DJB_OPT_CONTRACT_1E5: dense GGX eval batches run the two-tier value-contract kernels
@@ -162,6 +163,17 @@ struct djb_model_set : djb_set_base {
 	int proxy_res = 0, proxy_shadow = 0;     // proxy_res == 0: no proxy yet
 	std::vector<float> proxy_host;   // the block in host memory: what a CPU context computes on, and what djb_model_set_get_proxy reads
 	float *proxy_dev = nullptr;      // GPU context: the block in HBM
+};
+
+// a microfacet set (djb_microfacet_set.hip): M analytic materials of one NDF kind, one MfRow each (resolved parameters, Fresnel term, shadowing
+// flag), in one block where the set's context computes.  fr_kind: the Fresnel kind every row has, or -1 when they differ (the launch's
+// choice of instantiation).  host_rows (GPU context): the block in host memory, which djb_microfacet_set_set_params edits and uploads whole
+// in stream order on the context's stream.
+struct djb_microfacet_set : djb_set_base {
+	int kind = 0;                    // DJB_KIND_GGX or DJB_KIND_BECKMANN
+	int fr_kind = -1;
+	djbdev::MfRow *rows = nullptr;
+	std::vector<djbdev::MfRow> host_rows;
 };
 
 // a scene (djb_scene.hip): the slot table that maps a scene material id to (kind, local id) in up to four member sets, which the scene

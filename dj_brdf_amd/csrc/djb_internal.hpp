@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "djb_device.hpp"
+#include "djb_microfacet_row.hpp"
 
 namespace djbk {
 
@@ -160,6 +161,19 @@ hipError_t launch_model_set_evalp_is_proxy(hipStream_t s, int kind, const double
 hipError_t launch_model_set_evalp_pdf(hipStream_t s, int kind, const double *rows, int n_mat, bool rows_global, const ModelSetProxy &proxy,
                                       const Params &proxy_p, long long n, const int32_t *material, const View &i, const View &o,
                                       const View &out_fr, float *out_pdf);
+// Microfacet sets (djb_kernels_microfacet_set.hip): rows = MfRow[n_mat] (djb_microfacet_row.hpp) of ONE NDF kind, ggx or beckmann, material
+// = n ids (outside [0, n_mat): an inactive hit, +0 in every output).  fr_kind: the Fresnel kind every row has, or -1 when they differ.
+// eval: want bits as launch_eval_pp; sample: out_w == NULL gives sample(), else evalp_is().  One launch each.  rows_global: read the rows
+// from global memory whatever n_mat is (DJB_OPT_MICROFACET_SET_ROWS_GLOBAL); by default up to microfacet_set_rows_lds() rows go to LDS,
+// and the grid then has at most microfacet_set_grid_cap() workgroups
+using djbdev::MfRow;
+int microfacet_set_rows_lds();
+long long microfacet_set_grid_cap();
+hipError_t launch_microfacet_set_eval(hipStream_t s, int kind, const MfRow *rows, int n_mat, int fr_kind, bool rows_global, long long n,
+                                      const int32_t *material, const View &i, const View &o, const View &out, float *out_pdf, int want);
+hipError_t launch_microfacet_set_sample(hipStream_t s, int kind, const MfRow *rows, int n_mat, int fr_kind, bool rows_global, long long n,
+                                        const int32_t *material, const float *u1, const float *u2, const View &o, const View &out_i, const View *out_w,
+                                        float *out_pdf);
 // Scenes (djb_kernels_scene.hip): hits on up to four member sets at once.  slots = n_slots words, kind (0 merl, 1 utia, 2 sgd, 3 abc; any
 // other value: no material) << 16 | local id; a hit whose id is outside [0, n_slots) or whose slot has no material is inactive (+0).  One
 // call partitions a chunk of m <= SCENE_CHUNK_MAX hits by kind on the device (three launches) and runs one kernel per member set that is

@@ -1,7 +1,7 @@
-// djb_set_host.hpp -- what the C ABIs of the three material sets and of scenes share (djb_merl_set.hip, djb_utia_set.hip, djb_model_set.hip,
-// djb_scene.hip; included by those alone): the checks of a handle, a member and a count, the construction and release of the resident block,
+// djb_set_host.hpp -- what the C ABIs of the four material sets and of scenes share (djb_merl_set.hip, djb_utia_set.hip, djb_model_set.hip,
+// djb_microfacet_set.hip, djb_scene.hip; included by those alone): the checks of a handle, a member and a count, the construction and release of the resident block,
 // the proxy parameter block of the MERL and UTIA sets and the check of a proxy object, and the entry of a batch of either shape (eval or
-// light sample; sampling).  `what` is the set's noun in the messages: "merl" / "utia" / "model" / "scene".  Everything works on
+// light sample; sampling).  `what` is the set's noun in the messages: "merl" / "utia" / "model" / "microfacet" / "scene".  Everything works on
 // djb_set_base (djb_host.hpp).
 #pragma once
 #include "djb_host.hpp"

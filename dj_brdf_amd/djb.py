@@ -236,16 +236,23 @@ def _material_ids(material, like: _Vec):
     return material, ptr
 
 
-def _sampling_call(fn, head, material, u1, u2, o, tail=()):
+def _sampling_call(fn, head, material, u1, u2, o, tail=(), direction_only=False):
     """The marshalling of every sampling step: ``fn(*head, n, [ids,] u1, u2, o, *tail, out_weight, out_i, out_pdf, mem)`` -> (weight, i,
-    pdf).  ``head``: the handles that precede n; ``material``: the per-hit ids of a set or scene call, else None; ``tail``: the parameter
-    sets of a single-material call.  The staged arrays live until the call has returned."""
+    pdf); ``direction_only``: out_weight and out_pdf are passed as NULL (an entry whose ``sample()`` form that is) -> i.  ``head``: the
+    handles that precede n; ``material``: the per-hit ids of a set or scene call, else None; ``tail``: the parameter sets of a
+    single-material call.  The staged arrays live until the call has returned."""
     vo = _Vec(o)
     keep, mp = (None, None) if material is None else _material_ids(material, vo)
     ids = () if material is None else (C.c_void_p(mp),)
     k1, p1 = _scalar_in(u1, vo)
     k2, p2 = _scalar_in(u2, vo)
-    w, i = vo.like(), vo.like()
+    i = vo.like()
+    if direction_only:
+        _lib.check(fn(*head, C.c_int64(vo.n), *ids, C.c_void_p(p1), C.c_void_p(p2), C.byref(vo.view),
+                      *tail, None, C.byref(i.view), None, C.c_int(vo.mem)))
+        del keep, k1, k2
+        return i.keep
+    w = vo.like()
     pdf, pdf_ptr = vo.scalars()
     _lib.check(fn(*head, C.c_int64(vo.n), *ids, C.c_void_p(p1), C.c_void_p(p2), C.byref(vo.view),
                   *tail, C.byref(w.view), C.byref(i.view), C.c_void_p(pdf_ptr), C.c_int(vo.mem)))
@@ -253,20 +260,22 @@ def _sampling_call(fn, head, material, u1, u2, o, tail=()):
     return w.keep, i.keep, pdf
 
 
-def _light_call(fn, head, material, i, o, tail=()):
-    """The marshalling of every light sample: ``fn(*head, n, [ids,] i, o, *tail, out_fr, out_pdf, mem)`` -> (fr, pdf); the arguments as
-    in ``_sampling_call``."""
+def _light_call(fn, head, material, i, o, tail=(), want_fr=True, want_pdf=True):
+    """The marshalling of every light sample, and of every eval with an optional pdf: ``fn(*head, n, [ids,] i, o, *tail, out_fr, out_pdf,
+    mem)`` -> (fr, pdf); the arguments as in ``_sampling_call``.  An output that is not wanted is passed as NULL and not returned."""
     vi, vo = _Vec(i), _Vec(o)
     if vi.n != vo.n or vi.mem != vo.mem:
         raise exc(1, "djb_error: i and o must have the same length and memory space")
     keep, mp = (None, None) if material is None else _material_ids(material, vi)
     ids = () if material is None else (C.c_void_p(mp),)
-    fr = vi.like()
-    pdf, pdf_ptr = vi.scalars()
+    fr = vi.like() if want_fr else None
+    pdf, pdf_ptr = vi.scalars() if want_pdf else (None, None)
     _lib.check(fn(*head, C.c_int64(vi.n), *ids, C.byref(vi.view), C.byref(vo.view), *tail,
-                  C.byref(fr.view), C.c_void_p(pdf_ptr), C.c_int(vi.mem)))
+                  C.byref(fr.view) if want_fr else None, C.c_void_p(pdf_ptr), C.c_int(vi.mem)))
     del keep
-    return fr.keep, pdf
+    if want_fr and want_pdf:
+        return fr.keep, pdf
+    return fr.keep if want_fr else pdf
 
 
 # --------------------------------------------------------------------------- fresnel (dj_brdf.h:149-207)
@@ -1430,6 +1439,94 @@ class model_set(_material_set):
         return _light_call(_lib.load().djb_model_set_evalp_pdf_proxy_batch, (self.ctx._h, self._h), material, i, o)
 
 
+class microfacet_set(_material_set):
+    """M analytic materials of ONE NDF kind, ggx or beckmann -- each its own ``microfacet.params``, Fresnel term and shadowing flag --
+    resident in ONE block on their context's device: hits that land on many hand-authored materials are evaluated, importance-sampled and
+    light-sampled in one call each, every hit naming its material by id (djb_microfacet_set, include/djb_hip.h).  An extension: the
+    reference's objects are one material each.
+
+    ``microfacet_set(members, params)``: ``djb.ggx`` or ``djb.beckmann`` objects (all of one kind) and one ``microfacet.params`` per
+    member (None: ``params.standard()`` for all); the set copies Fresnel term and shadowing flag, it does not keep the objects.
+    ``from_materials`` takes plain descriptions.  ``material``: int32 ids, one per hit; an id outside [0, M) marks an inactive hit (a dead
+    path), whose outputs are all +0.  An active hit gets the bits of the single-material call on its material.  Arrays: numpy (host) or
+    torch CUDA (device), in the layouts the other operators take; the ids travel in the memory space of the directions."""
+
+    _C = "djb_microfacet_set"
+    _KINDS = {"beckmann": 0, "ggx": 1}       # DJB_KIND_BECKMANN, DJB_KIND_GGX
+
+    _params_array = staticmethod(_proxy_params_set._params_array)          # one microfacet.params per material -> djb_params[n], or None
+
+    def __init__(self, members, params=None, ctx: Optional[Context] = None):
+        members = list(members)
+        self.ctx = ctx or (members[0].ctx if members else default_context())
+        self._h = C.c_void_p()
+        ptrs = (C.c_void_p * max(len(members), 1))(*[getattr(b._h, "value", None) for b in members])
+        _lib.check(_lib.load().djb_microfacet_set_create_from_brdfs(self.ctx._h, C.c_int(len(members)), ptrs,
+                                                                    self._params_array(params, len(members)), C.byref(self._h)))
+
+    @classmethod
+    def from_materials(cls, kind: str, materials, ctx: Optional[Context] = None):
+        """``kind``: "ggx" or "beckmann"; ``materials``: (fresnel, shadow, params) per material -- a ``djb.fresnel`` term (None: ideal), a
+        bool and a ``microfacet.params`` (None: standard)"""
+        if kind not in cls._KINDS:
+            raise exc(1, f"djb_error: a microfacet set is of kind 'ggx' or 'beckmann' (got {kind!r})")
+        materials = list(materials)
+        arr = (_lib.MicrofacetMaterial * max(len(materials), 1))()
+        keep = []
+        for m, (fr, shadow, p) in enumerate(materials):
+            d, k = (fr or fresnel.ideal())._desc()
+            keep.append(k)
+            arr[m].fresnel, arr[m].shadow = d, int(bool(shadow))
+            if p is not None:
+                arr[m].params = p._p
+        self = cls.__new__(cls)
+        self.ctx = ctx or default_context()
+        self._h = C.c_void_p()
+        _lib.check(_lib.load().djb_microfacet_set_create(self.ctx._h, C.c_int(cls._KINDS[kind]), C.c_int(len(materials)), arr, C.byref(self._h)))
+        del keep
+        return self
+
+    def _info(self):
+        k, n = C.c_int(), C.c_int()
+        _lib.check(_lib.load().djb_microfacet_set_info(self._h, C.byref(k), C.byref(n)))
+        return k.value, n.value
+
+    @property
+    def kind(self) -> str:
+        return {v: k for k, v in self._KINDS.items()}[self._info()[0]]
+
+    @property
+    def n_materials(self) -> int:
+        return self._info()[1]
+
+    def set_params(self, params):
+        """one ``microfacet.params`` per material; replaces the resident parameter sets in stream order (Fresnel terms and flags stay)"""
+        _lib.check(_lib.load().djb_microfacet_set_set_params(self._h, self._params_array(params, self.n_materials)))
+
+    def _want(self, material, i, o, want):
+        return _light_call(_lib.load().djb_microfacet_set_eval_batch, (self.ctx._h, self._h), material, i, o, (C.c_int(want),),
+                           want_fr=bool(want & 3), want_pdf=bool(want & 4))
+
+    def _eval(self, material, i, o, want_cos):
+        return self._want(material, i, o, 2 if want_cos else 1)
+
+    def pdf(self, material, i, o):
+        """pdf of sampling i_k given o_k from material[k]"""
+        return self._want(material, i, o, 4)
+
+    def eval_pdf(self, material, i, o, cos=False):
+        """(eval or evalp, pdf) in one pass"""
+        return self._want(material, i, o, 6 if cos else 5)
+
+    def sample(self, material, u1, u2, o):
+        """i_k importance-sampled from material[k] at (u1_k, u2_k) given o_k"""
+        return _sampling_call(_lib.load().djb_microfacet_set_sample_batch, (self.ctx._h, self._h), material, u1, u2, o, direction_only=True)
+
+    def evalp_is(self, material, u1, u2, o):
+        """(f_r cos / pdf, i, pdf) per hit as ``brdf.evalp_is`` on material[k]"""
+        return _sampling_call(_lib.load().djb_microfacet_set_sample_batch, (self.ctx._h, self._h), material, u1, u2, o)
+
+
 class scene(_material_set):
     """A slot table over up to four member sets -- a ``merl_set``, a ``utia_set``, an sgd and an abc ``model_set`` of one context --: hits
     that land on measured, UTIA and data-driven materials at once are evaluated in one call, each hit naming its material by SCENE id
@@ -1877,6 +1974,11 @@ def set_model_set_rows_global(ctx: Context, on: bool):
     """model-set kernels read their parameter rows from global memory whatever M is (DJB_OPT_MODEL_SET_ROWS_GLOBAL; tests and A/B
     timing) instead of from the workgroup's copy in LDS; same bits."""
     _lib.check(_lib.load().djb_ctx_set_option(ctx._h, C.c_int(9), C.c_int(int(on))))
+
+
+def set_microfacet_set_rows_global(ctx: Context, on: bool):
+    """DJB_OPT_MICROFACET_SET_ROWS_GLOBAL (tests, A/B timing): the microfacet-set kernels read their rows from global memory whatever M is"""
+    _lib.check(_lib.load().djb_ctx_set_option(ctx._h, 11, int(bool(on))))
 
 
 def set_contract_1e5(ctx: Context, on: bool):

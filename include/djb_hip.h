@@ -88,7 +88,11 @@ extern "C" {
  *        set, an sgd and an abc model set at once, by per-hit scene material id, one call), DJB_OPT_TEST_SCENE_CHUNK.
  *        Additive under 235, no existing entry changed: proxy parameters on a UTIA set -- djb_utia_set_set_proxy_params,
  *        djb_utia_set_proxy_info -- and the two per-hit steps on a scene -- djb_scene_evalp_is_proxy_batch,
- *        djb_scene_evalp_pdf_proxy_batch (the sampling step and the light sample across all four member kinds, one call each). */
+ *        djb_scene_evalp_pdf_proxy_batch (the sampling step and the light sample across all four member kinds, one call each).
+ *        Additive under 235, no existing entry changed: microfacet sets -- djb_microfacet_set, djb_microfacet_material, DJB_MICROFACET_SET_MAX,
+ *        djb_microfacet_set_create, djb_microfacet_set_create_from_brdfs, djb_microfacet_set_set_params, djb_microfacet_set_info,
+ *        djb_microfacet_set_destroy, djb_microfacet_set_eval_batch, djb_microfacet_set_sample_batch (eval / evalp / pdf and sample / evalp_is
+ *        of hits on M resident ggx or beckmann materials by per-hit material id, one call), DJB_OPT_MICROFACET_SET_ROWS_GLOBAL. */
 #define DJB_HIP_VERSION 235
 #define DJB_HIP_VERSION_MAJOR(v) ((v) / 100)
 
@@ -129,6 +133,7 @@ typedef struct djb_leanmap djb_leanmap;   /* an immutable LEAN map (mip pyramid 
 typedef struct djb_merl_set djb_merl_set; /* M MERL tables in one resident block + one proxy parameter set per material */
 typedef struct djb_utia_set djb_utia_set; /* M UTIA record tables in one resident block */
 typedef struct djb_model_set djb_model_set; /* M sgd or abc parameter rows in one resident block */
+typedef struct djb_microfacet_set djb_microfacet_set; /* M ggx or beckmann materials (params, Fresnel term, shadowing) in one resident block */
 typedef struct djb_scene djb_scene;         /* a slot table over up to four member sets: scene material id -> (kind, local id) */
 
 typedef struct { float *x, *y, *z; int64_t stride; } djb_vec3_view;
@@ -261,7 +266,10 @@ enum { DJB_OPT_MERL_EXACT_ONLY = 1,
        DJB_OPT_MODEL_SET_ROWS_GLOBAL = 9,
 /* DJB_OPT_TEST_SCENE_CHUNK = <hits> (tests only; 0 = the default of 2^24, at most 2^26): the hits per chunk of djb_scene_eval_batch, to
  * reach chunk boundaries at small n.  Results never depend on it. */
-       DJB_OPT_TEST_SCENE_CHUNK = 10 };
+       DJB_OPT_TEST_SCENE_CHUNK = 10,
+/* DJB_OPT_MICROFACET_SET_ROWS_GLOBAL = 1 (tests and A/B timing; off by default): the microfacet-set kernels read their rows from global
+ * memory whatever M is, instead of from the copy a workgroup keeps in LDS when the set is small enough.  Same bits. */
+       DJB_OPT_MICROFACET_SET_ROWS_GLOBAL = 11 };
 djb_status  djb_ctx_set_option(djb_ctx *ctx, int option, int value);
 /* Observer of the MERL file pipeline (djb_fit_merl_files, both context kinds): `fn(path, user)` is called from the reader thread
  * after a file has passed its size check and has been mapped, before its entries are gathered; NULL removes it.  Diagnostics /
@@ -709,6 +717,54 @@ djb_status djb_model_set_evalp_is_proxy_batch(djb_ctx *, const djb_model_set *, 
 djb_status djb_model_set_evalp_pdf_proxy_batch(djb_ctx *, const djb_model_set *, int64_t n, const int32_t *material,
                                                const djb_vec3_view *i, const djb_vec3_view *o,
                                                const djb_vec3_view *out_fr, float *out_pdf, int mem);
+
+/* ---- microfacet sets: the material sets of the analytic lobes.  A microfacet set is M resident materials of ONE NDF kind, DJB_KIND_GGX or
+ * DJB_KIND_BECKMANN; each material is what a single-material call takes from its object and its djb_params -- the resolved parameter set,
+ * the Fresnel term and the shadowing flag.  The reference's dj_brdf plugin issues evalp(i, o, &params), pdf(i, o, &params) and
+ * evalp_is(u1, u2, o, &i, &pdf, &params) per hit (mitsuba/dj_brdf.cpp:353-362, 382-391, 404-413), dj_beckmannconductor without a LEAN map
+ * likewise: a wavefront renderer whose hits land on M such materials gets them in one call each, from the ids.
+ *
+ * Creation.  djb_microfacet_set_create takes n_materials plain descriptions in host memory.  djb_microfacet_set_create_from_brdfs reads
+ * Fresnel term and shadowing flag of n_materials ggx or beckmann objects of the call's context, all of one kind (a mixed list is
+ * DJB_ERR_INVALID_ARGUMENT and the message names the first odd member), with params[m] for member m or params::standard() for all when
+ * params is NULL; the set copies, it does not borrow: the members may be destroyed or changed as soon as the call returns, and the same
+ * handle may appear more than once.  Fresnel kinds IDEAL, UNPOLARIZED, SCHLICK and SGD; SPLINE is DJB_ERR_NOT_IMPLEMENTED (its point list
+ * has no fixed size, and it is what fitted lobes carry, not authored ones); HOST is refused as everywhere.  params: any kind
+ * djb_params_resolve accepts; DJB_PARAMS_RESOLVED_FOLLOWS is refused.  Each is resolved once, on the host, exactly as the single-material
+ * call of the set's context resolves it.  1 <= M <= DJB_MICROFACET_SET_MAX.  The set belongs to its context as a djb_brdf does and may be
+ * destroyed after it.  djb_microfacet_set_set_params replaces the n_materials parameter sets in stream order on the context's stream (the
+ * context must still exist), as djb_merl_set_set_proxy_params; Fresnel terms and flags stay.
+ *
+ * material: n int32 values in the memory space `mem` names.  A hit with 0 <= material[k] < M gets, bit for bit, what the single-material
+ * call returns for unit k's inputs on a ggx / beckmann object with material m's Fresnel term and shadowing flag, and material m's params:
+ *   djb_microfacet_set_eval_batch     want as for djb_eval_pp_batch: 1 eval or 2 evalp, optionally | 4 pdf; 4 alone with out_fr NULL.  An
+ *                                     array that `want` asks for and that is missing is DJB_ERR_INVALID_ARGUMENT; one it does not ask for
+ *                                     is not touched
+ *   djb_microfacet_set_sample_batch   out_weight == NULL and out_pdf == NULL: sample(), out_i alone; else evalp_is() with
+ *                                     djb_sample_pp_batch's conventions (weight, i, pdf; all three arrays)
+ * A hit whose id is outside [0, M) is INACTIVE: every output of that hit is +0.0f and no row is read for it.
+ *
+ * Options.  DJB_OPT_CONTRACT_1E5 changes nothing: a set has no contract-mode kernels, every active hit has the reference's bits.
+ * DJB_OPT_MICROFACET_SET_ROWS_GLOBAL (tests, A/B timing) makes the kernels read rows from global memory whatever M is; by default a set of
+ * up to 200 materials is copied into LDS by every workgroup.  CPU contexts serve every call with the host instantiation of the same
+ * per-unit code.  On a GPU context a device-memory batch is ONE kernel launch, with no allocation and no host read-back: it can be
+ * captured into a hipGraph.  Index-aligned in-place calls (an output names an input's arrays) are supported: every lane reads its hit
+ * before it writes it.  A host-memory batch of any size is staged through HBM (a set has no host twin). */
+#define DJB_MICROFACET_SET_MAX 65536       /* a local id fits the 16 bits a scene slot has for it */
+typedef struct { djb_fresnel_desc fresnel; int shadow; djb_params params; } djb_microfacet_material;
+djb_status djb_microfacet_set_create(djb_ctx *, int kind /* DJB_KIND_GGX | DJB_KIND_BECKMANN */, int n_materials,
+                                     const djb_microfacet_material *materials /* n_materials, host memory */, djb_microfacet_set **out);
+djb_status djb_microfacet_set_create_from_brdfs(djb_ctx *, int n_materials, const djb_brdf *const *members,
+                                                const djb_params *params /* n_materials, or NULL = standard */, djb_microfacet_set **out);
+djb_status djb_microfacet_set_set_params(djb_microfacet_set *, const djb_params *params /* n_materials */);
+djb_status djb_microfacet_set_info(const djb_microfacet_set *, int *kind, int *n_materials);
+djb_status djb_microfacet_set_destroy(djb_microfacet_set *);
+djb_status djb_microfacet_set_eval_batch(djb_ctx *, const djb_microfacet_set *, int64_t n, const int32_t *material,
+                                         const djb_vec3_view *i, const djb_vec3_view *o, int want,
+                                         const djb_vec3_view *out_fr, float *out_pdf, int mem);
+djb_status djb_microfacet_set_sample_batch(djb_ctx *, const djb_microfacet_set *, int64_t n, const int32_t *material,
+                                           const float *u1, const float *u2, const djb_vec3_view *o,
+                                           const djb_vec3_view *out_weight, const djb_vec3_view *out_i, float *out_pdf, int mem);
 
 /* ---- scenes: one call for a hit batch that lands on measured, UTIA and data-driven materials at once.  A material set holds materials
  * of ONE kind; a wavefront renderer's bounce does not.  A scene is a resident slot table that maps a SCENE material id to (kind, local id)

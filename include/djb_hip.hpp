@@ -1448,6 +1448,61 @@ private:
 	djb_model_set *m_h;
 };
 
+/* M ggx or beckmann materials -- each its own microfacet::params, Fresnel term and shadowing flag, all of ONE NDF kind -- resident in one
+ * block on their context's device (include/djb_hip.h, djb_microfacet_set): each hit names its material by id and the whole batch is one
+ * call.  An extension with no counterpart in the reference, whose dj_brdf plugin issues evalp / pdf / evalp_is per hit.  An id outside
+ * [0, size()) marks an inactive hit: every output of it is +0.  An active hit gets the bits of microfacet::eval / evalp / pdf / sample /
+ * evalp_is on a ggx (beckmann) object with its material's Fresnel term and shadowing flag, called with its material's params. */
+class microfacet_set {
+public:
+	/* Fresnel term and shadowing flag of n ggx (beckmann) objects are copied: the objects may be destroyed afterwards.  params: n sets, or
+	 * NULL = params::standard() for all.  Spline and user-defined Fresnel terms are refused */
+	microfacet_set(size_t n, const microfacet *const *members, const microfacet::params *params = NULL, hip::context *c = NULL) : m_ctx(c), m_h(NULL)
+	{
+		std::vector<const djb_brdf *> h(n);
+		for (size_t k = 0; k < n; ++k) h[k] = members[k] ? members[k]->handle() : NULL;
+		std::vector<djb_params> p = hip::plain_params(n, params);
+		hip::check(djb_microfacet_set_create_from_brdfs(ctx(), (int)n, h.data(), params ? p.data() : NULL, &m_h));
+	}
+	/* n plain descriptions; kind = DJB_KIND_GGX or DJB_KIND_BECKMANN */
+	microfacet_set(int kind, size_t n, const djb_microfacet_material *materials, hip::context *c = NULL) : m_ctx(c), m_h(NULL)
+	{ hip::check(djb_microfacet_set_create(ctx(), kind, (int)n, materials, &m_h)); }
+	~microfacet_set() { djb_microfacet_set_destroy(m_h); }
+	microfacet_set(microfacet_set &&o) noexcept : m_ctx(o.m_ctx), m_h(o.m_h) { o.m_h = NULL; }
+	microfacet_set &operator=(microfacet_set &&o) noexcept { if (this != &o) { djb_microfacet_set_destroy(m_h); m_ctx = o.m_ctx; m_h = o.m_h; o.m_h = NULL; } return *this; }
+	microfacet_set(const microfacet_set &) = delete;
+	microfacet_set &operator=(const microfacet_set &) = delete;
+	const djb_microfacet_set *get() const { return m_h; }
+	int size() const { int v; hip::check(djb_microfacet_set_info(m_h, NULL, &v)); return v; }
+	int kind() const { int v; hip::check(djb_microfacet_set_info(m_h, &v, NULL)); return v; }
+	/* one set per material; replaces the resident ones in stream order (Fresnel terms and flags stay) */
+	void set_params(const microfacet::params *params)
+	{ std::vector<djb_params> p = hip::plain_params((size_t)size(), params); hip::check(djb_microfacet_set_set_params(m_h, p.data())); }
+	// ---- host arrays
+	void eval(size_t n, const int32_t *material, const vec3 *i, const vec3 *o, vec3 *out) const { const djb_vec3_view v = hip::view(out); eval_views((int64_t)n, material, hip::view(i), hip::view(o), 1, &v, NULL, DJB_MEM_HOST); }
+	void evalp(size_t n, const int32_t *material, const vec3 *i, const vec3 *o, vec3 *out) const { const djb_vec3_view v = hip::view(out); eval_views((int64_t)n, material, hip::view(i), hip::view(o), 2, &v, NULL, DJB_MEM_HOST); }
+	void pdf(size_t n, const int32_t *material, const vec3 *i, const vec3 *o, float_t *out_pdf) const { eval_views((int64_t)n, material, hip::view(i), hip::view(o), 4, NULL, out_pdf, DJB_MEM_HOST); }
+	/* eval (cos = false) or evalp, and the pdf, in one pass */
+	void eval_pdf(size_t n, const int32_t *material, const vec3 *i, const vec3 *o, vec3 *out, float_t *out_pdf, bool cos = false) const
+	{ const djb_vec3_view v = hip::view(out); eval_views((int64_t)n, material, hip::view(i), hip::view(o), (cos ? 2 : 1) | 4, &v, out_pdf, DJB_MEM_HOST); }
+	void sample(size_t n, const int32_t *material, const float_t *u1, const float_t *u2, const vec3 *o, vec3 *out_i) const
+	{ sample_views((int64_t)n, material, u1, u2, hip::view(o), NULL, hip::view(out_i), NULL, DJB_MEM_HOST); }
+	void evalp_is(size_t n, const int32_t *material, const float_t *u1, const float_t *u2, const vec3 *o, vec3 *out_weight, vec3 *out_i, float_t *out_pdf) const
+	{ const djb_vec3_view w = hip::view(out_weight); sample_views((int64_t)n, material, u1, u2, hip::view(o), &w, hip::view(out_i), out_pdf, DJB_MEM_HOST); }
+	// ---- views (SoA or strided), in host memory or in HBM (mem = DJB_MEM_DEVICE: asynchronous on the context's stream, one launch).
+	// want: 1 eval or 2 evalp, optionally | 4 pdf, or 4 alone (out NULL); out_weight == NULL and out_pdf == NULL: sample(), else evalp_is()
+	void eval_views(int64_t n, const int32_t *material, const djb_vec3_view &i, const djb_vec3_view &o, int want, const djb_vec3_view *out,
+	                float_t *out_pdf, int mem) const
+	{ hip::check(djb_microfacet_set_eval_batch(ctx(), m_h, n, material, &i, &o, want, out, out_pdf, mem)); }
+	void sample_views(int64_t n, const int32_t *material, const float_t *u1, const float_t *u2, const djb_vec3_view &o, const djb_vec3_view *out_weight,
+	                  const djb_vec3_view &out_i, float_t *out_pdf, int mem) const
+	{ hip::check(djb_microfacet_set_sample_batch(ctx(), m_h, n, material, u1, u2, &o, out_weight, &out_i, out_pdf, mem)); }
+private:
+	djb_ctx *ctx() const { return (m_ctx ? *m_ctx : hip::context::standard()).get(); }
+	hip::context *m_ctx;
+	djb_microfacet_set *m_h;
+};
+
 /* A slot table over up to four member sets of one context -- a merl_set, a utia_set, an sgd and an abc model_set (include/djb_hip.h,
  * djb_scene): the hits of one bounce land on measured, UTIA and data-driven materials at once; each hit names its material by SCENE id
  * and the whole batch is one call.  An extension with no counterpart in the reference.  slots[k] = { kind, local }: kind DJB_KIND_MERL,

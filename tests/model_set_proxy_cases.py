@@ -27,6 +27,7 @@ import model_set_cases
 import param_space_cases
 import proxy_is_cases
 from dj_brdf_amd import _lib, djb
+from hit_calls import CANARY
 
 select, active, same_bits, inactive_values = merl_set_cases.select, merl_set_cases.active, merl_set_cases.same_bits, merl_set_cases.inactive_values
 KINDS, M, N = model_set_cases.KINDS, model_set_cases.M, model_set_cases.N
@@ -228,7 +229,6 @@ def tiled(a, n):
 
 # ------------------------------------------------------------------ refusals through the C ABI (host arrays): the status, the message, nothing written
 INVALID = 1
-CANARY = np.float32(-777.25)
 
 def _views(n):
     d = np.tile(np.float32([[0.3, 0.1, 0.9]]), (n, 1))

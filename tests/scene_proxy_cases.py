@@ -32,6 +32,7 @@ import model_set_proxy_cases
 import proxy_is_cases
 import scene_cases
 import utia_set_cases
+from hit_calls import CANARY
 
 same_bits = merl_set_cases.same_bits
 N = scene_cases.N
@@ -291,7 +292,6 @@ def tiled(head_arrays, block_arrays, n):
 
 # ------------------------------------------------------------------ the C ABI's refusals (host arrays): the status, the message, nothing written
 INVALID, NOT_IMPLEMENTED = 1, 5
-CANARY = np.float32(-777.25)
 
 
 def c_sample(ctx, s, proxy, n=4, out_pdf=True, out_w=True, material=True):

@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import hit_calls
 import merl_set_cases as cases
 import proxy_is_cases
 from dj_brdf_amd import _lib, djb, synth
@@ -34,10 +35,6 @@ def proxies(gpu_ctx):
     return {"ggx": djb.ggx(ctx=gpu_ctx), "beckmann": djb.beckmann(ctx=gpu_ctx)}
 
 
-def _dev(ctx):
-    return f"cuda:{ctx.device}"
-
-
 def _vec(a, layout, dev):
     import torch
     return torch.from_numpy(np.array(a if layout == "strided" else a.T, order="C")).to(dev)        # [n, 3] | [3, n]
@@ -50,10 +47,7 @@ def _back(t, layout):
 
 def _soa(t):
     """the view of a [3, n] device tensor, spelled out: djb._Vec reads a [3, 3] array as three records"""
-    n = t.shape[1]
-    v = _lib.Vec3View()
-    v.x, v.y, v.z, v.stride = t.data_ptr(), t.data_ptr() + 4 * n, t.data_ptr() + 8 * n, 1
-    return v
+    return hit_calls.view(t.data_ptr(), t.shape[1], "dense")
 
 
 def _eval(s, ids, i, o, want_cos, layout):
@@ -61,7 +55,7 @@ def _eval(s, ids, i, o, want_cos, layout):
     call = s.evalp if want_cos else s.eval
     if layout == "host":
         return call(ids, i, o)
-    dev = _dev(s.ctx)
+    dev = hit_calls.dev(s.ctx)
     dids = torch.from_numpy(np.array(ids)).to(dev)
     if layout == "strided":
         out = call(dids, _vec(i, layout, dev), _vec(o, layout, dev))
@@ -78,7 +72,7 @@ def _sample(s, proxy, ids, u1, u2, o, layout):
     import torch
     if layout == "host":
         return s.evalp_is_proxy(proxy, ids, u1, u2, o)
-    dev = _dev(s.ctx)
+    dev = hit_calls.dev(s.ctx)
     t = lambda a: torch.from_numpy(np.array(a)).to(dev)
     dids, d1, d2, do = t(ids), t(u1), t(u2), _vec(o, layout, dev)
     if layout == "strided":
@@ -140,7 +134,7 @@ def _near_normal_block(n):
 
 def _guard_stats(ctx, i, o):
     import torch
-    dev = _dev(ctx)
+    dev = hit_calls.dev(ctx)
     return djb.merl_guard_stats(torch.from_numpy(np.ascontiguousarray(i.T)).to(dev), torch.from_numpy(np.ascontiguousarray(o.T)).to(dev), ctx=ctx)
 
 
@@ -206,7 +200,7 @@ def test_outputs_stay_inside_their_bands(gpu_ctx, mset, proxies, layout):
     import torch
     from test_gpu_bounds import Buf
     lib = _lib.load()
-    dev = _dev(gpu_ctx)
+    dev = hit_calls.dev(gpu_ctx)
     aos, a16 = layout == "aos", layout == "soa16"
     all_ids, _ = cases.material_ids()
     for n in (1, 3, 63, 65, 255, 257, 1023, 4097):
@@ -276,39 +270,22 @@ def test_both_calls_replay_from_a_captured_graph(gpu_ctx, mset, proxies):
     import torch
     lib = _lib.load()
     n = 1 << 14
-    dev = _dev(gpu_ctx)
-    side = torch.cuda.Stream(device=gpu_ctx.device)
-    with torch.cuda.stream(side):
-        i = djb.gen_directions(n, synth.SEED_I, ctx=gpu_ctx); o = djb.gen_directions(n, synth.SEED_O, ctx=gpu_ctx)
-        u1 = djb.gen_uniforms(n, synth.SEED_U1, ctx=gpu_ctx); u2 = djb.gen_uniforms(n, synth.SEED_U2, ctx=gpu_ctx)
-        ids = torch.from_numpy(np.ascontiguousarray(cases.material_ids()[0][:n])).to(dev)
-        fr, w, si = (torch.zeros((3, n), dtype=torch.float32, device=dev) for _ in range(3))
-        pdf = torch.zeros(n, dtype=torch.float32, device=dev)
-        vi, vo, vfr, vw, vsi = djb._Vec(i), djb._Vec(o), djb._Vec(fr), djb._Vec(w), djb._Vec(si)
+    dev = hit_calls.dev(gpu_ctx)
+    i = djb.gen_directions(n, synth.SEED_I, ctx=gpu_ctx); o = djb.gen_directions(n, synth.SEED_O, ctx=gpu_ctx)
+    u1 = djb.gen_uniforms(n, synth.SEED_U1, ctx=gpu_ctx); u2 = djb.gen_uniforms(n, synth.SEED_U2, ctx=gpu_ctx)
+    ids = torch.from_numpy(np.ascontiguousarray(cases.material_ids()[0][:n])).to(dev)
+    fr, w, si = (torch.zeros((3, n), dtype=torch.float32, device=dev) for _ in range(3))
+    pdf = torch.zeros(n, dtype=torch.float32, device=dev)
+    vi, vo, vfr, vw, vsi = djb._Vec(i), djb._Vec(o), djb._Vec(fr), djb._Vec(w), djb._Vec(si)
 
-        def launch():
-            _lib.check(lib.djb_merl_set_eval_batch(gpu_ctx._h, mset._h, C.c_int64(n), C.c_void_p(ids.data_ptr()), C.byref(vi.view), C.byref(vo.view),
-                                                   C.c_int(1), C.byref(vfr.view), C.c_int(_lib.MEM_DEVICE)))
-            _lib.check(lib.djb_merl_set_evalp_is_proxy_batch(gpu_ctx._h, mset._h, proxies["beckmann"]._h, C.c_int64(n), C.c_void_p(ids.data_ptr()),
-                                                             C.c_void_p(u1.data_ptr()), C.c_void_p(u2.data_ptr()), C.byref(vo.view), C.byref(vw.view),
-                                                             C.byref(vsi.view), C.c_void_p(pdf.data_ptr()), C.c_int(_lib.MEM_DEVICE)))
-        outs = (fr, w, si, pdf)
-        launch()                            # eager: the results to hold the replay against
-        side.synchronize()
-        want = [a.clone() for a in outs]
-        for a in outs:
-            a.zero_()
-        side.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=side):
-        launch()
-    for a in outs:                          # capture executes nothing
-        assert not a.any(), "a call ran during capture instead of being recorded"
-    g.replay()
-    torch.cuda.synchronize()
+    def launch():
+        _lib.check(lib.djb_merl_set_eval_batch(gpu_ctx._h, mset._h, C.c_int64(n), C.c_void_p(ids.data_ptr()), C.byref(vi.view), C.byref(vo.view),
+                                               C.c_int(1), C.byref(vfr.view), C.c_int(_lib.MEM_DEVICE)))
+        _lib.check(lib.djb_merl_set_evalp_is_proxy_batch(gpu_ctx._h, mset._h, proxies["beckmann"]._h, C.c_int64(n), C.c_void_p(ids.data_ptr()),
+                                                         C.c_void_p(u1.data_ptr()), C.c_void_p(u2.data_ptr()), C.byref(vo.view), C.byref(vw.view),
+                                                         C.byref(vsi.view), C.c_void_p(pdf.data_ptr()), C.c_int(_lib.MEM_DEVICE)))
+    want, = hit_calls.graph_replay(gpu_ctx, launch, (fr, w, si, pdf), [lambda: None])      # one data set, resident
     assert want[0].abs().sum() > 0 and want[3].abs().sum() > 0
-    for a, e in zip(outs, want):
-        assert torch.equal(a.view(torch.int32), e.view(torch.int32)), "graph replay differs from the direct call"
 
 
 # ------------------------------------------------------------------ 7. contexts
@@ -316,7 +293,7 @@ def test_objects_of_other_contexts_are_refused(gpu_ctx, mset, proxies):
     import torch
     lib = _lib.load()
     n = 4096
-    dev = _dev(gpu_ctx)
+    dev = hit_calls.dev(gpu_ctx)
 
     def status(ctx, s, proxy, mem_device):
         if mem_device:

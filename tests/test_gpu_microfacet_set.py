@@ -12,11 +12,11 @@ import pytest
 
 import microfacet_set_cases as cases
 from dj_brdf_amd import _lib, djb
+from hit_calls import Arrays, dev, graph_replay, loads, resident, view
 
 pytestmark = pytest.mark.gpu
 PREFIXES = (1, 3, 4, 5, 63, 64, 65, 255, 256, 257, 1023, 1025)
 LAYOUTS = ("host", "dense", "strided")
-CANARY = np.float32(-777.25)
 ROWS_LDS = 200                 # rows: MF_ROWS_LDS of djb_kernels_microfacet_set.hip
 GRID_CAP = 256 * 8             # workgroups: GRID_CAP of djb_kernels_microfacet_set.hip (rows in LDS)
 # op -> (want bits of djb_microfacet_set_eval_batch, outputs) / (evalp_is?, outputs)
@@ -40,93 +40,33 @@ def sets(gpu_ctx):
         s.close()
 
 
-def _dev(ctx):
-    return f"cuda:{ctx.device}"
-
-
-def _view(ptr, n_alloc, layout):
-    v = _lib.Vec3View()
-    if layout == "dense":                         # [3, n_alloc]
-        v.x, v.y, v.z, v.stride = ptr, ptr + 4 * n_alloc, ptr + 8 * n_alloc, 1
-    else:                                         # [n_alloc, 3]
-        v.x, v.y, v.z, v.stride = ptr, ptr + 4, ptr + 8, 3
-    return v
-
-
-class _Arrays:
-    """the arrays of one call in one layout: inputs as given, every output n + 1 units long with a canary in the last one"""
-
-    def __init__(self, ctx, n, layout):
-        self.ctx, self.n, self.layout, self.host = ctx, n, layout, layout == "host"
-        self.vl = "strided" if self.host else layout
-        self.keep, self.outs = [], {}
-
-    def vec_in(self, a, n_alloc=None):
-        n_alloc = self.n if n_alloc is None else n_alloc
-        if self.host:
-            h = np.ascontiguousarray(a, np.float32)
-            self.keep.append(h)
-            return _view(h.ctypes.data, n_alloc, "strided")
-        import torch
-        d = torch.from_numpy(np.array(a.T if self.layout == "dense" else a, dtype=np.float32, order="C")).to(_dev(self.ctx))
-        self.keep.append(d)
-        return _view(d.data_ptr(), n_alloc, self.layout)
-
-    def arr_in(self, a, dtype=np.float32):
-        h = np.array(a, dtype)                    # a writable copy: the cases' arrays are read-only
-        if self.host:
-            self.keep.append(h)
-            return C.c_void_p(h.ctypes.data)
-        import torch
-        d = torch.from_numpy(h).to(_dev(self.ctx))
-        self.keep.append(d)
-        return C.c_void_p(d.data_ptr())
-
-    def vec_out(self, name):
-        v = self.vec_in(np.full((self.n + 1, 3), CANARY, np.float32), self.n + 1)
-        self.outs[name] = (self.keep[-1], 3)
-        return C.byref(v)
-
-    def arr_out(self, name):
-        p = self.arr_in(np.full(self.n + 1, CANARY, np.float32))
-        self.outs[name] = (self.keep[-1], 1)
-        return p
-
-    def results(self, tag):
-        res = {}
-        if not self.host:
-            import torch
-            torch.cuda.synchronize()
-        for name, (a, width) in self.outs.items():
-            h = a if self.host else a.cpu().numpy()
-            if width == 3 and self.layout == "dense":
-                h = h.T
-            assert (h[self.n] == CANARY).all(), f"{tag}, {self.layout}, n = {self.n}: the unit behind output {name} was written"
-            res[name] = np.ascontiguousarray(h[:self.n])
-        return res
-
-
-def _call(s, op, ids, a, b, c=None, layout="dense", ctx=None):
-    """one call through the C ABI.  eval ops: a, b = i, o; sampling ops: a, b, c = u1, u2, o.  -> {output name: array}"""
+def _call(s, op, ids, a, b, c=None, layout="dense", ctx=None, over={}):
+    """one call through the C ABI.  eval ops: a, b = i, o; sampling ops: a, b, c = u1, u2, o.  over = {output: input}: that output's
+    arrays are that input's arrays.  -> {output name: array}"""
     ctx = ctx or s.ctx
     n = len(ids)
-    A = _Arrays(ctx, n, layout)
-    mem = C.c_int(_lib.MEM_HOST if A.host else _lib.MEM_DEVICE)
+    A = Arrays(ctx, n, layout)
+    mem = C.c_int(A.mem)
     lib = _lib.load()
+    pid = A.arr_in(ids, np.int32)
+
+    def out(name, make, wanted):
+        if not wanted:
+            return None
+        if name not in over:
+            return make(name)
+        return C.byref(ins[over[name]]) if make == A.vec_out else ins[over[name]]
     if op in EVAL:
         want, outs = EVAL[op]
-        pid, vi, vo = A.arr_in(ids, np.int32), A.vec_in(a), A.vec_in(b)
-        fr = A.vec_out("fr") if "fr" in outs else None
-        pdf = A.arr_out("pdf") if "pdf" in outs else None
-        _lib.check(lib.djb_microfacet_set_eval_batch(ctx._h, s._h, C.c_int64(n), pid, C.byref(vi), C.byref(vo), C.c_int(want), fr, pdf, mem))
+        ins = {"i": A.vec_in(a), "o": A.vec_in(b)}
+        _lib.check(lib.djb_microfacet_set_eval_batch(ctx._h, s._h, C.c_int64(n), pid, C.byref(ins["i"]), C.byref(ins["o"]), C.c_int(want),
+                                                     out("fr", A.vec_out, "fr" in outs), out("pdf", A.arr_out, "pdf" in outs), mem))
     else:
         is_, outs = SAMPLE[op]
-        pid, p1, p2, vo = A.arr_in(ids, np.int32), A.arr_in(a), A.arr_in(b), A.vec_in(c)
-        w = A.vec_out("w") if is_ else None
-        i_ = A.vec_out("i")
-        pdf = A.arr_out("pdf") if is_ else None
-        _lib.check(lib.djb_microfacet_set_sample_batch(ctx._h, s._h, C.c_int64(n), pid, p1, p2, C.byref(vo), w, i_, pdf, mem))
-    return A.results(op)
+        ins = {"u1": A.arr_in(a), "u2": A.arr_in(b), "o": A.vec_in(c)}
+        _lib.check(lib.djb_microfacet_set_sample_batch(ctx._h, s._h, C.c_int64(n), pid, ins["u1"], ins["u2"], C.byref(ins["o"]),
+                                                       out("w", A.vec_out, is_), out("i", A.vec_out, True), out("pdf", A.arr_out, is_), mem))
+    return dict(A.results(op), **{name: A.read(ins[src]) for name, src in over.items()})
 
 
 def _inputs(op, ev, sm, n=None):
@@ -299,88 +239,43 @@ def test_the_first_waves_are_wholly_dead(sets, kind, op):
 @pytest.mark.parametrize("kind", cases.KINDS)
 @pytest.mark.parametrize("layout", ["dense", "strided"])
 def test_in_place_calls_equal_out_of_place(gpu_ctx, sets, kind, layout):
-    import torch
-    lib = _lib.load()
     ids, i, o, u1, u2 = cases.mix_block()
-    n = len(ids)
-    dev = _dev(gpu_ctx)
-    dids = torch.from_numpy(np.array(ids)).to(dev)
-    up = lambda a: torch.from_numpy(np.array(a.T if layout == "dense" and a.ndim == 2 else a, order="C")).to(dev)
-    back = lambda d: np.ascontiguousarray(d.cpu().numpy().T if layout == "dense" else d.cpu().numpy())
     want = cases.mix_expected(kind)
     for which in ("i", "o"):                          # evalp + pdf: fr over i's (o's) arrays
-        di, do, dpdf = up(i), up(o), torch.zeros(n, dtype=torch.float32, device=dev)
-        vi, vo = _view(di.data_ptr(), n, layout), _view(do.data_ptr(), n, layout)
-        _lib.check(lib.djb_microfacet_set_eval_batch(gpu_ctx._h, sets[kind]._h, C.c_int64(n), C.c_void_p(dids.data_ptr()), C.byref(vi), C.byref(vo), C.c_int(6),
-                                                     C.byref(vi if which == "i" else vo), C.c_void_p(dpdf.data_ptr()), C.c_int(_lib.MEM_DEVICE)))
-        torch.cuda.synchronize()
-        cases.assert_bits(f"in place over {which}, {kind}, {layout}", back(di if which == "i" else do), want["evalp"])
-        cases.assert_bits(f"in place over {which}, {kind}, {layout}: pdf", dpdf.cpu().numpy(), want["pdf"])
-    # evalp_is: i over o's arrays, pdf over u1
-    do, d1, d2 = up(o), up(u1), up(u2)
-    dw = torch.zeros_like(do)
-    vo, vw = _view(do.data_ptr(), n, layout), _view(dw.data_ptr(), n, layout)
-    _lib.check(lib.djb_microfacet_set_sample_batch(gpu_ctx._h, sets[kind]._h, C.c_int64(n), C.c_void_p(dids.data_ptr()), C.c_void_p(d1.data_ptr()),
-                                                   C.c_void_p(d2.data_ptr()), C.byref(vo), C.byref(vw), C.byref(vo), C.c_void_p(d1.data_ptr()), C.c_int(_lib.MEM_DEVICE)))
-    torch.cuda.synchronize()
-    for name, got, w in zip(("weight", "i", "pdf"), (back(dw), back(do), d1.cpu().numpy()), want["evalp_is"]):
-        cases.assert_bits(f"evalp_is in place, {kind}, {layout}: {name}", got, w)
+        got = _call(sets[kind], "evalp_pdf", ids, i, o, layout=layout, over={"fr": which})
+        cases.assert_bits(f"in place over {which}, {kind}, {layout}", got["fr"], want["evalp"])
+        cases.assert_bits(f"in place over {which}, {kind}, {layout}: pdf", got["pdf"], want["pdf"])
+    got = _call(sets[kind], "evalp_is", ids, u1, u2, o, layout=layout, over={"i": "o", "pdf": "u1"})      # i over o's arrays, pdf over u1
+    for name, out, w in zip(("weight", "i", "pdf"), ("w", "i", "pdf"), want["evalp_is"]):
+        cases.assert_bits(f"evalp_is in place, {kind}, {layout}: {name}", got[out], w)
 
 
 # ------------------------------------------------------------------ 8. graph capture
 def test_calls_replay_from_a_captured_graph(gpu_ctx, sets):
     import torch
     lib = _lib.load()
-    dev = _dev(gpu_ctx)
     mids, mi, mo, mu1, mu2 = cases.mix_block()
     n = len(mids)
     ids2, _ = cases.material_ids()
     (i2, o2), (_, u12, u22) = cases.eval_inputs(), cases.sample_inputs()
     data = [(mids, mi, mo, mu1, mu2), (ids2[:n], i2[:n], o2[:n], u12[:n], u22[:n])]
-    side = torch.cuda.Stream(device=gpu_ctx.device)
-    up = lambda a: torch.from_numpy(np.array(a.T if a.ndim == 2 else a, order="C")).to(dev)
-    with torch.cuda.stream(side):
-        ids, i, o, u1, u2 = (up(a) for a in data[0])
-        vec = lambda: torch.zeros((3, n), dtype=torch.float32, device=dev)
-        outs = {k: {"fr": vec(), "pdf": torch.zeros(n, dtype=torch.float32, device=dev), "w": vec(), "i": vec(), "ipdf": torch.zeros(n, dtype=torch.float32, device=dev)}
-                for k in cases.KINDS}
-        vi, vo = _view(i.data_ptr(), n, "dense"), _view(o.data_ptr(), n, "dense")
+    ids, i, o, u1, u2 = (resident(gpu_ctx, a) for a in data[0])
+    vec = lambda: torch.zeros((3, n), dtype=torch.float32, device=dev(gpu_ctx))
+    sca = lambda: torch.zeros(n, dtype=torch.float32, device=dev(gpu_ctx))
+    outs = {k: {"fr": vec(), "pdf": sca(), "w": vec(), "i": vec(), "ipdf": sca()} for k in cases.KINDS}
+    vi, vo = view(i.data_ptr(), n, "dense"), view(o.data_ptr(), n, "dense")
 
-        def launch():                       # two device-memory calls per kind: evalp + pdf, evalp_is
-            for k in cases.KINDS:
-                a = outs[k]
-                _lib.check(lib.djb_microfacet_set_eval_batch(gpu_ctx._h, sets[k]._h, C.c_int64(n), C.c_void_p(ids.data_ptr()), C.byref(vi), C.byref(vo), C.c_int(6),
-                                                             C.byref(_view(a["fr"].data_ptr(), n, "dense")), C.c_void_p(a["pdf"].data_ptr()), C.c_int(_lib.MEM_DEVICE)))
-                _lib.check(lib.djb_microfacet_set_sample_batch(gpu_ctx._h, sets[k]._h, C.c_int64(n), C.c_void_p(ids.data_ptr()), C.c_void_p(u1.data_ptr()),
-                                                               C.c_void_p(u2.data_ptr()), C.byref(vo), C.byref(_view(a["w"].data_ptr(), n, "dense")),
-                                                               C.byref(_view(a["i"].data_ptr(), n, "dense")), C.c_void_p(a["ipdf"].data_ptr()), C.c_int(_lib.MEM_DEVICE)))
-
-        def load(which):
-            for dst, src in zip((ids, i, o, u1, u2), data[which]):
-                dst.copy_(up(src))
-        flat = lambda: [a for k in cases.KINDS for a in outs[k].values()]
-        want = []
-        for which in (0, 1):                # eager: the warm call, and the results to hold the replays against
-            load(which); launch(); side.synchronize()
-            want.append([a.clone() for a in flat()])
-        for a in flat():
-            a.zero_()
-        side.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=side):
-        launch()
-    for a in flat():                        # capture executes nothing
-        assert not a.any(), "a call ran during capture instead of being recorded"
+    def launch():                           # two device-memory calls per kind: evalp + pdf, evalp_is
+        for k in cases.KINDS:
+            a = outs[k]
+            _lib.check(lib.djb_microfacet_set_eval_batch(gpu_ctx._h, sets[k]._h, C.c_int64(n), C.c_void_p(ids.data_ptr()), C.byref(vi), C.byref(vo), C.c_int(6),
+                                                         C.byref(view(a["fr"].data_ptr(), n, "dense")), C.c_void_p(a["pdf"].data_ptr()), C.c_int(_lib.MEM_DEVICE)))
+            _lib.check(lib.djb_microfacet_set_sample_batch(gpu_ctx._h, sets[k]._h, C.c_int64(n), C.c_void_p(ids.data_ptr()), C.c_void_p(u1.data_ptr()),
+                                                           C.c_void_p(u2.data_ptr()), C.byref(vo), C.byref(view(a["w"].data_ptr(), n, "dense")),
+                                                           C.byref(view(a["i"].data_ptr(), n, "dense")), C.c_void_p(a["ipdf"].data_ptr()), C.c_int(_lib.MEM_DEVICE)))
+    want = graph_replay(gpu_ctx, launch, [a for k in cases.KINDS for a in outs[k].values()], loads(gpu_ctx, (ids, i, o, u1, u2), data))
     assert want[0][0].abs().sum() > 0 and not torch.equal(want[0][0], want[1][0])
     cases.assert_bits("eager, ggx evalp", want[0][0].cpu().numpy().T, cases.mix_expected("ggx")["evalp"])
-    for which in (0, 1):
-        with torch.cuda.stream(side):
-            load(which)
-        side.synchronize()
-        g.replay()
-        torch.cuda.synchronize()
-        for a, e in zip(flat(), want[which]):
-            assert torch.equal(a.view(torch.int32), e.view(torch.int32)), f"graph replay {which} differs from the direct call"
 
 
 # ------------------------------------------------------------------ 9. set_params in stream order, contexts

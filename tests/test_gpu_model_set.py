@@ -12,12 +12,12 @@ import pytest
 
 import model_set_cases as cases
 from dj_brdf_amd import _lib, djb, synth
+from hit_calls import Arrays, dev, graph_replay, loads, resident, view
 
 pytestmark = pytest.mark.gpu
 PREFIXES = (1, 3, 4, 5, 63, 64, 65, 255, 256, 257, 1023, 1025)
 LAYOUTS = ("host", "dense", "strided")
 OPS = ((0, "eval"), (1, "evalp"))
-CANARY = np.float32(-777.25)
 GRID_CAP = 256 * 16            # workgroups: GRID_CAP of djb_kernels_model_set.hip (launch_set), as k_eval's for these kinds
 
 
@@ -37,47 +37,15 @@ def sets(gpu_ctx):
         s.close()
 
 
-def _dev(ctx):
-    return f"cuda:{ctx.device}"
-
-
-def _view(ptr, n_alloc, layout):
-    v = _lib.Vec3View()
-    if layout == "dense":                         # [3, n_alloc]
-        v.x, v.y, v.z, v.stride = ptr, ptr + 4 * n_alloc, ptr + 8 * n_alloc, 1
-    else:                                         # [n_alloc, 3]
-        v.x, v.y, v.z, v.stride = ptr, ptr + 4, ptr + 8, 3
-    return v
-
-
-def _call(s, ids, i, o, want_cos, layout, ctx=None):
-    """one call through the C ABI -> [n, 3]; the output has n + 1 units, the last one a canary"""
-    import torch
+def _call(s, ids, i, o, want_cos, layout, ctx=None, over=None):
+    """one call through the C ABI -> [n, 3]; over = "i" / "o": the output arrays are that input's arrays"""
     ctx = ctx or s.ctx
-    n = len(ids)
-    ids = np.array(ids, np.int32)                 # a writable copy: the cases' arrays are read-only
-    if layout == "host":
-        hi, ho = np.ascontiguousarray(i, np.float32), np.ascontiguousarray(o, np.float32)
-        out = np.full((n + 1, 3), CANARY, np.float32)
-        st = _lib.load().djb_model_set_eval_batch(ctx._h, s._h, C.c_int64(n), C.c_void_p(ids.ctypes.data), C.byref(_view(hi.ctypes.data, n, "strided")),
-                                                  C.byref(_view(ho.ctypes.data, n, "strided")), C.c_int(want_cos), C.byref(_view(out.ctypes.data, n + 1, "strided")),
-                                                  C.c_int(_lib.MEM_HOST))
-        _lib.check(st)
-        res = out
-    else:
-        dev = _dev(ctx)
-        up = lambda a: torch.from_numpy(np.array(a.T if layout == "dense" else a, order="C")).to(dev)
-        dids, di, do = torch.from_numpy(ids).to(dev), up(i), up(o)
-        out = torch.full((3, n + 1) if layout == "dense" else (n + 1, 3), float(CANARY), dtype=torch.float32, device=dev)
-        st = _lib.load().djb_model_set_eval_batch(ctx._h, s._h, C.c_int64(n), C.c_void_p(dids.data_ptr()), C.byref(_view(di.data_ptr(), n, layout)),
-                                                  C.byref(_view(do.data_ptr(), n, layout)), C.c_int(want_cos), C.byref(_view(out.data_ptr(), n + 1, layout)),
-                                                  C.c_int(_lib.MEM_DEVICE))
-        _lib.check(st)
-        torch.cuda.synchronize()
-        res = out.cpu().numpy()
-        res = res.T if layout == "dense" else res
-    assert (res[n] == CANARY).all(), f"{layout}, n = {n}: the unit behind the output was written"
-    return np.ascontiguousarray(res[:n])
+    A = Arrays(ctx, len(ids), layout)
+    pid, vi, vo = A.arr_in(ids, np.int32), A.vec_in(i), A.vec_in(o)
+    alias = {"i": vi, "o": vo}.get(over)
+    out = A.vec_out("fr") if alias is None else C.byref(alias)
+    _lib.check(_lib.load().djb_model_set_eval_batch(ctx._h, s._h, C.c_int64(A.n), pid, C.byref(vi), C.byref(vo), C.c_int(want_cos), out, C.c_int(A.mem)))
+    return A.results("eval")["fr"] if alias is None else A.read(alias)
 
 
 # ------------------------------------------------------------------ 1. bits equal to the oracle selection
@@ -207,71 +175,33 @@ def test_a_wave_of_dead_hits_among_live_ones(sets, kind):
 def test_calls_replay_from_a_captured_graph(gpu_ctx, sets):
     import torch
     lib = _lib.load()
-    dev = _dev(gpu_ctx)
     gids, gi, go = cases.wall_block("sgd")
     n = len(gids)
     ids2, _ = cases.material_ids()
     i2, o2 = cases.eval_inputs()
     data = [(gids, gi, go), (ids2[:n], i2[:n], o2[:n])]
-    side = torch.cuda.Stream(device=gpu_ctx.device)
-    up = lambda a: torch.from_numpy(np.array(a.T if a.ndim == 2 else a, order="C")).to(dev)
-    with torch.cuda.stream(side):
-        ids, i, o = (up(a) for a in data[0])
-        outs = [torch.zeros((3, n), dtype=torch.float32, device=dev) for _ in range(4)]
-        vi, vo = _view(i.data_ptr(), n, "dense"), _view(o.data_ptr(), n, "dense")
-        vouts = [_view(a.data_ptr(), n, "dense") for a in outs]
+    ids, i, o = (resident(gpu_ctx, a) for a in data[0])
+    outs = [torch.zeros((3, n), dtype=torch.float32, device=dev(gpu_ctx)) for _ in range(4)]
+    vi, vo = view(i.data_ptr(), n, "dense"), view(o.data_ptr(), n, "dense")
+    vouts = [view(a.data_ptr(), n, "dense") for a in outs]
 
-        def launch():                       # four device-memory calls: sgd eval, sgd evalp, abc eval, abc evalp
-            for k, vout in enumerate(vouts):
-                _lib.check(lib.djb_model_set_eval_batch(gpu_ctx._h, sets[cases.KINDS[k >> 1]]._h, C.c_int64(n), C.c_void_p(ids.data_ptr()), C.byref(vi), C.byref(vo),
-                                                        C.c_int(k & 1), C.byref(vout), C.c_int(_lib.MEM_DEVICE)))
-
-        def load(which):
-            for dst, src in zip((ids, i, o), data[which]):
-                dst.copy_(up(src))
-        want = []
-        for which in (0, 1):                # eager: the warm call, and the results to hold the replays against
-            load(which); launch(); side.synchronize()
-            want.append([a.clone() for a in outs])
-        for a in outs:
-            a.zero_()
-        side.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=side):
-        launch()
-    for a in outs:                          # capture executes nothing
-        assert not a.any(), "a call ran during capture instead of being recorded"
+    def launch():                           # four device-memory calls: sgd eval, sgd evalp, abc eval, abc evalp
+        for k, vout in enumerate(vouts):
+            _lib.check(lib.djb_model_set_eval_batch(gpu_ctx._h, sets[cases.KINDS[k >> 1]]._h, C.c_int64(n), C.c_void_p(ids.data_ptr()), C.byref(vi), C.byref(vo),
+                                                    C.c_int(k & 1), C.byref(vout), C.c_int(_lib.MEM_DEVICE)))
+    want = graph_replay(gpu_ctx, launch, outs, loads(gpu_ctx, (ids, i, o), data))
     assert want[0][1].abs().sum() > 0 and not torch.equal(want[0][1], want[1][1])
     cases.assert_eval("eager, sgd evalp", want[0][1].cpu().numpy().T, cases.wall_expected("sgd", "evalp"))
-    for which in (0, 1):
-        with torch.cuda.stream(side):
-            load(which)
-        side.synchronize()
-        g.replay()
-        torch.cuda.synchronize()
-        for a, e in zip(outs, want[which]):
-            assert torch.equal(a.view(torch.int32), e.view(torch.int32)), f"graph replay {which} differs from the direct call"
 
 
 # ------------------------------------------------------------------ 8. aliasing
 @pytest.mark.parametrize("kind", cases.KINDS)
 @pytest.mark.parametrize("layout", ["dense", "strided"])
 def test_in_place_call_equals_out_of_place(gpu_ctx, sets, kind, layout):
-    import torch
     ids, i, o = cases.wall_block(kind)
-    n = len(ids)
-    dev = _dev(gpu_ctx)
     want = _call(sets[kind], ids, i, o, 1, layout)
-    dids = torch.from_numpy(np.array(ids)).to(dev)
-    up = lambda a: torch.from_numpy(np.array(a.T if layout == "dense" else a, order="C")).to(dev)
     for which in ("i", "o"):
-        di, do = up(i), up(o)
-        vi, vo = _view(di.data_ptr(), n, layout), _view(do.data_ptr(), n, layout)
-        _lib.check(_lib.load().djb_model_set_eval_batch(gpu_ctx._h, sets[kind]._h, C.c_int64(n), C.c_void_p(dids.data_ptr()), C.byref(vi), C.byref(vo), C.c_int(1),
-                                                        C.byref(vi if which == "i" else vo), C.c_int(_lib.MEM_DEVICE)))      # the output arrays are i's (o's) arrays
-        torch.cuda.synchronize()
-        got = (di if which == "i" else do).cpu().numpy()
-        got = got.T if layout == "dense" else got
+        got = _call(sets[kind], ids, i, o, 1, layout, over=which)      # the output arrays are i's (o's) arrays
         cases.assert_eval(f"in place over {which}, {kind}, {layout}", got, want)
         cases.assert_eval(f"in place over {which}, {kind}, {layout}, against the oracle", got, cases.wall_expected(kind, "evalp"))
 

@@ -14,10 +14,10 @@ import pytest
 import model_set_cases
 import model_set_proxy_cases as cases
 from dj_brdf_amd import _lib, djb
+from hit_calls import Arrays, dev, graph_replay, loads, resident, view
 
 pytestmark = pytest.mark.gpu
 LAYOUTS = ("host", "dense", "strided")
-CANARY = np.float32(-777.25)
 
 
 @pytest.fixture(scope="module")
@@ -33,80 +33,24 @@ def sets(gpu_ctx):
         s.close()
 
 
-def _view(ptr, n_alloc, layout):
-    v = _lib.Vec3View()
-    if layout == "dense":                         # [3, n_alloc]
-        v.x, v.y, v.z, v.stride = ptr, ptr + 4 * n_alloc, ptr + 8 * n_alloc, 1
-    else:                                         # [n_alloc, 3]
-        v.x, v.y, v.z, v.stride = ptr, ptr + 4, ptr + 8, 3
-    return v
-
-
-class _Buffers:
-    """the arrays of one call where `layout` puts them; every output has n + 1 units, the last one a canary"""
-
-    def __init__(self, ctx, n, layout):
-        self.n, self.layout, self.host = n, layout, layout == "host"
-        self.dev = f"cuda:{ctx.device}"
-        self.mem = _lib.MEM_HOST if self.host else _lib.MEM_DEVICE
-        self.keep = []
-
-    def _put(self, a):
-        import torch
-        if self.host:
-            a = np.ascontiguousarray(a)
-            self.keep.append(a)
-            return a, a.ctypes.data
-        t = torch.from_numpy(np.array(a, order="C")).to(self.dev)
-        self.keep.append(t)
-        return t, t.data_ptr()
-
-    def scalars(self, a):
-        return C.c_void_p(self._put(np.asarray(a))[1])
-
-    def vec(self, a):
-        a = np.asarray(a, np.float32)
-        _, ptr = self._put(a.T if self.layout == "dense" else a)
-        return C.byref(_view(ptr, self.n, "strided" if self.host else self.layout))
-
-    def out_vec(self):
-        shape = (3, self.n + 1) if self.layout == "dense" else (self.n + 1, 3)
-        t, ptr = self._put(np.full(shape, CANARY, np.float32))
-        return t, C.byref(_view(ptr, self.n + 1, "strided" if self.host else self.layout))
-
-    def out_scalars(self):
-        t, ptr = self._put(np.full(self.n + 1, CANARY, np.float32))
-        return t, C.c_void_p(ptr)
-
-    def back(self, t, tag):
-        import torch
-        if not self.host:
-            torch.cuda.synchronize()
-            t = t.cpu().numpy()
-        if t.ndim == 2 and self.layout == "dense":
-            t = t.T
-        assert (t[self.n] == CANARY).all(), f"{tag}, {self.layout}, n = {self.n}: the unit behind the output was written"
-        return np.ascontiguousarray(t[:self.n])
-
-
 def _sample(s, ids, u1, u2, o, layout, ctx=None):
     """djb_model_set_evalp_is_proxy_batch through the C ABI -> (weight, i, pdf)"""
     ctx = ctx or s.ctx
-    b = _Buffers(ctx, len(ids), layout)
-    w, vw = b.out_vec(); i, vi = b.out_vec(); pdf, ppdf = b.out_scalars()
-    _lib.check(_lib.load().djb_model_set_evalp_is_proxy_batch(ctx._h, s._h, C.c_int64(b.n), b.scalars(np.array(ids, np.int32)), b.scalars(np.array(u1, np.float32)),
-                                                             b.scalars(np.array(u2, np.float32)), b.vec(o), vw, vi, ppdf, C.c_int(b.mem)))
-    return b.back(w, "weight"), b.back(i, "i"), b.back(pdf, "pdf")
+    A = Arrays(ctx, len(ids), layout)
+    vo = A.vec_in(o)
+    _lib.check(_lib.load().djb_model_set_evalp_is_proxy_batch(ctx._h, s._h, C.c_int64(A.n), A.arr_in(ids, np.int32), A.arr_in(u1), A.arr_in(u2), C.byref(vo),
+                                                             A.vec_out("weight"), A.vec_out("i"), A.arr_out("pdf"), C.c_int(A.mem)))
+    return tuple(A.results("sampling").values())
 
 
 def _light(s, ids, i, o, layout, ctx=None):
     """djb_model_set_evalp_pdf_proxy_batch through the C ABI -> (fr, pdf)"""
     ctx = ctx or s.ctx
-    b = _Buffers(ctx, len(ids), layout)
-    fr, vfr = b.out_vec(); pdf, ppdf = b.out_scalars()
-    _lib.check(_lib.load().djb_model_set_evalp_pdf_proxy_batch(ctx._h, s._h, C.c_int64(b.n), b.scalars(np.array(ids, np.int32)), b.vec(i), b.vec(o), vfr, ppdf,
-                                                              C.c_int(b.mem)))
-    return b.back(fr, "fr"), b.back(pdf, "pdf")
+    A = Arrays(ctx, len(ids), layout)
+    vi, vo = A.vec_in(i), A.vec_in(o)
+    _lib.check(_lib.load().djb_model_set_evalp_pdf_proxy_batch(ctx._h, s._h, C.c_int64(A.n), A.arr_in(ids, np.int32), C.byref(vi), C.byref(vo), A.vec_out("fr"),
+                                                              A.arr_out("pdf"), C.c_int(A.mem)))
+    return tuple(A.results("light sample").values())
 
 
 def _head(arrays, n):
@@ -312,59 +256,31 @@ def test_calls_replay_from_a_captured_graph(gpu_ctx, sets):
     """the two calls of one bounce, captured into one graph after one warm call and replayed on new inputs"""
     import torch
     lib = _lib.load()
-    dev = f"cuda:{gpu_ctx.device}"
     n = 4096
     s = sets["sgd"]
     o_, u1_, u2_ = cases.sampler_inputs()
     li, lo = cases.light_inputs()
     data = [(cases.wall_ids("sgd"), u1_[:n], u2_[:n], o_[:n], li[:n], lo[:n]),
             (cases.material_ids()[n:2 * n], u1_[n:2 * n], u2_[n:2 * n], o_[n:2 * n], li[n:2 * n], lo[n:2 * n])]
-    side = torch.cuda.Stream(device=gpu_ctx.device)
-    up = lambda a: torch.from_numpy(np.array(a.T if a.ndim == 2 else a, order="C")).to(dev)
-    with torch.cuda.stream(side):
-        ids, u1, u2, o, i, o2 = (up(a) for a in data[0])
-        w, si, fr = (torch.zeros((3, n), dtype=torch.float32, device=dev) for _ in range(3))
-        spdf, lpdf = (torch.zeros(n, dtype=torch.float32, device=dev) for _ in range(2))
-        outs = [w, si, spdf, fr, lpdf]
-        v = lambda t: _view(t.data_ptr(), n, "dense")
-        vo, vw, vsi, vi, vo2, vfr = v(o), v(w), v(si), v(i), v(o2), v(fr)
+    ids, u1, u2, o, i, o2 = (resident(gpu_ctx, a) for a in data[0])
+    w, si, fr = (torch.zeros((3, n), dtype=torch.float32, device=dev(gpu_ctx)) for _ in range(3))
+    spdf, lpdf = (torch.zeros(n, dtype=torch.float32, device=dev(gpu_ctx)) for _ in range(2))
+    v = lambda t: view(t.data_ptr(), n, "dense")
+    vo, vw, vsi, vi, vo2, vfr = v(o), v(w), v(si), v(i), v(o2), v(fr)
 
-        def launch():
-            _lib.check(lib.djb_model_set_evalp_is_proxy_batch(gpu_ctx._h, s._h, C.c_int64(n), C.c_void_p(ids.data_ptr()), C.c_void_p(u1.data_ptr()),
-                                                              C.c_void_p(u2.data_ptr()), C.byref(vo), C.byref(vw), C.byref(vsi), C.c_void_p(spdf.data_ptr()),
-                                                              C.c_int(_lib.MEM_DEVICE)))
-            _lib.check(lib.djb_model_set_evalp_pdf_proxy_batch(gpu_ctx._h, s._h, C.c_int64(n), C.c_void_p(ids.data_ptr()), C.byref(vi), C.byref(vo2), C.byref(vfr),
-                                                               C.c_void_p(lpdf.data_ptr()), C.c_int(_lib.MEM_DEVICE)))
-
-        def load(which):
-            for dst, src in zip((ids, u1, u2, o, i, o2), data[which]):
-                dst.copy_(up(src))
-        want = []
-        for which in (0, 1):                # eager: the warm call, and the results to hold the replays against
-            load(which); launch(); side.synchronize()
-            want.append([a.clone() for a in outs])
-        for a in outs:
-            a.zero_()
-        side.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=side):
-        launch()
-    for a in outs:                          # capture executes nothing
-        assert not a.any(), "a call ran during capture instead of being recorded"
+    def launch():
+        _lib.check(lib.djb_model_set_evalp_is_proxy_batch(gpu_ctx._h, s._h, C.c_int64(n), C.c_void_p(ids.data_ptr()), C.c_void_p(u1.data_ptr()),
+                                                          C.c_void_p(u2.data_ptr()), C.byref(vo), C.byref(vw), C.byref(vsi), C.c_void_p(spdf.data_ptr()),
+                                                          C.c_int(_lib.MEM_DEVICE)))
+        _lib.check(lib.djb_model_set_evalp_pdf_proxy_batch(gpu_ctx._h, s._h, C.c_int64(n), C.c_void_p(ids.data_ptr()), C.byref(vi), C.byref(vo2), C.byref(vfr),
+                                                           C.c_void_p(lpdf.data_ptr()), C.c_int(_lib.MEM_DEVICE)))
+    want = graph_replay(gpu_ctx, launch, [w, si, spdf, fr, lpdf], loads(gpu_ctx, (ids, u1, u2, o, i, o2), data))
     assert want[0][2].abs().sum() > 0 and not torch.equal(want[0][2], want[1][2])
     ids0 = data[0][0]
     cases.assert_same("eager, sampling", [want[0][0].cpu().numpy().T, want[0][1].cpu().numpy().T, want[0][2].cpu().numpy()],
                       cases.select_all([_head(r, n) for r in cases.sample_per_material("sgd", 90, True)], ids0))
     cases.assert_light("eager, light sample", [want[0][3].cpu().numpy().T, want[0][4].cpu().numpy()],
                        cases.select_all([_head(r, n) for r in cases.light_per_material("sgd", 90, True)], ids0))
-    for which in (0, 1):
-        with torch.cuda.stream(side):
-            load(which)
-        side.synchronize()
-        g.replay()
-        torch.cuda.synchronize()
-        for a, e in zip(outs, want[which]):
-            assert torch.equal(a.view(torch.int32), e.view(torch.int32)), f"graph replay {which} differs from the direct call"
 
 
 # ------------------------------------------------------------------ 9. refusals

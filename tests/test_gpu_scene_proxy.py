@@ -16,11 +16,11 @@ import model_set_cases
 import scene_proxy_cases as cases
 import utia_set_cases
 from dj_brdf_amd import _lib, djb
+from hit_calls import CANARY, Arrays, dev, graph_replay, loads, resident, view
 
 pytestmark = pytest.mark.gpu
 PREFIXES = (1, 3, 63, 64, 65, 255, 256, 257, 1023, 1025)
 LAYOUTS = ("host", "dense", "strided")
-CANARY = cases.CANARY
 
 
 def _members(ctx, prepared=True):
@@ -61,97 +61,29 @@ def lobes(gpu_ctx):
     return {"ggx": djb.ggx(ctx=gpu_ctx), "beckmann": djb.beckmann(ctx=gpu_ctx)}
 
 
-def _dev(ctx):
-    return f"cuda:{ctx.device}"
-
-
-def _view(ptr, n_alloc, layout):
-    v = _lib.Vec3View()
-    if layout == "dense":                         # [3, n_alloc]
-        v.x, v.y, v.z, v.stride = ptr, ptr + 4 * n_alloc, ptr + 8 * n_alloc, 1
-    else:                                         # [n_alloc, 3]
-        v.x, v.y, v.z, v.stride = ptr, ptr + 4, ptr + 8, 3
-    return v
-
-
-class _Batch:
-    """the arrays of one call in `layout`: inputs as given, outputs of n + 1 units filled with the canary"""
-
-    def __init__(self, ctx, n, layout):
-        self.ctx, self.n, self.layout, self.keep = ctx, n, layout, []
-        self.mem = _lib.MEM_HOST if layout == "host" else _lib.MEM_DEVICE
-
-    def scalars(self, a, dtype=np.float32):
-        import torch
-        a = np.array(a, dtype)                    # a writable copy: the cases' arrays are read-only
-        if self.layout != "host":
-            a = torch.from_numpy(a).to(_dev(self.ctx))
-        self.keep.append(a)
-        return C.c_void_p(a.ctypes.data if self.layout == "host" else a.data_ptr())
-
-    def vec_in(self, a):
-        import torch
-        if self.layout == "host":
-            a = np.ascontiguousarray(a, np.float32)
-            self.keep.append(a)
-            return _view(a.ctypes.data, self.n, "strided")
-        t = torch.from_numpy(np.array(a.T if self.layout == "dense" else a, order="C")).to(_dev(self.ctx))
-        self.keep.append(t)
-        return _view(t.data_ptr(), self.n, self.layout)
-
-    def vec_out(self):
-        import torch
-        n = self.n + 1
-        if self.layout == "host":
-            a = np.full((n, 3), CANARY, np.float32)
-            return a, _view(a.ctypes.data, n, "strided")
-        a = torch.full((3, n) if self.layout == "dense" else (n, 3), float(CANARY), dtype=torch.float32, device=_dev(self.ctx))
-        return a, _view(a.data_ptr(), n, self.layout)
-
-    def scalar_out(self):
-        import torch
-        if self.layout == "host":
-            a = np.full(self.n + 1, CANARY, np.float32)
-            return a, C.c_void_p(a.ctypes.data)
-        a = torch.full((self.n + 1,), float(CANARY), dtype=torch.float32, device=_dev(self.ctx))
-        return a, C.c_void_p(a.data_ptr())
-
-    def results(self, tag, vecs, scalar):
-        """[n, 3] per vector output and [n] of the scalar one, after the canary behind each was checked"""
-        import torch
-        if self.layout != "host":
-            torch.cuda.synchronize()
-        out = []
-        for a in vecs + [scalar]:
-            a = a if self.layout == "host" else a.cpu().numpy()
-            a = a.T if self.layout == "dense" and a.ndim == 2 else a
-            assert (a[self.n] == CANARY).all(), f"{tag}, {self.layout}, n = {self.n}: the unit behind an output was written"
-            out.append(np.ascontiguousarray(a[:self.n]))
-        return tuple(out)
-
-
 def _h(x):
     return x._h if x is not None else None
 
 
-def _sample(s, proxy, ids, u1, u2, o, layout, ctx=None):
-    """one sampling call through the C ABI -> (weight [n, 3], i [n, 3], pdf [n])"""
-    b = _Batch(ctx or s.ctx, len(ids), layout)
-    w, vw = b.vec_out(); si, vsi = b.vec_out(); pdf, ppdf = b.scalar_out()
-    vo = b.vec_in(o)
-    _lib.check(_lib.load().djb_scene_evalp_is_proxy_batch(b.ctx._h, s._h, _h(proxy), C.c_int64(b.n), b.scalars(ids, np.int32), b.scalars(u1), b.scalars(u2),
-                                                         C.byref(vo), C.byref(vw), C.byref(vsi), ppdf, C.c_int(b.mem)))
-    return b.results("sampling", [w, si], pdf)
+def _sample(s, proxy, ids, u1, u2, o, layout, ctx=None, in_place=False):
+    """one sampling call through the C ABI -> (weight [n, 3], i [n, 3], pdf [n]); in_place: out_i names o's arrays"""
+    A = Arrays(ctx or s.ctx, len(ids), layout)
+    vo = A.vec_in(o)
+    _lib.check(_lib.load().djb_scene_evalp_is_proxy_batch(A.ctx._h, s._h, _h(proxy), C.c_int64(A.n), A.arr_in(ids, np.int32), A.arr_in(u1), A.arr_in(u2),
+                                                         C.byref(vo), A.vec_out("weight"), C.byref(vo) if in_place else A.vec_out("i"), A.arr_out("pdf"),
+                                                         C.c_int(A.mem)))
+    res = A.results("sampling")
+    return res["weight"], A.read(vo) if in_place else res["i"], res["pdf"]
 
 
-def _light(s, proxy, ids, i, o, layout, ctx=None):
-    """one light-sample call through the C ABI -> (fr [n, 3], pdf [n])"""
-    b = _Batch(ctx or s.ctx, len(ids), layout)
-    fr, vfr = b.vec_out(); pdf, ppdf = b.scalar_out()
-    vi, vo = b.vec_in(i), b.vec_in(o)
-    _lib.check(_lib.load().djb_scene_evalp_pdf_proxy_batch(b.ctx._h, s._h, _h(proxy), C.c_int64(b.n), b.scalars(ids, np.int32), C.byref(vi), C.byref(vo),
-                                                          C.byref(vfr), ppdf, C.c_int(b.mem)))
-    return b.results("light sample", [fr], pdf)
+def _light(s, proxy, ids, i, o, layout, ctx=None, in_place=False):
+    """one light-sample call through the C ABI -> (fr [n, 3], pdf [n]); in_place: out_fr names i's arrays"""
+    A = Arrays(ctx or s.ctx, len(ids), layout)
+    vi, vo = A.vec_in(i), A.vec_in(o)
+    _lib.check(_lib.load().djb_scene_evalp_pdf_proxy_batch(A.ctx._h, s._h, _h(proxy), C.c_int64(A.n), A.arr_in(ids, np.int32), C.byref(vi), C.byref(vo),
+                                                          C.byref(vi) if in_place else A.vec_out("fr"), A.arr_out("pdf"), C.c_int(A.mem)))
+    res = A.results("light sample")
+    return A.read(vi) if in_place else res["fr"], res["pdf"]
 
 
 def _check_sample(tag, s, lobe, pk, ids, table, o, u1, u2, want, layouts=LAYOUTS):
@@ -370,7 +302,6 @@ def test_calls_replay_from_a_captured_graph(gpu_ctx, main, lobes):
     fresh inputs; the replays are held, as bits, against direct calls"""
     import torch
     lib = _lib.load()
-    dev = _dev(gpu_ctx)
     n = 8192
     lobe = lobes["ggx"]
     so, su1, su2 = cases.sampler_inputs()
@@ -381,40 +312,21 @@ def test_calls_replay_from_a_captured_graph(gpu_ctx, main, lobes):
         sl = slice(lo_, lo_ + n)
         return (np.array(ids_a), np.array(ids_b), su1[sl], su2[sl], so[sl], li[sl], lo[sl])
     sets = [data(0, all_ids[:n], all_ids[n:2 * n][::-1]), data(n, cases.mixed_light("merl")[0], all_ids[2 * n:3 * n])]
-    side = torch.cuda.Stream(device=gpu_ctx.device)
-    up = lambda a: torch.from_numpy(np.array(a.T if a.ndim == 2 else a, order="C")).to(dev)
-    with torch.cuda.stream(side):
-        ids0, ids1, u1, u2, o, i, o2 = (up(a) for a in sets[0])
-        vec = lambda: torch.zeros((3, n), dtype=torch.float32, device=dev)
-        sca = lambda: torch.zeros((n,), dtype=torch.float32, device=dev)
-        outs = [[vec(), vec(), sca(), vec(), sca()] for _ in range(2)]        # per id stream: weight, i, pdf; fr, pdf
-        view = lambda t: _view(t.data_ptr(), n, "dense")
-        vo, vi, vo2 = view(o), view(i), view(o2)
+    ids0, ids1, u1, u2, o, i, o2 = (resident(gpu_ctx, a) for a in sets[0])
+    vec = lambda: torch.zeros((3, n), dtype=torch.float32, device=dev(gpu_ctx))
+    sca = lambda: torch.zeros((n,), dtype=torch.float32, device=dev(gpu_ctx))
+    outs = [[vec(), vec(), sca(), vec(), sca()] for _ in range(2)]        # per id stream: weight, i, pdf; fr, pdf
+    dense = lambda t: view(t.data_ptr(), n, "dense")
+    vo, vi, vo2 = dense(o), dense(i), dense(o2)
 
-        def launch():
-            for ids, (w, si, pdf, fr, lpdf) in zip((ids0, ids1), outs):
-                _lib.check(lib.djb_scene_evalp_is_proxy_batch(gpu_ctx._h, main._h, lobe._h, C.c_int64(n), C.c_void_p(ids.data_ptr()), C.c_void_p(u1.data_ptr()),
-                                                              C.c_void_p(u2.data_ptr()), C.byref(vo), C.byref(view(w)), C.byref(view(si)),
-                                                              C.c_void_p(pdf.data_ptr()), C.c_int(_lib.MEM_DEVICE)))
-                _lib.check(lib.djb_scene_evalp_pdf_proxy_batch(gpu_ctx._h, main._h, lobe._h, C.c_int64(n), C.c_void_p(ids.data_ptr()), C.byref(vi), C.byref(vo2),
-                                                               C.byref(view(fr)), C.c_void_p(lpdf.data_ptr()), C.c_int(_lib.MEM_DEVICE)))
-
-        def load(which):
-            for dst, src in zip((ids0, ids1, u1, u2, o, i, o2), sets[which]):
-                dst.copy_(up(src))
-        flat = lambda: [a for per in outs for a in per]
-        want = []
-        for which in (0, 1):                # eager: the warm call, and the results to hold the replays against
-            load(which); launch(); side.synchronize()
-            want.append([a.clone() for a in flat()])
-        for a in flat():
-            a.zero_()
-        side.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=side):
-        launch()
-    for a in flat():                        # capture executes nothing
-        assert not a.any(), "a call ran during capture instead of being recorded"
+    def launch():
+        for ids, (w, si, pdf, fr, lpdf) in zip((ids0, ids1), outs):
+            _lib.check(lib.djb_scene_evalp_is_proxy_batch(gpu_ctx._h, main._h, lobe._h, C.c_int64(n), C.c_void_p(ids.data_ptr()), C.c_void_p(u1.data_ptr()),
+                                                          C.c_void_p(u2.data_ptr()), C.byref(vo), C.byref(dense(w)), C.byref(dense(si)),
+                                                          C.c_void_p(pdf.data_ptr()), C.c_int(_lib.MEM_DEVICE)))
+            _lib.check(lib.djb_scene_evalp_pdf_proxy_batch(gpu_ctx._h, main._h, lobe._h, C.c_int64(n), C.c_void_p(ids.data_ptr()), C.byref(vi), C.byref(vo2),
+                                                           C.byref(dense(fr)), C.c_void_p(lpdf.data_ptr()), C.c_int(_lib.MEM_DEVICE)))
+    want = graph_replay(gpu_ctx, launch, [a for per in outs for a in per], loads(gpu_ctx, (ids0, ids1, u1, u2, o, i, o2), sets))
     bits = lambda a: a.view(torch.int32)
     assert not torch.equal(bits(want[0][0]), bits(want[1][0])) and not torch.equal(bits(want[0][0]), bits(want[0][5]))
     # the direct calls themselves, against the oracle
@@ -424,53 +336,27 @@ def test_calls_replay_from_a_captured_graph(gpu_ctx, main, lobes):
     cases.assert_sample("direct call before capture, sampling", got[0:3], exp, cases.compared_sample(ids_a, cases.TABLE, exp[1], so[:n]))
     cases.assert_light("direct call before capture, light sample", got[8:10], cases.expected_light_on("ggx", ids_b, cases.TABLE, li[:n], lo[:n]),
                        cases.compared_light(ids_b, cases.TABLE, li[:n], lo[:n]))
-    for which in (0, 1):
-        with torch.cuda.stream(side):
-            load(which)
-        side.synchronize()
-        g.replay()
-        torch.cuda.synchronize()
-        for a, e in zip(flat(), want[which]):
-            assert torch.equal(bits(a), bits(e)), f"graph replay {which} differs from the direct call"
 
 
 # ------------------------------------------------------------------ 6. aliasing
 @pytest.mark.parametrize("layout", ["dense", "strided"])
 def test_in_place_calls_equal_out_of_place(gpu_ctx, main, lobes, layout):
     """index-aligned in-place views: out_i over o (sampling) and out_fr over i (the light sample)"""
-    import torch
-    lib = _lib.load()
-    dev = _dev(gpu_ctx)
     lobe = lobes["beckmann"]
-    up = lambda a: torch.from_numpy(np.array(a.T if layout == "dense" and a.ndim == 2 else a, order="C")).to(dev)
-    down = lambda t: (t.cpu().numpy().T if layout == "dense" and t.ndim == 2 else t.cpu().numpy())
     ids, o, u1, u2 = cases.mixed_sample("merl")
-    n = len(ids)
     want = _sample(main, lobe, ids, u1, u2, o, layout)
-    dids, do, d1, d2 = up(np.array(ids)), up(o), up(u1), up(u2)
-    w = torch.zeros_like(do); pdf = torch.zeros((n,), dtype=torch.float32, device=dev)
-    vo = _view(do.data_ptr(), n, layout)
-    _lib.check(lib.djb_scene_evalp_is_proxy_batch(gpu_ctx._h, main._h, lobe._h, C.c_int64(n), C.c_void_p(dids.data_ptr()), C.c_void_p(d1.data_ptr()),
-                                                  C.c_void_p(d2.data_ptr()), C.byref(vo), C.byref(_view(w.data_ptr(), n, layout)), C.byref(vo),
-                                                  C.c_void_p(pdf.data_ptr()), C.c_int(_lib.MEM_DEVICE)))               # out_i names o's arrays
-    torch.cuda.synchronize()
-    for name, g, e in zip(("weight", "i", "pdf"), (down(w), down(do), down(pdf)), want):
+    got = _sample(main, lobe, ids, u1, u2, o, layout, in_place=True)
+    for name, g, e in zip(("weight", "i", "pdf"), got, want):
         assert cases.same_bits(g, e).all(), f"sampling in place, {layout}: {name} differs from the out-of-place call"
     exp = cases.mixed_sample_expected("beckmann", "merl")
-    cases.assert_sample(f"sampling in place, {layout}, against the oracle", (down(w), down(do), down(pdf)), exp, cases.compared_sample(ids, cases.TABLE, exp[1], o))
+    cases.assert_sample(f"sampling in place, {layout}, against the oracle", got, exp, cases.compared_sample(ids, cases.TABLE, exp[1], o))
 
     ids, i, o = cases.mixed_light("merl")
     want = _light(main, lobe, ids, i, o, layout)
-    dids, di, do = up(np.array(ids)), up(i), up(o)
-    pdf = torch.zeros((n,), dtype=torch.float32, device=dev)
-    vi = _view(di.data_ptr(), n, layout)
-    _lib.check(lib.djb_scene_evalp_pdf_proxy_batch(gpu_ctx._h, main._h, lobe._h, C.c_int64(n), C.c_void_p(dids.data_ptr()), C.byref(vi),
-                                                   C.byref(_view(do.data_ptr(), n, layout)), C.byref(vi), C.c_void_p(pdf.data_ptr()),
-                                                   C.c_int(_lib.MEM_DEVICE)))                                            # out_fr names i's arrays
-    torch.cuda.synchronize()
-    for name, g, e in zip(("fr", "pdf"), (down(di), down(pdf)), want):
+    got = _light(main, lobe, ids, i, o, layout, in_place=True)
+    for name, g, e in zip(("fr", "pdf"), got, want):
         assert cases.same_bits(g, e).all(), f"light sample in place, {layout}: {name} differs from the out-of-place call"
-    cases.assert_light(f"light sample in place, {layout}, against the oracle", (down(di), down(pdf)), cases.mixed_light_expected("beckmann", "merl"),
+    cases.assert_light(f"light sample in place, {layout}, against the oracle", got, cases.mixed_light_expected("beckmann", "merl"),
                        cases.compared_light(ids, cases.TABLE, i, o))
 
 

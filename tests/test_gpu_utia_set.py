@@ -11,11 +11,11 @@ import pytest
 
 import utia_set_cases as cases
 from dj_brdf_amd import _lib, djb
+from hit_calls import Arrays, dev, graph_replay, loads, resident, view
 
 pytestmark = pytest.mark.gpu
 PREFIXES = (1, 3, 4, 5, 63, 64, 65, 255, 256, 257, 1023, 1025)
 LAYOUTS = ("host", "dense", "strided")
-CANARY = np.float32(-777.25)
 
 
 @pytest.fixture(scope="module")
@@ -30,47 +30,15 @@ def uset(gpu_ctx):
     s.close()
 
 
-def _dev(ctx):
-    return f"cuda:{ctx.device}"
-
-
-def _view(ptr, n_alloc, layout):
-    v = _lib.Vec3View()
-    if layout == "dense":                         # [3, n_alloc]
-        v.x, v.y, v.z, v.stride = ptr, ptr + 4 * n_alloc, ptr + 8 * n_alloc, 1
-    else:                                         # [n_alloc, 3]
-        v.x, v.y, v.z, v.stride = ptr, ptr + 4, ptr + 8, 3
-    return v
-
-
-def _call(s, ids, i, o, want_cos, layout, ctx=None):
-    """one call through the C ABI -> [n, 3]; the output has n + 1 units, the last one a canary"""
-    import torch
+def _call(s, ids, i, o, want_cos, layout, ctx=None, over=None):
+    """one call through the C ABI -> [n, 3]; over = "i" / "o": the output arrays are that input's arrays"""
     ctx = ctx or s.ctx
-    n = len(ids)
-    ids = np.array(ids, np.int32)                 # a writable copy: the cases' arrays are read-only
-    if layout == "host":
-        hi, ho = np.ascontiguousarray(i, np.float32), np.ascontiguousarray(o, np.float32)
-        out = np.full((n + 1, 3), CANARY, np.float32)
-        st = _lib.load().djb_utia_set_eval_batch(ctx._h, s._h, C.c_int64(n), C.c_void_p(ids.ctypes.data), C.byref(_view(hi.ctypes.data, n, "strided")),
-                                                 C.byref(_view(ho.ctypes.data, n, "strided")), C.c_int(want_cos), C.byref(_view(out.ctypes.data, n + 1, "strided")),
-                                                 C.c_int(_lib.MEM_HOST))
-        _lib.check(st)
-        res = out
-    else:
-        dev = _dev(ctx)
-        up = lambda a: torch.from_numpy(np.array(a.T if layout == "dense" else a, order="C")).to(dev)
-        dids, di, do = torch.from_numpy(ids).to(dev), up(i), up(o)
-        out = torch.full((3, n + 1) if layout == "dense" else (n + 1, 3), float(CANARY), dtype=torch.float32, device=dev)
-        st = _lib.load().djb_utia_set_eval_batch(ctx._h, s._h, C.c_int64(n), C.c_void_p(dids.data_ptr()), C.byref(_view(di.data_ptr(), n, layout)),
-                                                 C.byref(_view(do.data_ptr(), n, layout)), C.c_int(want_cos), C.byref(_view(out.data_ptr(), n + 1, layout)),
-                                                 C.c_int(_lib.MEM_DEVICE))
-        _lib.check(st)
-        torch.cuda.synchronize()
-        res = out.cpu().numpy()
-        res = res.T if layout == "dense" else res
-    assert (res[n] == CANARY).all(), f"{layout}, n = {n}: the unit behind the output was written"
-    return np.ascontiguousarray(res[:n])
+    A = Arrays(ctx, len(ids), layout)
+    pid, vi, vo = A.arr_in(ids, np.int32), A.vec_in(i), A.vec_in(o)
+    alias = {"i": vi, "o": vo}.get(over)
+    out = A.vec_out("fr") if alias is None else C.byref(alias)
+    _lib.check(_lib.load().djb_utia_set_eval_batch(ctx._h, s._h, C.c_int64(A.n), pid, C.byref(vi), C.byref(vo), C.c_int(want_cos), out, C.c_int(A.mem)))
+    return A.results("eval")["fr"] if alias is None else A.read(alias)
 
 
 # ------------------------------------------------------------------ 1. bits equal to the oracle selection
@@ -180,69 +148,32 @@ def test_a_wave_of_dead_hits_among_live_ones(uset):
 def test_calls_replay_from_a_captured_graph(gpu_ctx, uset):
     import torch
     lib = _lib.load()
-    dev = _dev(gpu_ctx)
     gids, gi, go = cases.grid_block()
     n = len(gids)
     ids2, _ = cases.material_ids()
     i2, o2 = cases.eval_inputs()
     ok2 = cases.defined(i2, o2)
     sets = [(gids, gi, go), (ids2[ok2][:n], i2[ok2][:n], o2[ok2][:n])]
-    side = torch.cuda.Stream(device=gpu_ctx.device)
-    up = lambda a: torch.from_numpy(np.array(a.T if a.ndim == 2 else a, order="C")).to(dev)
-    with torch.cuda.stream(side):
-        ids, i, o = (up(a) for a in sets[0])
-        outs = [torch.zeros((3, n), dtype=torch.float32, device=dev) for _ in range(4)]
-        vi, vo = _view(i.data_ptr(), n, "dense"), _view(o.data_ptr(), n, "dense")
-        vouts = [_view(a.data_ptr(), n, "dense") for a in outs]
+    ids, i, o = (resident(gpu_ctx, a) for a in sets[0])
+    outs = [torch.zeros((3, n), dtype=torch.float32, device=dev(gpu_ctx)) for _ in range(4)]
+    vi, vo = view(i.data_ptr(), n, "dense"), view(o.data_ptr(), n, "dense")
+    vouts = [view(a.data_ptr(), n, "dense") for a in outs]
 
-        def launch():                       # four device-memory calls
-            for k, vout in enumerate(vouts):
-                _lib.check(lib.djb_utia_set_eval_batch(gpu_ctx._h, uset._h, C.c_int64(n), C.c_void_p(ids.data_ptr()), C.byref(vi), C.byref(vo), C.c_int(k & 1),
-                                                       C.byref(vout), C.c_int(_lib.MEM_DEVICE)))
-
-        def load(which):
-            for dst, src in zip((ids, i, o), sets[which]):
-                dst.copy_(up(src))
-        want = []
-        for which in (0, 1):                # eager: the warm call, and the results to hold the replays against
-            load(which); launch(); side.synchronize()
-            want.append([a.clone() for a in outs])
-        for a in outs:
-            a.zero_()
-        side.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=side):
-        launch()
-    for a in outs:                          # capture executes nothing
-        assert not a.any(), "a call ran during capture instead of being recorded"
+    def launch():                           # four device-memory calls
+        for k, vout in enumerate(vouts):
+            _lib.check(lib.djb_utia_set_eval_batch(gpu_ctx._h, uset._h, C.c_int64(n), C.c_void_p(ids.data_ptr()), C.byref(vi), C.byref(vo), C.c_int(k & 1),
+                                                   C.byref(vout), C.c_int(_lib.MEM_DEVICE)))
+    want = graph_replay(gpu_ctx, launch, outs, loads(gpu_ctx, (ids, i, o), sets))
     assert want[0][1].abs().sum() > 0 and not torch.equal(want[0][1], want[1][1])
-    for which in (0, 1):
-        with torch.cuda.stream(side):
-            load(which)
-        side.synchronize()
-        g.replay()
-        torch.cuda.synchronize()
-        for a, e in zip(outs, want[which]):
-            assert torch.equal(a.view(torch.int32), e.view(torch.int32)), f"graph replay {which} differs from the direct call"
 
 
 # ------------------------------------------------------------------ 7. aliasing
 @pytest.mark.parametrize("layout", ["dense", "strided"])
 def test_in_place_call_equals_out_of_place(gpu_ctx, uset, layout):
-    import torch
     ids, i, o = cases.grid_block()
     n = len(ids)
-    dev = _dev(gpu_ctx)
     want = _call(uset, ids, i, o, 1, layout)
-    dids = torch.from_numpy(np.array(ids)).to(dev)
-    up = lambda a: torch.from_numpy(np.array(a.T if layout == "dense" else a, order="C")).to(dev)
-    di, do = up(i), up(o)
-    vi, vo = _view(di.data_ptr(), n, layout), _view(do.data_ptr(), n, layout)
-    _lib.check(_lib.load().djb_utia_set_eval_batch(gpu_ctx._h, uset._h, C.c_int64(n), C.c_void_p(dids.data_ptr()), C.byref(vi), C.byref(vo), C.c_int(1),
-                                                   C.byref(vi), C.c_int(_lib.MEM_DEVICE)))      # the output arrays are i's arrays
-    torch.cuda.synchronize()
-    got = di.cpu().numpy()
-    got = got.T if layout == "dense" else got
+    got = _call(uset, ids, i, o, 1, layout, over="i")      # the output arrays are i's arrays
     cases.assert_eval(f"in place, {layout}", got, want, np.ones(n, bool))
     cases.assert_eval(f"in place, {layout}, against the oracle", got, cases.grid_expected("evalp"), np.ones(n, bool))
 
@@ -251,23 +182,20 @@ def test_output_over_the_ids_equals_out_of_place(gpu_ctx, uset):
     """The ids are an input stream too: the x plane of the output is the id array itself, index-aligned.  Tier 1 declines the block's hits
     and tier 2 would re-read their ids after tier 1 wrote placeholders over them, so the call has to take the exact kernel -- with the
     default worklist, and with a worklist of 0 entries, where tier 2 would redo the whole batch."""
-    import torch
     ids, i, o = cases.grid_block()
     n = len(ids)
-    dev = _dev(gpu_ctx)
     want = _call(uset, ids, i, o, 1, "dense")
-    di, do = (torch.from_numpy(np.array(a.T, order="C")).to(dev) for a in (i, o))
-    vi, vo = _view(di.data_ptr(), n, "dense"), _view(do.data_ptr(), n, "dense")
+    A = Arrays(gpu_ctx, n, "dense")
+    vi, vo = A.vec_in(i), A.vec_in(o)
     try:
         for cap in (-1, 0):
             djb.set_test_worklist_cap(gpu_ctx, cap)
-            host = np.zeros((3, n), np.float32)
-            host.view(np.int32)[0] = ids                   # plane 0: the int32 bits of the ids
-            buf = torch.from_numpy(host).to(dev)
-            _lib.check(_lib.load().djb_utia_set_eval_batch(gpu_ctx._h, uset._h, C.c_int64(n), C.c_void_p(buf.data_ptr()), C.byref(vi), C.byref(vo), C.c_int(1),
-                                                           C.byref(_view(buf.data_ptr(), n, "dense")), C.c_int(_lib.MEM_DEVICE)))
-            torch.cuda.synchronize()
-            got = buf.cpu().numpy().T
+            host = np.zeros((n, 3), np.float32)
+            host.view(np.int32)[:, 0] = ids                # plane 0: the int32 bits of the ids
+            vbuf = A.vec_in(host)
+            _lib.check(_lib.load().djb_utia_set_eval_batch(gpu_ctx._h, uset._h, C.c_int64(n), C.c_void_p(vbuf.x), C.byref(vi), C.byref(vo), C.c_int(1),
+                                                           C.byref(vbuf), C.c_int(A.mem)))
+            got = A.read(vbuf)
             cases.assert_eval(f"output over the ids, cap {cap}", got, want, np.ones(n, bool))
             cases.assert_eval(f"output over the ids, cap {cap}, against the oracle", got, cases.grid_expected("evalp"), np.ones(n, bool))
     finally:
